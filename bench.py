@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the OcRF render + BEV-pool + HOA hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the hot path (ocrfdet_amd.hotpath.HotPath.step) over one batch of
 synthetic input (seeded) that is already resident in HBM.  Rank 0 prints ONE JSON
 line; `value` = BEV voxels written per second by the whole job (both pools executed per voxel
-grid), with `roofline` for the dominant kernel (HIP-event timed inside the timed region) and
-`cpu_baseline` (the C oracle on this box's host cores, rank 0, N=1 only).
+grid), with `roofline` for the dominant kernel (HIP-event timed over one more block of the step,
+right before the timed region) and `cpu_baseline` (the C oracle on this box's host cores, rank 0,
+N=1 only).  The timed region is exactly K steps; `ms_per_step` is the time per step of its median
+block.  `--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy.
 
 N > 1 (`--shard`):
   camera_frames (default) — BASELINE.json north_star: the camera-frames of ONE sample over ALL ranks
@@ -26,6 +28,7 @@ N > 1 (`--shard`):
 import argparse
 import json
 import os
+import random
 import sys
 import time
 
@@ -42,6 +45,8 @@ BLEND_FLOPS_PER_PIXEL_RECORD = 20.0      # blend flops ~= 20 x s
 PMC_FILE = os.path.join('profiles', 'r6_pmc_mean.csv')     # rocprofv3 --pmc passes of this same command (tools/collect_profiles.sh)
 PMC_META = os.path.join('profiles', 'r6_pmc_meta.json')    # what those passes ran: config, flags, hash of csrc/
 DEFAULT_CONFIG = 'cfg2_6cam_2frame_bev200x200_render_hoa'
+MIN_BLOCK_STEPS = 20            # timed steps per block at the least (a block's fill and drain are amortised over them)
+DUMP_BYTES = 63 * 10 ** 6      # --dump-outputs: the data of all arrays, with room for the .npy headers in 64 MB
 
 
 def parse():
@@ -51,8 +56,9 @@ def parse():
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--config', default=DEFAULT_CONFIG)
     ap.add_argument('--blocks', type=int, default=0,
-                    help='timed blocks of --steps steps (the median block is reported); 0 = 9 blocks of up to 50 steps, else 5: a short '
-                         'block is 5 ms of device time and one noisy neighbour on the host moves it by 10 %')
+                    help='the --steps timed steps are split into this many blocks (the median block\'s time per step is reported); '
+                         '0 = one block per ' + str(MIN_BLOCK_STEPS) + ' steps, at most 9: one noisy neighbour on the host moves a '
+                         'short block by 10 %%, the median keeps it out of the figure')
     ap.add_argument('--cpu-seconds', type=float, default=12.0, help='CPU-baseline sample budget')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--shard', choices=('camera_frames', 'samples', 'frames', 'cameras'), default='camera_frames')
@@ -100,7 +106,13 @@ def parse():
     ap.add_argument('--index-prep', choices=('cached', 'per_step'), default='cached',
                     help="'per_step': rank vectors recomputed by the HIP index preparation inside every step "
                          "(the reference with accelerate=False); 'cached': once per calibration (accelerate=True)")
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, '
+                         'at most 64 MB in all: a larger output is written as a fixed, seeded sample of its flattened elements)')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 def _hoa_params(hp):
@@ -327,6 +339,12 @@ def bench_neck(args, cfg, dev, world, rank):
         step = neck.step_graphed
         for _ in range(3):
             step()
+    last_out = [None]
+    if args.dump_outputs:
+        issue = step
+
+        def step():
+            last_out[0] = issue()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier(group=CONTROL)
@@ -338,6 +356,9 @@ def bench_neck(args, cfg, dev, world, rank):
         dist.barrier(group=CONTROL)
     elapsed = time.perf_counter() - t0
     neck.module.check_render()        # render_guard='host': one status read verifies every render of the timed region
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(last_out[0], ('bev', 'depth', 'bev_mask', 'extras'), args.dump_outputs)
     # kernel events cannot bracket launches inside a graph replay: the pooling kernel is timed over a
     # short eager run of the same step right after the timed region
     timer = _lib.KernelTimer(_lib.K_BEV_POOL_FWD, 64)
@@ -385,6 +406,8 @@ def bench_neck(args, cfg, dev, world, rank):
                             'note': 'kernel timed over an eager run of the same step right after the timed region '
                                     '(HIP events cannot bracket a launch inside a graph replay)'},
                'cpu_baseline': None}
+        if dumped is not None:
+            out['outputs_dumped'] = {'dir': args.dump_outputs, 'arrays': dumped}
         emit(out)
     timer.close()
     if world > 1:
@@ -636,6 +659,59 @@ def emit(obj):
         os.write(_REAL_STDOUT, line)
 
 
+def _output_arrays(out, name, acc, seen):
+    """The tensors a step returned, depth first, as (name, tensor); a tensor object met twice is listed once."""
+    if torch.is_tensor(out):
+        if id(out) not in seen:
+            seen.add(id(out))
+            acc.append((name, out))
+    elif isinstance(out, dict):
+        for k, v in out.items():
+            _output_arrays(v, f'{name}.{k}', acc, seen)
+    elif isinstance(out, (list, tuple)):
+        for i, v in enumerate(out):
+            _output_arrays(v, f'{name}.{i}', acc, seen)
+    return acc
+
+
+def dump_outputs(out, names, directory):
+    """--dump-outputs: the step's outputs as ``directory/<name>.npy``; floating point as float32 (float64 stays float64),
+    integers and flags as float64.  If they hold more than DUMP_BYTES, the budget is shared out smallest array first:
+    an array that fits its share is written whole, a larger one as the elements at a fixed, seeded sample of its
+    flattened indices (ascending; the seed is the CRC-32 of its name), so two runs of the same arguments write the same
+    positions.  -> {name: {'shape', 'elements', 'written'}} for the result line."""
+    import zlib
+    import numpy as np
+    acc, seen = [], set()
+    top = list(out) if isinstance(out, (list, tuple)) else [out]
+    for i, o in enumerate(top):
+        _output_arrays(o, names[i] if i < len(names) else f'out{i}', acc, seen)
+    if any(t.is_cuda for _, t in acc):
+        torch.cuda.synchronize()
+    arrays = []
+    for name, t in acc:
+        t = t.detach()
+        dt = torch.float32 if (t.is_floating_point() and t.dtype != torch.float64) else torch.float64
+        arrays.append((name, t, dt, 4 if dt == torch.float32 else 8))
+    os.makedirs(directory, exist_ok=True)
+    left, todo, info = DUMP_BYTES, len(arrays), {}
+    for name, t, dt, size in sorted(arrays, key=lambda a: (a[1].numel() * a[3], a[0])):
+        n = t.numel()
+        keep = min(n, max(0, (left // todo) // size))
+        flat = t.reshape(-1)
+        if keep < n:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(n, keep, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            arr = flat.to(dt).cpu().numpy()
+        else:
+            arr = t.to(dt).cpu().numpy()
+        np.save(os.path.join(directory, name + '.npy'), arr)
+        left -= arr.nbytes
+        todo -= 1
+        info[name] = {'shape': list(t.shape), 'elements': n, 'written': int(arr.size)}
+    return info
+
+
 def main():
     args = parse()
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -647,6 +723,7 @@ def main():
     os.dup2(2, 1)
     rank = int(os.environ.get('RANK', '0'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
+    random.seed(rank)               # the neck's random render camera per sample: the same choices in every run
     single_dev = os.environ.get('OCRF_BENCH_SINGLE_DEVICE') == '1'      # plumbing test: all ranks on cuda:0 (gloo)
     if single_dev:
         local_rank = 0
@@ -754,27 +831,41 @@ def main():
         return fused
 
     step = {'camera_frames': (lambda: sp.step(sp_inputs)), 'cameras': step_cameras}.get(shard, step_whole)
+    last_out = [None]
+    if args.dump_outputs:
+        issue = step
+
+        def step():
+            last_out[0] = issue()
     for _ in range(args.warmup):
         step()
-    # device duration of the kernels of interest, HIP events on their launch stream inside the timed region
+    # device duration of the kernels of interest, HIP events on their launch stream (armed below)
     t_blend = _lib.KernelTimer(k_blend, 2 * args.steps + 8) if cfg.render else None
     t_pool = _lib.KernelTimer(_lib.K_BEV_POOL_FWD, 2 * (cfg.batch * cfg.n_frames if sp else 1) * args.steps + 8)
     t_mfma = _lib.KernelTimer(_lib.K_BEV_POOL_MFMA, 2 * (cfg.batch * cfg.n_frames if sp else 1) * args.steps + 8)
     t_panel = _lib.KernelTimer(_lib.K_BEV_POOL_PANEL, 2 * (cfg.batch * cfg.n_frames if sp else 1) * args.steps + 8)
     t_cw = _lib.KernelTimer(_lib.K_BEV_POOL_CELL_WEIGHTS, 2 * (cfg.batch * cfg.n_frames if sp else 1) * args.steps + 8)
+    # the --steps timed steps in blocks of as equal a length as may be, each bracketed like the contract says; the
+    # reported time per step is the MEDIAN block's (ms_per_step x steps = elapsed), min / max beside it
+    n_blocks = args.blocks if args.blocks > 0 else min(9, args.steps // MIN_BLOCK_STEPS)
+    n_blocks = max(1, min(n_blocks, args.steps))
+    block_steps = [args.steps // n_blocks + (k < args.steps % n_blocks) for k in range(n_blocks)]
+    # the kernel timers cover a block of their own, right BEFORE the timed region: the events they record around every
+    # launch of interest slow the step they bracket down by ~10 %
     for t in (t_blend, t_pool, t_mfma, t_panel, t_cw):
         if t is not None:
             t.arm()
-    # K blocks of `steps` steps, each bracketed like the contract says; the reported block is the MEDIAN one
-    # (ms_per_step x steps = that block), min / max beside it.  The kernel timers cover the first block.
-    blocks = [timed(step, args.steps, world, dev)]
+    timed(step, min(args.steps, 50), world, dev)
     _lib.KernelTimer.disarm_all()
-    n_blocks = args.blocks if args.blocks > 0 else (9 if args.steps <= 50 else 5)
-    for _ in range(max(1, n_blocks) - 1):
-        blocks.append(timed(step, args.steps, world, dev))
-    elapsed = sorted(blocks)[len(blocks) // 2]
-    # planned renders with the host guard: ONE status read per plan verifies every render of the warm-up and the timed
-    # region (raises if a Gaussian left the plans' extent bound: those renders would not be valid)
+    blocks = [timed(step, n, world, dev) / n for n in block_steps]
+    elapsed = sorted(blocks)[len(blocks) // 2] * args.steps
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        names = {'camera_frames': ('fused', 'rendered', 'gated', 'opacity_bev'), 'cameras': ('fused',)}.get(
+            shard, ('lss', 'ht') + (('rendered',) if cfg.render else ()) + (('gated', 'opacity_bev') if cfg.hoa else ()))
+        dumped = dump_outputs(last_out[0], names, args.dump_outputs)
+    # planned renders with the host guard: ONE status read per plan verifies every render of the warm-up, the timer
+    # block and the timed region (raises if a Gaussian left the plans' extent bound: those renders would not be valid)
     hp.check_render_plans()
     for sub in (sp.subs.values() if sp is not None else ()):
         sub.check_render_plans()
@@ -1183,9 +1274,9 @@ def main():
             'rendered_views_per_sec': views / elapsed,
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
             'ms_per_step': 1e3 * elapsed / args.steps,
-            'ms_per_step_blocks': {'n': len(blocks), 'median': 1e3 * elapsed / args.steps,
-                                   'min': 1e3 * min(blocks) / args.steps, 'max': 1e3 * max(blocks) / args.steps,
-                                   'in_order': [round(1e3 * b / args.steps, 5) for b in blocks]},
+            'ms_per_step_blocks': {'n': len(blocks), 'steps': block_steps, 'median': 1e3 * elapsed / args.steps,
+                                   'min': 1e3 * min(blocks), 'max': 1e3 * max(blocks),
+                                   'in_order': [round(1e3 * b, 5) for b in blocks]},
             'per_step_ms': per_step_ms,
             'per_step_device_geometry_ms': per_step_devgeom_ms,
             # a sample with a NEW POSE (the reference's only working mode: cameras per sample, accelerate=False): rank
@@ -1251,6 +1342,8 @@ def main():
             out['samples_layout'] = samples_layout
         if pipelined_layout is not None:
             out['pipelined_camera_frames'] = pipelined_layout
+        if dumped is not None:
+            out['outputs_dumped'] = {'dir': args.dump_outputs, 'arrays': dumped}
         if world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(hp, depth, feat, args.cpu_seconds)
             out['gpu_over_cpu'] = out['value'] / out['cpu_baseline']['value']
