@@ -439,6 +439,57 @@ int ocrf_sh_to_rgb_backward(int P, int deg, int max_coeffs, const float *means3D
                             float *dL_dmeans3D, float *dL_dshs, ocrf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Training losses of the neck (csrc/losses.hip): view_transformer_ocrf.py get_loss (:1354-1417) and its helpers.
+ * Deterministic: per-block partials, then one fixed-order final sum; no float atomics.  No entry writes its inputs.
+ *
+ * ocrf_depth_labels (get_downsampled_gt_depth_and_semantic, :1203-1282): gt_depth / gt_semantic (BN,H,W) f32, H and W
+ *   multiples of ds -> depth_labels (BN*h*w, D) and semantic_labels (BN*h*w, 2), h = H/ds, w = W/ds.  Depths outside
+ *   [d_min, d_max] (strict comparisons) and their semantics count as 0; the bin is (m - (float)(d_min - d_step)) /
+ *   (float)d_step; rows whose semantic max is 1 get the normalised histogram of the patch's depth x semantic bins
+ *   (NaN when it is empty, as the reference).  Bit for bit the reference's labels.
+ * ocrf_depth_semantic_loss (get_depth_and_semantic_loss, :1284-1314): depth (BN,D,h,w) and semantic (BN,2,h,w) softmax
+ *   outputs in NCHW, HW = h*w.  out[0] = w_depth * sum BCE * w / max(0.1, sum w), out[1] = w_semantic * focal BCE /
+ *   max(1, rows) over the rows whose depth label max is > 0; denoms[2] (device) keeps the two divisors for the backward.
+ *   Two launches; workspace from ocrf_depth_semantic_loss_workspace_bytes(BN*HW).
+ * ocrf_depth_semantic_loss_backward: grad_out (2 floats, device) -> grad_depth (BN,D,h,w), grad_semantic (BN,2,h,w),
+ *   every element written.
+ * ocrf_render_losses (the per-sample loop of get_loss, :1370-1410): K (1..3) renders r0..r2 (B,C,H,W) against gt
+ *   (>= B,C,H,W), all multiplied by the Box2dtoMask mask of boxes (B,n_max,4) (n_max <= 256) when use_mask; meta (int,
+ *   device): [0,B) box counts, [B,2B) camera of each sample.  With gt_depth (B,n_cams,H,W) also the depth L1 of rd0..rd2
+ *   (B,1,H,W) against the range-zeroed, min-max normalised gt depth of the sample's camera (gt_depth NULL: no depth
+ *   term).  out[3] (device) = {w_color * mean MSE, w_ssim * mean (1 - SSIM), w_depth * mean L1}, means over samples and
+ *   renders; SSIM window 11, sigma 1.5, zero padding.  saved (B*C*K*3*H*W floats) and depth_stats (2B floats) are the
+ *   state of the backward.  Three launches (two without the depth term); workspace from
+ *   ocrf_render_losses_workspace_bytes(B, C, H, W).
+ * ocrf_render_losses_backward: the same arguments + saved state and grad_out (3 floats, device) -> grad_r0..2 (B,C,H,W)
+ *   and grad_rd0..2 (B,1,H,W); NULL outputs are skipped.  One launch.
+ */
+int ocrf_depth_labels(int BN, int H, int W, int ds, int D, double d_min, double d_max, double d_step,
+                      const float *gt_depth, const float *gt_semantic, float *depth_labels, float *semantic_labels,
+                      ocrf_stream_t stream);
+size_t ocrf_depth_semantic_loss_workspace_bytes(int rows);
+int ocrf_depth_semantic_loss(int BN, int HW, int D, const float *depth_labels, const float *semantic_labels,
+                             const float *depth, const float *semantic, float w_depth, float w_semantic, float *out,
+                             float *denoms, void *workspace, size_t workspace_bytes, ocrf_stream_t stream);
+int ocrf_depth_semantic_loss_backward(int BN, int HW, int D, const float *depth_labels, const float *semantic_labels,
+                                      const float *depth, const float *semantic, float w_depth, float w_semantic,
+                                      const float *denoms, const float *grad_out, float *grad_depth,
+                                      float *grad_semantic, ocrf_stream_t stream);
+size_t ocrf_render_losses_workspace_bytes(int B, int C, int H, int W);
+int ocrf_render_losses(int B, int K, int C, int H, int W, const float *gt, const float *r0, const float *r1,
+                       const float *r2, const float *boxes, const int *meta, int n_max, int use_mask,
+                       const float *gt_depth, int n_cams, const float *rd0, const float *rd1, const float *rd2,
+                       float d_min, float d_max, float w_color, float w_ssim, float w_depth, float *out, float *saved,
+                       float *depth_stats, void *workspace, size_t workspace_bytes, ocrf_stream_t stream);
+int ocrf_render_losses_backward(int B, int K, int C, int H, int W, const float *gt, const float *r0, const float *r1,
+                                const float *r2, const float *boxes, const int *meta, int n_max, int use_mask,
+                                const float *gt_depth, int n_cams, const float *rd0, const float *rd1, const float *rd2,
+                                float d_min, float d_max, float w_color, float w_ssim, float w_depth, const float *saved,
+                                const float *depth_stats, const float *grad_out, float *grad_r0, float *grad_r1,
+                                float *grad_r2, float *grad_rd0, float *grad_rd1, float *grad_rd2,
+                                ocrf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Index preparation of the two poolings on the device (csrc/index_prep.hip).
  *
  * ocrf_lss_prepare replaces get_lidar_coor + voxel_pooling_prepare_v2
@@ -815,7 +866,14 @@ enum {
   OCRF_K_RASTER_SH = 50,         /* sh_colors_kernel */
   OCRF_K_RASTER_SH_BWD = 51,     /* sh_colors_backward_kernel */
   OCRF_K_NECK_HEADS_BWD = 71,    /* neck_gauss_heads_backward_kernel */
-  OCRF_K_NECK_HEADS_BWD_SUM = 72 /* neck_partial_rows_sum_kernel (both stages) */
+  OCRF_K_NECK_HEADS_BWD_SUM = 72, /* neck_partial_rows_sum_kernel (both stages) */
+  OCRF_K_LOSS_DEPTH_LABELS = 80, /* depth_labels_kernel */
+  OCRF_K_LOSS_DS = 81,           /* ds_loss_partial_kernel */
+  OCRF_K_LOSS_FINAL = 82,        /* ds_loss_final_kernel, render_final_kernel */
+  OCRF_K_LOSS_DS_BWD = 83,       /* ds_loss_backward_kernel */
+  OCRF_K_LOSS_RENDER = 84,       /* render_tile_kernel */
+  OCRF_K_LOSS_RENDER_DEPTH = 85, /* render_depth_kernel */
+  OCRF_K_LOSS_RENDER_BWD = 86    /* render_backward_kernel */
 };
 const char *ocrf_kernel_name(int kernel_id);           /* symbol as rocprofv3 prints it */
 /* Diagnostic: a one-thread kernel that stores the device's constant-rate clock (wall_clock64, 100 MHz)

@@ -206,6 +206,22 @@ def _declare(L):
     L.ocrf_gauss_heads.argtypes = [c_void_p] * 3 + [c_int] * 4 + [c_void_p] * 5
     L.ocrf_gauss_heads_params_len.restype = c_int
     L.ocrf_gauss_heads_params_len.argtypes = [c_int, c_int]
+    c_double = ctypes.c_double
+    L.ocrf_depth_labels.restype = c_int
+    L.ocrf_depth_labels.argtypes = [c_int] * 5 + [c_double] * 3 + [c_void_p] * 5
+    L.ocrf_depth_semantic_loss_workspace_bytes.restype = c_size_t
+    L.ocrf_depth_semantic_loss_workspace_bytes.argtypes = [c_int]
+    L.ocrf_depth_semantic_loss.restype = c_int
+    L.ocrf_depth_semantic_loss.argtypes = [c_int] * 3 + [c_void_p] * 4 + [c_float] * 2 + [c_void_p] * 3 + [c_size_t, c_void_p]
+    L.ocrf_depth_semantic_loss_backward.restype = c_int
+    L.ocrf_depth_semantic_loss_backward.argtypes = [c_int] * 3 + [c_void_p] * 4 + [c_float] * 2 + [c_void_p] * 5
+    L.ocrf_render_losses_workspace_bytes.restype = c_size_t
+    L.ocrf_render_losses_workspace_bytes.argtypes = [c_int] * 4
+    _render = [c_int] * 5 + [c_void_p] * 6 + [c_int] * 2 + [c_void_p, c_int] + [c_void_p] * 3 + [c_float] * 5
+    L.ocrf_render_losses.restype = c_int
+    L.ocrf_render_losses.argtypes = _render + [c_void_p] * 4 + [c_size_t, c_void_p]
+    L.ocrf_render_losses_backward.restype = c_int
+    L.ocrf_render_losses_backward.argtypes = _render + [c_void_p] * 9 + [c_void_p]
     L.ocrf_sh_to_rgb.restype = c_int
     L.ocrf_sh_to_rgb.argtypes = [c_int] * 3 + [c_void_p] * 6
     L.ocrf_sh_to_rgb_backward.restype = c_int

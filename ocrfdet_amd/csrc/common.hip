@@ -131,6 +131,13 @@ const char* ocrf_kernel_name(int kernel_id) {
     case OCRF_K_NECK_CHANNEL_MLP: return "neck_channel_mlp_kernel";
     case OCRF_K_NECK_SCALED_STATS: return "neck_scaled_channel_stats_kernel";
     case OCRF_K_NECK_CBAM_TAIL: return "neck_cbam_tail_kernel";
+    case OCRF_K_LOSS_DEPTH_LABELS: return "depth_labels_kernel";
+    case OCRF_K_LOSS_DS: return "ds_loss_partial_kernel";
+    case OCRF_K_LOSS_FINAL: return "ds_loss_final_kernel / render_final_kernel";
+    case OCRF_K_LOSS_DS_BWD: return "ds_loss_backward_kernel";
+    case OCRF_K_LOSS_RENDER: return "render_tile_kernel";
+    case OCRF_K_LOSS_RENDER_DEPTH: return "render_depth_kernel";
+    case OCRF_K_LOSS_RENDER_BWD: return "render_backward_kernel";
     default: return "";
   }
 }

@@ -34,7 +34,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import _lib, bevpool, gaussian_renderer, hoa, index_prep, neck_ops
+from . import _lib, bevpool, gaussian_renderer, hoa, index_prep, losses, neck_ops
 from .diff_gaussian_rasterization import pack_cameras, rasterize_packed_autograd, rasterize_sets
 
 __all__ = ['OcRFViewTransformerFull', 'GraphedNeck', 'MS_CAM', 'ChannelAttention', 'SpatialAttention', 'ResCBAMBlock', 'ProbNet',
@@ -206,6 +206,34 @@ class ProbNet(nn.Module):
                 self.__dict__['_pack_key'] = key
             return neck_ops.probnet_forward(input, self.__dict__['_pack'])
         return self.mask_net(self.prob_conv(self.base_conv(input)))
+
+    def _centerness_on(self, device):
+        """``centerness`` on the loss's device, copied once per device (the reference keeps it on the GPU, :166)."""
+        c = self.__dict__.get('_centerness_dev')
+        if c is None or c.device != device:
+            c = self.__dict__['_centerness_dev'] = self.centerness.to(device)
+        return c
+
+    def _mask_losses(self, gt_bev_mask, pred_bev_mask, dice):
+        """Centerness-weighted BCE with logits (pos_weight 2.13) + Dice over B x Y x X maps (:177-201), without the
+        reference's switch of ``ce_loss.reduction`` as a side effect."""
+        bs, bev_h, bev_w = gt_bev_mask.shape
+        b = gt_bev_mask.reshape(bs, bev_w * bev_h).permute(1, 0).to(torch.float)
+        a = pred_bev_mask.reshape(bs, bev_w * bev_h).permute(1, 0)
+        if self.with_centerness:
+            tmp = F.binary_cross_entropy_with_logits(a, b, pos_weight=self.ce_loss.pos_weight, reduction='none')
+            ce = (tmp * self._centerness_on(a.device).reshape(bev_w * bev_h, 1)).mean()
+        else:
+            ce = self.ce_loss(a, b)
+        return ce, dice(pred_bev_mask.reshape(bs, -1), gt_bev_mask.reshape(bs, -1))
+
+    def get_bev_mask_loss(self, gt_bev_mask, pred_bev_mask):
+        ce, dice = self._mask_losses(gt_bev_mask, pred_bev_mask, self.dice_loss)
+        return dict(mask_ce_loss=self.loss_weight * ce, mask_dice_loss=dice)
+
+    def get_bev_opacity_loss(self, gt_bev_mask, pred_bev_mask):
+        ce, dice = self._mask_losses(gt_bev_mask, pred_bev_mask, self.dice_loss_opacity)
+        return dict(mask_ce_opacity_loss=self.loss_weight_opacity * ce, mask_dice_opacity_loss=dice)
 
 
 class DualFeatFusion(nn.Module):
@@ -507,6 +535,12 @@ class OcRFViewTransformerFull(nn.Module):
         self.fork_ht_prep = True         # per-forward geometry: HT preparation + pooling beside the LSS pair (see _core_segments)
         self._rank_bufs = (index_prep._RankBuffers(), index_prep._RankBuffers())
         self._packs = {}
+        # training losses (get_loss) by the fused HIP kernels of csrc/losses.hip; False: their torch formulation (also
+        # taken on the CPU and when a gt tensor requires grad)
+        self.fused_losses = True
+        # calls of get_loss so far: the box mask applies once it passes 3862 * 2 (:1375).  Per instance, where the
+        # reference keeps a module-global counter; settable, not part of the state_dict
+        self.loss_iteration = 0
 
     def _recording(self, *tensors):
         if not torch.is_grad_enabled():
@@ -1193,6 +1227,61 @@ class OcRFViewTransformerFull(nn.Module):
                 and all(type(m) is cls and m.fc1.in_features == cin and m.fc1.out_features == 4
                         and m.fc2.out_features == cout and m.fc1.bias is not None and m.fc2.bias is not None
                         for m, cls, cin, cout in heads))
+
+    # -------------------------------------------------------------------------------- training losses
+    def _fused_loss_inputs(self, *tensors):
+        return self.fused_losses and all(t.is_cuda for t in tensors)
+
+    def get_downsampled_gt_depth_and_semantic(self, gt_depths, gt_semantics):
+        """:1203-1282 -> (depth_labels (B*N*h*w, D), semantic_labels (B*N*h*w, 2)).  The gt tensors are not written
+        (the reference zeroes their out-of-range depths in place)."""
+        if self._fused_loss_inputs(gt_depths, gt_semantics) and not (gt_depths.requires_grad or gt_semantics.requires_grad):
+            return losses.depth_labels(gt_depths, gt_semantics, self.grid_config['depth'], self.D, self.downsample)
+        return losses.depth_labels_torch(gt_depths, gt_semantics, self.grid_config['depth'], self.D, self.downsample)
+
+    def get_depth_and_semantic_loss(self, depth_labels, depth_preds, semantic_labels, semantic_preds):
+        """:1284-1314 -> (loss_depth_weight * depth BCE, loss_semantic_weight * focal BCE); no host read."""
+        if (self._fused_loss_inputs(depth_labels, depth_preds, semantic_labels, semantic_preds)
+                and not (depth_labels.requires_grad or semantic_labels.requires_grad)):
+            return losses.depth_semantic_loss(depth_labels, depth_preds, semantic_labels, semantic_preds,
+                                              self.loss_depth_weight, self.loss_semantic_weight)
+        return losses.depth_semantic_loss_torch(depth_labels, depth_preds.float(), semantic_labels,
+                                                semantic_preds.float(), self.loss_depth_weight, self.loss_semantic_weight)
+
+    def depth_l1_loss(self, pred_depth, gt_depth):
+        return F.l1_loss(pred_depth, gt_depth)
+
+    def Box2dtoMask(self, gt_bboxes, new_width, new_height, device=None):
+        """:1337-1352 -> (1,3,H,W) float mask on ``device`` (default: the boxes' device), without a host loop."""
+        m = losses.box_mask(gt_bboxes, new_width, new_height, device)
+        return m.view(1, 1, new_height, new_width).repeat(1, 3, 1, 1)
+
+    def get_loss(self, depth, semantic, gt_depth, gt_semantic, gt_bboxes, cam_idx_list, render_imgs, gt_images,
+                 render_image_G_all, render_image_N_all, render_depth, render_depth_G_all, render_depth_N_all):
+        """:1354-1417 -> (loss_depth, loss_ce_semantic, color_loss, ssim_loss, render_depth_loss).  ``cam_idx_list``:
+        the forward's camera of each sample (host ints); ``gt_bboxes[b][cam]`` the (n,4) 2D boxes of that camera.
+        On the GPU the three parts run as the fused kernels of csrc/losses.hip: no host synchronisation.  Deviations
+        (INTEGRATION.md): the debug ``visualize_images`` call is dropped, the gt tensors are not written, the iteration
+        counter is ``self.loss_iteration``."""
+        self.loss_iteration += 1
+        use_mask = self.loss_iteration > losses.MASK_AFTER_ITERATION
+        depth_labels, semantic_labels = self.get_downsampled_gt_depth_and_semantic(gt_depth, gt_semantic)
+        loss_depth, loss_ce_semantic = self.get_depth_and_semantic_loss(depth_labels, depth, semantic_labels, semantic)
+        B = render_imgs.shape[0]
+        boxes = [gt_bboxes[b][cam_idx_list[b]] for b in range(B)]
+        renders = (render_imgs, render_image_G_all, render_image_N_all)
+        render_depths = (render_depth, render_depth_G_all, render_depth_N_all)
+        depth_range = self.grid_config['depth'][:2]
+        if (self._fused_loss_inputs(gt_images, gt_depth, *renders, *render_depths)
+                and not (gt_images.requires_grad or gt_depth.requires_grad)):
+            color_loss, ssim_loss, render_depth_loss = losses.render_losses(
+                gt_images, renders, render_depths, gt_depth, cam_idx_list, boxes, use_mask, depth_range)
+        else:
+            H, W = gt_images.shape[2:]
+            masks = [self.Box2dtoMask(bx, W, H, device=gt_images.device) if use_mask else None for bx in boxes]
+            color_loss, ssim_loss, render_depth_loss = losses.render_losses_torch(
+                gt_images, renders, render_depths, gt_depth, cam_idx_list, masks, depth_range)
+        return loss_depth, loss_ce_semantic, color_loss, ssim_loss, render_depth_loss
 
     # -------------------------------------------------------------------------------- forward
     def forward(self, input, stereo_metas=None):
