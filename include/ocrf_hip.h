@@ -490,6 +490,23 @@ int ocrf_render_losses_backward(int B, int K, int C, int H, int W, const float *
                                 ocrf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Stereo cost volume of the depth network (csrc/stereo.hip): view_transformer.py DepthNet.gen_grid +
+ * calculate_cost_volumn (:538-596), forward only (the reference runs it under no_grad).
+ *
+ * ocrf_stereo_cost_volume: prev, curr (BN,C,H,W) f32 contiguous, C >= 4 (channels past the last whole group of 4 are
+ *   ignored); the frustum's axes u[W], v[H], d[D] as strided views (element strides stride_*, e.g. the (D,H,W,3)
+ *   cv_frustum's [0,0,:,0], [0,:,0,1], [:,0,0,2]); per camera the raw k2s_sensor (BN,4,4), intrins (BN,3,3),
+ *   post_rots (BN,3,3) and post_trans (BN,3), contiguous.  The image size is (4 H, 4 W).  out (BN,D,H,W) NCHW:
+ *   mode 0 the softmax over D of raw, mode 1 raw = -(cost + bias [warped channel 4 (C/4 - 1) == 0]).  The 3x3 inverses
+ *   are taken in the kernel.  One launch, deterministic, no atomics.
+ */
+int ocrf_stereo_cost_volume(int BN, int C, int H, int W, int D, const float *prev, const float *curr,
+                            const float *frustum_u, long long stride_u, const float *frustum_v, long long stride_v,
+                            const float *frustum_d, long long stride_d, const float *k2s_sensor, const float *intrins,
+                            const float *post_rots, const float *post_trans, float bias, int mode, float *out,
+                            ocrf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Index preparation of the two poolings on the device (csrc/index_prep.hip).
  *
  * ocrf_lss_prepare replaces get_lidar_coor + voxel_pooling_prepare_v2
@@ -873,7 +890,8 @@ enum {
   OCRF_K_LOSS_DS_BWD = 83,       /* ds_loss_backward_kernel */
   OCRF_K_LOSS_RENDER = 84,       /* render_tile_kernel */
   OCRF_K_LOSS_RENDER_DEPTH = 85, /* render_depth_kernel */
-  OCRF_K_LOSS_RENDER_BWD = 86    /* render_backward_kernel */
+  OCRF_K_LOSS_RENDER_BWD = 86,  /* render_backward_kernel */
+  OCRF_K_STEREO_COST_VOLUME = 90 /* stereo_cost_volume_kernel */
 };
 const char *ocrf_kernel_name(int kernel_id);           /* symbol as rocprofv3 prints it */
 /* Diagnostic: a one-thread kernel that stores the device's constant-rate clock (wall_clock64, 100 MHz)

@@ -222,6 +222,10 @@ def _declare(L):
     L.ocrf_render_losses.argtypes = _render + [c_void_p] * 4 + [c_size_t, c_void_p]
     L.ocrf_render_losses_backward.restype = c_int
     L.ocrf_render_losses_backward.argtypes = _render + [c_void_p] * 9 + [c_void_p]
+    c_longlong = ctypes.c_longlong
+    L.ocrf_stereo_cost_volume.restype = c_int
+    L.ocrf_stereo_cost_volume.argtypes = ([c_int] * 5 + [c_void_p] * 2 + [c_void_p, c_longlong] * 3 + [c_void_p] * 4 +
+                                          [c_float, c_int, c_void_p, c_void_p])
     L.ocrf_sh_to_rgb.restype = c_int
     L.ocrf_sh_to_rgb.argtypes = [c_int] * 3 + [c_void_p] * 6
     L.ocrf_sh_to_rgb_backward.restype = c_int

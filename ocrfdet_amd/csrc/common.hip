@@ -138,6 +138,7 @@ const char* ocrf_kernel_name(int kernel_id) {
     case OCRF_K_LOSS_RENDER: return "render_tile_kernel";
     case OCRF_K_LOSS_RENDER_DEPTH: return "render_depth_kernel";
     case OCRF_K_LOSS_RENDER_BWD: return "render_backward_kernel";
+    case OCRF_K_STEREO_COST_VOLUME: return "stereo_cost_volume_kernel";
     default: return "";
   }
 }

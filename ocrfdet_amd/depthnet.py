@@ -1,0 +1,305 @@
+"""The stereo depth network of the neck: the reference's ``DepthNet`` (view_transformer.py:464-626) with its submodules
+``Mlp``, ``SELayer``, ``ASPP`` / ``_ASPPModule`` (:316-462) and mmdet 2.x's ``BasicBlock``, written from their structure
+with the same constructor arguments and the same ``state_dict`` keys and shapes.
+
+The convolutions are stock PyTorch-ROCm layers (MIOpen).  The one operation that is not a convolution, the stereo cost
+volume (``gen_grid`` + ``calculate_cost_volumn``, :538-596), has two formulations of the same arithmetic:
+
+* the fused one, ``ocrf_stereo_cost_volume`` (csrc/stereo.hip): one launch writes the softmax over depth, reading each
+  feature map about once; no warped (BN, 4, D*H, W) tensor per channel group, no host synchronisation;
+* the torch one, ``stereo_cost_volume_torch``: the CPU path, and the GPU path when ``DepthNet.fused_cost_volume`` is
+  False.  Its 3x3 inverses are closed-form as in the kernel, so it does not synchronise either.
+
+Both run under ``no_grad`` as in the reference (:617): the cost volume has no backward.  ``use_dcn=True`` needs mmcv's
+deformable convolution and is not supported.
+"""
+import torch
+import torch.nn.functional as F
+from torch import nn
+from torch.utils.checkpoint import checkpoint
+
+from . import _lib
+
+__all__ = ['BasicBlock', 'Mlp', 'SELayer', 'ASPP', '_ASPPModule', 'DepthNet', 'stereo_cost_volume',
+           'stereo_cost_volume_torch', 'stereo_cost_volume_hip', 'stereo_grid_torch', 'supports']
+
+GROUP = 4                   # channels per group of the reference's loop (:580)
+
+
+# --------------------------------------------------------------------------------------------- building blocks
+class BasicBlock(nn.Module):
+    """mmdet 2.x ``BasicBlock`` (expansion 1, pytorch style, BN): conv1 / bn1 / conv2 / bn2 / optional downsample."""
+    expansion = 1
+
+    def __init__(self, inplanes, planes, stride=1, dilation=1, downsample=None):
+        super().__init__()
+        self.conv1 = nn.Conv2d(inplanes, planes, 3, stride=stride, padding=dilation, dilation=dilation, bias=False)
+        self.bn1 = nn.BatchNorm2d(planes)
+        self.conv2 = nn.Conv2d(planes, planes, 3, padding=1, bias=False)
+        self.bn2 = nn.BatchNorm2d(planes)
+        self.relu = nn.ReLU(inplace=True)
+        self.downsample = downsample
+
+    def forward(self, x):
+        y = self.relu(self.bn1(self.conv1(x)))
+        y = self.bn2(self.conv2(y))
+        return self.relu(y + (x if self.downsample is None else self.downsample(x)))
+
+
+def _kaiming_init(module):
+    for m in module.modules():
+        if isinstance(m, nn.Conv2d):
+            nn.init.kaiming_normal_(m.weight)
+        elif isinstance(m, nn.BatchNorm2d):
+            nn.init.ones_(m.weight)
+            nn.init.zeros_(m.bias)
+
+
+class _ASPPModule(nn.Module):
+    """Atrous conv (no bias) + BN + ReLU."""
+
+    def __init__(self, inplanes, planes, kernel_size, padding, dilation, BatchNorm=nn.BatchNorm2d):
+        super().__init__()
+        self.atrous_conv = nn.Conv2d(inplanes, planes, kernel_size, stride=1, padding=padding, dilation=dilation,
+                                     bias=False)
+        self.bn = BatchNorm(planes)
+        self.relu = nn.ReLU()
+        _kaiming_init(self)
+
+    def forward(self, x):
+        return self.relu(self.bn(self.atrous_conv(x)))
+
+
+class ASPP(nn.Module):
+    """Four atrous branches (dilations 1, 6, 12, 18) and a global-pool branch, concatenated, 1x1 conv + BN + ReLU,
+    dropout 0.5."""
+
+    def __init__(self, inplanes, mid_channels=256, BatchNorm=nn.BatchNorm2d):
+        super().__init__()
+        for i, dil in enumerate((1, 6, 12, 18)):
+            k, pad = (1, 0) if dil == 1 else (3, dil)
+            setattr(self, f'aspp{i + 1}', _ASPPModule(inplanes, mid_channels, k, pad, dil, BatchNorm))
+        self.global_avg_pool = nn.Sequential(nn.AdaptiveAvgPool2d((1, 1)),
+                                             nn.Conv2d(inplanes, mid_channels, 1, stride=1, bias=False),
+                                             BatchNorm(mid_channels), nn.ReLU())
+        self.conv1 = nn.Conv2d(5 * mid_channels, inplanes, 1, bias=False)
+        self.bn1 = BatchNorm(inplanes)
+        self.relu = nn.ReLU()
+        self.dropout = nn.Dropout(0.5)
+        _kaiming_init(self)
+
+    def forward(self, x):
+        branches = [self.aspp1(x), self.aspp2(x), self.aspp3(x), self.aspp4(x)]
+        pooled = self.global_avg_pool(x)
+        branches.append(F.interpolate(pooled, size=branches[3].shape[2:], mode='bilinear', align_corners=True))
+        return self.dropout(self.relu(self.bn1(self.conv1(torch.cat(branches, dim=1)))))
+
+
+class Mlp(nn.Module):
+    """fc1 -> act -> dropout -> fc2 -> dropout."""
+
+    def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.ReLU, drop=0.0):
+        super().__init__()
+        hidden_features = hidden_features or in_features
+        out_features = out_features or in_features
+        self.fc1 = nn.Linear(in_features, hidden_features)
+        self.act = act_layer()
+        self.drop1 = nn.Dropout(drop)
+        self.fc2 = nn.Linear(hidden_features, out_features)
+        self.drop2 = nn.Dropout(drop)
+
+    def forward(self, x):
+        return self.drop2(self.fc2(self.drop1(self.act(self.fc1(x)))))
+
+
+class SELayer(nn.Module):
+    """x * sigmoid(expand(relu(reduce(x_se)))), both 1x1 convolutions with bias."""
+
+    def __init__(self, channels, act_layer=nn.ReLU, gate_layer=nn.Sigmoid):
+        super().__init__()
+        self.conv_reduce = nn.Conv2d(channels, channels, 1, bias=True)
+        self.act1 = act_layer()
+        self.conv_expand = nn.Conv2d(channels, channels, 1, bias=True)
+        self.gate = gate_layer()
+
+    def forward(self, x, x_se):
+        return x * self.gate(self.conv_expand(self.act1(self.conv_reduce(x_se))))
+
+
+# --------------------------------------------------------------------------------------------- cost volume
+def _inv3(m):
+    """Closed-form inverse of (..., 3, 3) matrices (adjugate / determinant): no LAPACK call, no ``info`` check, so no
+    host synchronisation on the GPU.  The same formula as the kernel's."""
+    a = [[m[..., i, j] for j in range(3)] for i in range(3)]
+    c00 = a[1][1] * a[2][2] - a[1][2] * a[2][1]
+    c01 = a[1][2] * a[2][0] - a[1][0] * a[2][2]
+    c02 = a[1][0] * a[2][1] - a[1][1] * a[2][0]
+    inv_det = 1.0 / (a[0][0] * c00 + a[0][1] * c01 + a[0][2] * c02)
+    rows = [[c00, a[0][2] * a[2][1] - a[0][1] * a[2][2], a[0][1] * a[1][2] - a[0][2] * a[1][1]],
+            [c01, a[0][0] * a[2][2] - a[0][2] * a[2][0], a[0][2] * a[1][0] - a[0][0] * a[1][2]],
+            [c02, a[0][1] * a[2][0] - a[0][0] * a[2][1], a[0][0] * a[1][1] - a[0][1] * a[1][0]]]
+    return torch.stack([torch.stack([e * inv_det for e in r], -1) for r in rows], -2)
+
+
+def _mv(m, x, y, z):
+    """Rows of m (BN, 1, 1, 1, 3, 3) applied to (x, y, z), k ascending."""
+    return tuple(m[..., i, 0] * x + m[..., i, 1] * y + m[..., i, 2] * z for i in range(3))
+
+
+def stereo_grid_torch(metas, H, W):
+    """Normalised sample grid (BN, D, H, W, 2) of ``gen_grid``: the image size is (4 H, 4 W), cells whose depth
+    before the intrinsics is below 1e-3 get -2."""
+    fr = metas['frustum']
+    B, N, _ = metas['post_trans'].shape
+    BN = B * N
+    view = lambda t, *s: t.reshape(BN, 1, 1, 1, *s)          # noqa: E731
+    pt = view(metas['post_trans'].float(), 3)
+    pr = metas['post_rots'].float().reshape(BN, 3, 3)
+    K = metas['intrins'].float().reshape(BN, 3, 3)
+    S = metas['k2s_sensor'].float().reshape(BN, 4, 4)
+    comb = view(S[:, :3, :3] @ _inv3(K), 3, 3)
+    K, pri = view(K, 3, 3), view(_inv3(pr), 3, 3)
+    t = view(S[:, :3, 3].contiguous(), 3)
+    u, v, d = (fr[..., i].unsqueeze(0) for i in range(3))
+    x, y, z = _mv(pri, u - pt[..., 0], v - pt[..., 1], d - pt[..., 2])
+    x, y, z = _mv(comb, x * z, y * z, z)
+    x, y, z = x + t[..., 0], y + t[..., 1], z + t[..., 2]
+    neg = ~(z >= 1e-3)
+    x, y, z = _mv(K, x, y, z)
+    x, y = x / z, y / z
+    p2 = view(pr[:, :2, :2].contiguous(), 2, 2)
+    sx = p2[..., 0, 0] * x + p2[..., 0, 1] * y + pt[..., 0]
+    sy = p2[..., 1, 0] * x + p2[..., 1, 1] * y + pt[..., 1]
+    m2 = torch.full_like(sx, -2.0)
+    px = torch.where(neg, m2, sx / (4.0 * W - 1.0) * 2.0 - 1.0)
+    py = torch.where(neg, m2, sy / (4.0 * H - 1.0) * 2.0 - 1.0)
+    return torch.stack([px, py], -1)
+
+
+def _split(metas):
+    prev, curr = metas['cv_feat_list']
+    D, H, W, _ = metas['frustum'].shape
+    B, N, _ = metas['post_trans'].shape
+    return prev.reshape(B * N, -1, H, W), curr.reshape(B * N, -1, H, W), D, H, W
+
+
+def stereo_cost_volume_torch(metas, bias, raw=False):
+    """Torch formulation: per group of 4 channels one ``grid_sample`` (align_corners, zeros padding) of ``prev`` and
+    the absolute difference to ``curr`` summed over the group, the group sums added; ``bias`` where the warp of
+    channel 4 (C // 4 - 1) is exactly 0.  Returns softmax_D(raw), or raw = -(cost + bias [warp == 0])."""
+    prev, curr, D, H, W = _split(metas)
+    BN, C = curr.shape[:2]
+    G = C // GROUP
+    if G < 1:
+        raise ValueError(f'the stereo cost volume needs at least {GROUP} channels, got {C}')
+    grid = stereo_grid_torch(metas, H, W).to(curr.dtype).reshape(BN, D * H, W, 2)
+    cost = None
+    for g in range(G):
+        sl = slice(g * GROUP, (g + 1) * GROUP)
+        warp = F.grid_sample(prev[:, sl], grid, mode='bilinear', padding_mode='zeros', align_corners=True)
+        part = (curr[:, sl].unsqueeze(2) - warp.view(BN, GROUP, D, H, W)).abs().sum(1)
+        cost = part if cost is None else cost + part
+    if bias != 0:
+        cost = cost + bias * (warp[:, 0].view(BN, D, H, W) == 0)
+    raw_cost = -cost
+    return raw_cost if raw else raw_cost.softmax(1)
+
+
+def stereo_cost_volume_hip(metas, bias, raw=False):
+    """``stereo_cost_volume_torch`` by ``ocrf_stereo_cost_volume``: one launch, forward only, deterministic.  The
+    frustum axes are passed as strided views of ``metas['frustum']``; the small calibration tensors are moved to the
+    features' device if they are elsewhere."""
+    prev, curr, D, H, W = _split(metas)
+    _lib.require_cuda(prev, curr)
+    BN, C = curr.shape[:2]
+    if C < GROUP or prev.shape[1] != C:
+        raise ValueError(f'stereo features must have the same channel count >= {GROUP}: {prev.shape} vs {curr.shape}')
+    dev = curr.device
+    prev, curr = prev.detach().float().contiguous(), curr.detach().float().contiguous()
+    cal = [metas[k].detach().to(dev, torch.float32).reshape(BN, -1).contiguous()
+           for k in ('k2s_sensor', 'intrins', 'post_rots', 'post_trans')]
+    fr = metas['frustum'].detach().to(dev, torch.float32)
+    u, v, d = fr[0, 0, :, 0], fr[0, :, 0, 1], fr[:, 0, 0, 2]
+    out = torch.empty(BN, D, H, W, device=dev)
+    with _lib.on_device(dev):
+        _lib.check(_lib.lib().ocrf_stereo_cost_volume(
+            BN, C, H, W, D, _lib.ptr(prev), _lib.ptr(curr), _lib.ptr(u), u.stride(0), _lib.ptr(v), v.stride(0),
+            _lib.ptr(d), d.stride(0), *(_lib.ptr(t) for t in cal), float(bias), 1 if raw else 0, _lib.ptr(out),
+            _lib.stream_ptr(dev)), 'ocrf_stereo_cost_volume')
+    return out
+
+
+def stereo_cost_volume(metas, bias, fused=True, raw=False):
+    """The kernel for CUDA float32 features when ``fused``, else the torch formulation (also on the CPU)."""
+    prev, curr = metas['cv_feat_list']
+    if fused and curr.is_cuda and prev.is_cuda and curr.dtype == torch.float32 and prev.dtype == torch.float32:
+        return stereo_cost_volume_hip(metas, bias, raw)
+    return stereo_cost_volume_torch(metas, bias, raw)
+
+
+# --------------------------------------------------------------------------------------------- DepthNet
+def supports(cfg):
+    """Whether ``DepthNet(..., **cfg)`` can be built natively (no deformable convolution)."""
+    return not cfg.get('use_dcn', True)
+
+
+class DepthNet(nn.Module):
+    """view_transformer.py:464-626.  ``forward(x, mlp_input, stereo_metas=None)`` returns cat(depth logits
+    (depth_channels), context (context_channels)) along channels."""
+
+    def __init__(self, in_channels, mid_channels, context_channels, depth_channels, use_dcn=True, use_aspp=True,
+                 with_cp=False, stereo=False, bias=0.0, aspp_mid_channels=-1):
+        super().__init__()
+        if use_dcn:
+            raise NotImplementedError('DepthNet(use_dcn=True) needs mmcv\'s deformable convolution, which has no '
+                                      'native implementation here (INTEGRATION.md 3c)')
+        self.reduce_conv = nn.Sequential(nn.Conv2d(in_channels, mid_channels, 3, stride=1, padding=1),
+                                         nn.BatchNorm2d(mid_channels), nn.ReLU(inplace=True))
+        self.context_conv = nn.Conv2d(mid_channels, context_channels, 1, stride=1, padding=0)
+        self.bn = nn.BatchNorm1d(27)
+        self.depth_mlp = Mlp(27, mid_channels, mid_channels)
+        self.depth_se = SELayer(mid_channels)
+        self.context_mlp = Mlp(27, mid_channels, mid_channels)
+        self.context_se = SELayer(mid_channels)
+        # the stereo branch feeds depth_channels - 2 cost channels (the frustum's D) into the first block
+        first_in, downsample = mid_channels, None
+        if stereo:
+            cv = depth_channels - 2
+            first_in = mid_channels + cv
+            downsample = nn.Conv2d(first_in, mid_channels, 1, 1, 0)
+            self.cost_volumn_net = nn.Sequential(nn.Conv2d(cv, cv, 3, stride=2, padding=1), nn.BatchNorm2d(cv),
+                                                 nn.Conv2d(cv, cv, 3, stride=2, padding=1), nn.BatchNorm2d(cv))
+            self.bias = bias
+        layers = [BasicBlock(first_in, mid_channels, downsample=downsample), BasicBlock(mid_channels, mid_channels),
+                  BasicBlock(mid_channels, mid_channels)]
+        if use_aspp:
+            layers.append(ASPP(mid_channels, mid_channels if aspp_mid_channels < 0 else aspp_mid_channels))
+        layers.append(nn.Conv2d(mid_channels, depth_channels, 1, stride=1, padding=0))
+        self.depth_conv = nn.Sequential(*layers)
+        self.with_cp = with_cp
+        self.depth_channels = depth_channels
+        # the stereo cost volume by ocrf_stereo_cost_volume for CUDA float32 features; False: its torch formulation
+        self.fused_cost_volume = True
+
+    def cost_volume(self, stereo_metas):
+        return stereo_cost_volume(stereo_metas, self.bias, fused=self.fused_cost_volume)
+
+    def forward(self, x, mlp_input, stereo_metas=None):
+        mlp_input = self.bn(mlp_input.reshape(-1, mlp_input.shape[-1]))
+        x = self.reduce_conv(x)
+        context = self.context_conv(self.context_se(x, self.context_mlp(mlp_input)[..., None, None]))
+        depth = self.depth_se(x, self.depth_mlp(mlp_input)[..., None, None])
+        if stereo_metas is not None:
+            if stereo_metas['cv_feat_list'][0] is None:
+                BN, _, H, W = x.shape
+                scale = float(stereo_metas['downsample']) / stereo_metas['cv_downsample']
+                cv = x.new_zeros((BN, self.depth_channels - 2, int(H * scale), int(W * scale)))
+            else:
+                with torch.no_grad():
+                    cv = self.cost_volume(stereo_metas)
+            depth = torch.cat([depth, self.cost_volumn_net(cv)], dim=1)
+        if self.with_cp:
+            depth = checkpoint(self.depth_conv, depth, use_reentrant=False)
+        else:
+            depth = self.depth_conv(depth)
+        return torch.cat([depth, context], dim=1)

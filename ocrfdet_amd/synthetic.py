@@ -126,6 +126,16 @@ def rig(n_cams=6, input_size=(256, 704), batch=1, dtype=np.float32, frame_motion
     return out
 
 
+def stereo_k2s(n_cams=6, batch=1, k=1, dtype=np.float32):
+    """(batch, n_cams, 4, 4) ``k2s_sensor`` of the stereo cost volume: each key-frame camera's sensor frame into the
+    same camera of adjacent frame k, whose ego pose is ``ego_motion(k)`` (bevdet.py:437-455 builds curr2adjsensor the
+    same way: inv(adjacent sensor -> key ego) . key sensor -> key ego)."""
+    r = rig(n_cams, batch=1, dtype=np.float64)
+    T = ego_motion(k)
+    out = [np.linalg.inv(T @ M) @ M for M in r['c2w'][0]]
+    return np.broadcast_to(np.stack(out).astype(dtype), (batch, n_cams, 4, 4)).copy()
+
+
 def rig_tensors(cfg, device='cpu'):
     r = rig(cfg.n_cams, cfg.input_size, cfg.batch)
     return {k: (torch.from_numpy(v).to(device) if isinstance(v, np.ndarray) else v) for k, v in r.items()}

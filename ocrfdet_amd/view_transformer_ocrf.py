@@ -22,9 +22,11 @@ configs/ocrfdet/ocrfdet.py:259-337), assembled MI355X-first:
   training mode: the reference's op sequence as differentiable torch ops around the differentiable
     HIP ops (bev_pool_v2 and the rasteriser have HIP backwards).
 
-``depth_net`` (a CNN outside the path, view_transformer.py:463-630) is injected: pass
-``depth_net=module``; when the reference's mmdet3d is importable its ``DepthNet`` is built from
-``depthnet_cfg`` exactly as the reference does (:588-589).
+``depth_net`` (view_transformer.py:463-630): an explicit ``depth_net=module`` is used as given.  Otherwise a
+``depthnet_cfg`` without deformable convolution (``use_dcn=False``, the reference config's) builds the native
+``depthnet.DepthNet`` (same ``state_dict``; its stereo cost volume is ocrf_stereo_cost_volume); any other cfg builds the
+reference's ``DepthNet`` when its mmdet3d is importable, else none.  ``cv_frustum`` (LSSViewTransformerBEVStereo,
+:783-789) is a non-persistent buffer, so the detector's ``cv_frustum.to(x)`` finds it on the device already.
 """
 import contextlib
 import math
@@ -34,7 +36,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import _lib, bevpool, gaussian_renderer, hoa, index_prep, losses, neck_ops
+from . import _lib, bevpool, depthnet, gaussian_renderer, hoa, index_prep, losses, neck_ops
 from .diff_gaussian_rasterization import pack_cameras, rasterize_packed_autograd, rasterize_sets
 
 __all__ = ['OcRFViewTransformerFull', 'GraphedNeck', 'MS_CAM', 'ChannelAttention', 'SpatialAttention', 'ResCBAMBlock', 'ProbNet',
@@ -473,6 +475,11 @@ class OcRFViewTransformerFull(nn.Module):
         self.grid_lower_bound, self.grid_interval, self.grid_size = index_prep.grid_infos(grid_config)
         self.frustum = index_prep.create_frustum(grid_config['depth'], input_size, downsample)
         self.D = self.frustum.shape[0]
+        # LSSViewTransformerBEVStereo (:783-789): the stereo frustum at downsample 4, read by OcRFDet4D.prepare_bev_feat.
+        # A buffer follows .to(device) (the reference keeps it on the host: a 16 MB copy per forward); not persistent, so
+        # the state_dict keys do not change
+        self.register_buffer('cv_frustum', index_prep.create_frustum(grid_config['depth'], input_size, 4),
+                             persistent=False)
         self.in_channels, self.out_channels = in_channels, out_channels
         self.accelerate, self.initial_flag = accelerate, True
         self.loss_depth_weight = loss_depth_weight
@@ -549,6 +556,8 @@ class OcRFViewTransformerFull(nn.Module):
                 or any(p.requires_grad for p in _tensors_of(self, 'all', (self,), buffers=False)))
 
     def _reference_depth_net(self, cfg):
+        if depthnet.supports(cfg):
+            return depthnet.DepthNet(self.in_channels, self.in_channels, self.out_channels, self.D + 2, **cfg)
         try:
             from mmdet3d.models.necks.view_transformer import DepthNet
         except Exception:
