@@ -507,6 +507,60 @@ int ocrf_stereo_cost_volume(int BN, int C, int H, int W, int D, const float *pre
                             ocrf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Training targets and losses of the detection head (csrc/center_head.hip): centerpoint_head.py CenterHead
+ * get_targets_single (:437-585) and loss (:587-668) for every sample and task in one call each.  Deterministic, no host
+ * reads, no entry writes its inputs.  T <= OCRF_CH_MAX_TASKS tasks of ncls[t] classes, at most OCRF_CH_MAX_PLANES
+ * classes in all; HW = H * W of the feature map.
+ *
+ * ocrf_center_head_targets: boxes (n_boxes, box_dim) f32 as LiDARInstance3DBoxes.tensor (bottom-centre z; box_dim >= 9
+ *   with velocity, else >= 7), labels (n_boxes) int64, offsets (B + 1) int64 (sample b owns rows [offsets[b],
+ *   offsets[b+1])), class_table (n_labels, 2) int32 = (task, class in task), task -1 for a label in no task.  The
+ *   train_cfg scalars: voxel_size[2], pc_range[2] (host), out_size_factor, gaussian_overlap, min_radius.  Outputs
+ *   (device): heatmap = the tasks' (B, ncls[t], H, W) blocks back to back, anno_box (T, B, max_objs, 10 | 8), ind
+ *   (T, B, max_objs) int64, mask (T, B, max_objs) uint8, counts[2T] f32 = per task the heatmap pixels equal to 1 and
+ *   the mask sum.  A memset of counts and two launches; workspace from ocrf_center_head_targets_workspace_bytes.
+ * ocrf_center_head_heatmap_loss: logits[T] (host table of device (B, ncls[t], HW) f32) against the targets' heatmap ->
+ *   clipped[T] (clip_sigmoid, same shapes), out[T] = loss_weight * gaussian focal sum / (float)(max(counts[t], 1) +
+ *   FLT_EPSILON) and dens[T] for the backward.  Two launches; workspace from ..._heatmap_loss_workspace_bytes.
+ * ocrf_center_head_heatmap_loss_backward: grad_out[T] (device) -> grad_logits[T] (host table), every element written.
+ *   One launch.
+ * ocrf_center_head_reg_loss: heads[5T] (host table: per task reg (B,2,HW), height (B,1,HW), dim (B,3,HW), rot (B,2,HW),
+ *   vel (B,2,HW); vel unused without velocity), the targets' anno_box / ind / mask, code_weights[10 | 8] (host) ->
+ *   out (T, 6) f32: loss_weight * the L1 sums of code groups [0,2,3,6,8,10) over (num + 1e-4) + FLT_EPSILON, and in
+ *   column 5 of all codes over num + FLT_EPSILON, num = max(counts[T + t], 1e-4); dens (T, 2) for the backward.  Two
+ *   launches; workspace from ocrf_center_head_reg_loss_workspace_bytes.
+ * ocrf_center_head_reg_loss_backward: grad_out (T, 6) (device) -> grad_heads[5T] (host table, zero-filled by the
+ *   caller): only the pixels at ind are written, duplicate indices summed in slot order.  One launch, max_objs <= 16384.
+ */
+#define OCRF_CH_MAX_TASKS 8
+#define OCRF_CH_MAX_PLANES 64
+size_t ocrf_center_head_targets_workspace_bytes(int n_boxes);
+int ocrf_center_head_targets(int B, int T, const int *ncls, int n_labels, const int *class_table, int n_boxes,
+                             int box_dim, const float *boxes, const long long *labels, const long long *offsets, int H,
+                             int W, int max_objs, int with_velocity, int norm_bbox, const float *voxel_size,
+                             const float *pc_range, int out_size_factor, double gaussian_overlap, int min_radius,
+                             float *heatmap, float *anno_box, long long *ind, unsigned char *mask, float *counts,
+                             void *workspace, size_t workspace_bytes, ocrf_stream_t stream);
+size_t ocrf_center_head_heatmap_loss_workspace_bytes(int B, int T, const int *ncls, int HW);
+int ocrf_center_head_heatmap_loss(int B, int T, const int *ncls, int HW, const float *const *logits,
+                                  const float *heatmap, const float *counts, float loss_weight, float *const *clipped,
+                                  float *out, float *dens, void *workspace, size_t workspace_bytes,
+                                  ocrf_stream_t stream);
+int ocrf_center_head_heatmap_loss_backward(int B, int T, const int *ncls, int HW, const float *const *logits,
+                                           const float *heatmap, const float *dens, const float *grad_out,
+                                           float loss_weight, float *const *grad_logits, ocrf_stream_t stream);
+size_t ocrf_center_head_reg_loss_workspace_bytes(int B, int T);
+int ocrf_center_head_reg_loss(int B, int T, int HW, int max_objs, int with_velocity, const float *const *heads,
+                              const float *anno_box, const long long *ind, const unsigned char *mask,
+                              const float *code_weights, const float *counts, float loss_weight, float *out,
+                              float *dens, void *workspace, size_t workspace_bytes, ocrf_stream_t stream);
+int ocrf_center_head_reg_loss_backward(int B, int T, int HW, int max_objs, int with_velocity,
+                                       const float *const *heads, const float *anno_box, const long long *ind,
+                                       const unsigned char *mask, const float *code_weights, const float *dens,
+                                       const float *grad_out, float loss_weight, float *const *grad_heads,
+                                       ocrf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Index preparation of the two poolings on the device (csrc/index_prep.hip).
  *
  * ocrf_lss_prepare replaces get_lidar_coor + voxel_pooling_prepare_v2
@@ -891,7 +945,14 @@ enum {
   OCRF_K_LOSS_RENDER = 84,       /* render_tile_kernel */
   OCRF_K_LOSS_RENDER_DEPTH = 85, /* render_depth_kernel */
   OCRF_K_LOSS_RENDER_BWD = 86,  /* render_backward_kernel */
-  OCRF_K_STEREO_COST_VOLUME = 90 /* stereo_cost_volume_kernel */
+  OCRF_K_STEREO_COST_VOLUME = 90, /* stereo_cost_volume_kernel */
+  OCRF_K_CH_ASSIGN = 91,         /* ch_assign_kernel */
+  OCRF_K_CH_HEATMAP = 92,        /* ch_heatmap_kernel */
+  OCRF_K_CH_HM_LOSS = 93,        /* ch_hm_loss_partial_kernel */
+  OCRF_K_CH_FINAL = 94,          /* ch_hm_loss_final_kernel, ch_reg_loss_final_kernel */
+  OCRF_K_CH_HM_LOSS_BWD = 95,    /* ch_hm_loss_backward_kernel */
+  OCRF_K_CH_REG_LOSS = 96,       /* ch_reg_loss_partial_kernel */
+  OCRF_K_CH_REG_LOSS_BWD = 97    /* ch_reg_loss_backward_kernel */
 };
 const char *ocrf_kernel_name(int kernel_id);           /* symbol as rocprofv3 prints it */
 /* Diagnostic: a one-thread kernel that stores the device's constant-rate clock (wall_clock64, 100 MHz)

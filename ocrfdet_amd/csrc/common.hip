@@ -139,6 +139,13 @@ const char* ocrf_kernel_name(int kernel_id) {
     case OCRF_K_LOSS_RENDER_DEPTH: return "render_depth_kernel";
     case OCRF_K_LOSS_RENDER_BWD: return "render_backward_kernel";
     case OCRF_K_STEREO_COST_VOLUME: return "stereo_cost_volume_kernel";
+    case OCRF_K_CH_ASSIGN: return "ch_assign_kernel";
+    case OCRF_K_CH_HEATMAP: return "ch_heatmap_kernel";
+    case OCRF_K_CH_HM_LOSS: return "ch_hm_loss_partial_kernel";
+    case OCRF_K_CH_FINAL: return "ch_hm_loss_final_kernel / ch_reg_loss_final_kernel";
+    case OCRF_K_CH_HM_LOSS_BWD: return "ch_hm_loss_backward_kernel";
+    case OCRF_K_CH_REG_LOSS: return "ch_reg_loss_partial_kernel";
+    case OCRF_K_CH_REG_LOSS_BWD: return "ch_reg_loss_backward_kernel";
     default: return "";
   }
 }

@@ -219,3 +219,29 @@ def stress_gaussians(n, seed=0, extent=40.0, device='cpu'):
     rgb = rng.uniform(0.0, 1.0, (n, 3)).astype(np.float32)
     t = lambda a: torch.from_numpy(a).to(device)  # noqa: E731
     return dict(xyz=t(xyz), scales=t(scales), rotations=t(q), opacity=t(opacity), rgb=t(rgb))
+
+
+def nuscenes_boxes(batch=8, seed=0, n_range=(30, 40), n_out=4, pc_range=(-51.2, -51.2, -5.0, 51.2, 51.2, 3.0),
+                   device='cpu'):
+    """nuScenes-like gt for the detection head: per sample (boxes (n, 9) float32 as LiDARInstance3DBoxes.tensor --
+    x, y, bottom z, dx, dy, dz, yaw, vx, vy -- and labels (n,) int64 over the ten classes), 30-40 boxes inside the
+    range and ``n_out`` outside it.  Sizes follow the classes' typical dimensions."""
+    # car, truck, construction_vehicle, bus, trailer, barrier, motorcycle, bicycle, pedestrian, traffic_cone
+    dims = np.array([[1.9, 4.6, 1.7], [2.5, 6.9, 2.8], [2.8, 6.4, 3.2], [2.9, 11.0, 3.5], [2.9, 12.3, 3.9],
+                     [2.5, 0.5, 1.0], [0.8, 2.1, 1.5], [0.6, 1.7, 1.3], [0.7, 0.7, 1.8], [0.4, 0.4, 1.1]], np.float32)
+    freq = np.array([0.40, 0.07, 0.02, 0.02, 0.03, 0.13, 0.02, 0.02, 0.19, 0.10])
+    rng = np.random.default_rng(seed)
+    boxes, labels = [], []
+    for _ in range(batch):
+        n = int(rng.integers(n_range[0], n_range[1] + 1))
+        lab = rng.choice(10, size=n + n_out, p=freq / freq.sum())
+        xy = rng.uniform(pc_range[0] + 1, pc_range[3] - 1, (n + n_out, 2))
+        xy[n:] = np.sign(rng.uniform(-1, 1, (n_out, 2))) * rng.uniform(pc_range[3] + 1, pc_range[3] + 10, (n_out, 2))
+        d = dims[lab] * rng.uniform(0.85, 1.15, (n + n_out, 3))
+        z = rng.uniform(-2.5, 0.5, (n + n_out, 1))
+        yaw = rng.uniform(-np.pi, np.pi, (n + n_out, 1))
+        vel = rng.normal(0, 2, (n + n_out, 2)) * (lab[:, None] < 8)
+        b = np.concatenate([xy, z, d, yaw, vel], 1).astype(np.float32)
+        boxes.append(torch.from_numpy(b).to(device))
+        labels.append(torch.from_numpy(lab.astype(np.int64)).to(device))
+    return boxes, labels
