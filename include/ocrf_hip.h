@@ -561,6 +561,33 @@ int ocrf_center_head_reg_loss_backward(int B, int T, int HW, int max_objs, int w
                                        ocrf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Test-time decode and NMS of the detection head (csrc/center_decode.hip): centerpoint_head.py CenterHead.get_bboxes
+ * (:670-763), get_task_detections (:765-898), CenterPointBBoxCoder.decode, circle_nms and nms_bev (mmcv nms_rotated)
+ * for every sample and task in one call.  Deterministic, no atomics on results, no host reads.
+ *
+ * ocrf_center_decode: heads[6T] (host table of device f32 pointers, per task heatmap logits (B, ncls[t], H, W), reg
+ *   (B, 2, H, W), height (B, 1, H, W), dim (B, 3, H, W), rot (B, 2, H, W) and vel (B, 2, H, W), vel NULL without
+ *   velocity).  Host scalars: max_num = K (<= 1024, <= H * W), pre_max_size, post_max_size (> 0), out_size_factor,
+ *   voxel_size[2], pc_range[2], the coder's score threshold (applied when has_coder_score_threshold) and
+ *   post_center_range[6] (NULL = none), the test cfg's score threshold (>=, when has_score_threshold) and
+ *   post_center_limit_range[6] (NULL = none), per task nms_circle[T] (1 = circle NMS), nms_threshold[T] (the IoU
+ *   threshold, or min_radius for circle tasks) and rescale_factor[T * OCRF_CD_MAX_CLASSES] (per class in task).
+ *   Outputs (device), M = T * post_max_size: boxes (B, M, 9 | 7) with bottom-centre z, scores (B, M), labels (B, M)
+ *   int32 (with the task's class offset), counts (B) int32; rows past counts[b] are zero.  Four launches, no memset;
+ *   workspace from ocrf_center_decode_workspace_bytes.
+ */
+#define OCRF_CD_MAX_TASKS 8
+#define OCRF_CD_MAX_CLASSES 8
+size_t ocrf_center_decode_workspace_bytes(int B, int T, int max_num, int post_max_size);
+int ocrf_center_decode(int B, int T, const int *ncls, int H, int W, const float *const *heads, int with_velocity,
+                       int norm_bbox, int max_num, int pre_max_size, int post_max_size, float out_size_factor,
+                       const float *voxel_size, const float *pc_range, int has_coder_score_threshold,
+                       float coder_score_threshold, const float *post_center_range, int has_score_threshold,
+                       float score_threshold, const float *post_center_limit_range, const int *nms_circle,
+                       const double *nms_threshold, const float *rescale_factor, float *boxes, float *scores,
+                       int *labels, int *counts, void *workspace, size_t workspace_bytes, ocrf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Index preparation of the two poolings on the device (csrc/index_prep.hip).
  *
  * ocrf_lss_prepare replaces get_lidar_coor + voxel_pooling_prepare_v2
@@ -952,7 +979,11 @@ enum {
   OCRF_K_CH_FINAL = 94,          /* ch_hm_loss_final_kernel, ch_reg_loss_final_kernel */
   OCRF_K_CH_HM_LOSS_BWD = 95,    /* ch_hm_loss_backward_kernel */
   OCRF_K_CH_REG_LOSS = 96,       /* ch_reg_loss_partial_kernel */
-  OCRF_K_CH_REG_LOSS_BWD = 97    /* ch_reg_loss_backward_kernel */
+  OCRF_K_CH_REG_LOSS_BWD = 97,   /* ch_reg_loss_backward_kernel */
+  OCRF_K_CD_SELECT = 98,         /* cd_select_kernel */
+  OCRF_K_CD_MASK = 99,           /* cd_mask_kernel */
+  OCRF_K_CD_SCAN = 100,          /* cd_scan_kernel */
+  OCRF_K_CD_WRITE = 101          /* cd_write_kernel */
 };
 const char *ocrf_kernel_name(int kernel_id);           /* symbol as rocprofv3 prints it */
 /* Diagnostic: a one-thread kernel that stores the device's constant-rate clock (wall_clock64, 100 MHz)

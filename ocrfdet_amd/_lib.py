@@ -246,6 +246,12 @@ def _declare(L):
     L.ocrf_center_head_reg_loss.argtypes = [c_int] * 5 + [c_void_p] * 6 + [c_float] + [c_void_p] * 3 + [c_size_t, c_void_p]
     L.ocrf_center_head_reg_loss_backward.restype = c_int
     L.ocrf_center_head_reg_loss_backward.argtypes = [c_int] * 5 + [c_void_p] * 7 + [c_float] + [c_void_p] * 2
+    L.ocrf_center_decode_workspace_bytes.restype = c_size_t
+    L.ocrf_center_decode_workspace_bytes.argtypes = [c_int] * 4
+    L.ocrf_center_decode.restype = c_int
+    L.ocrf_center_decode.argtypes = ([c_int, c_int, c_void_p, c_int, c_int, c_void_p] + [c_int] * 5 + [c_float] +
+                                     [c_void_p] * 2 + [c_int, c_float, c_void_p, c_int, c_float] + [c_void_p] * 8 +
+                                     [c_void_p, c_size_t, c_void_p])
     L.ocrf_sh_to_rgb.restype = c_int
     L.ocrf_sh_to_rgb.argtypes = [c_int] * 3 + [c_void_p] * 6
     L.ocrf_sh_to_rgb_backward.restype = c_int

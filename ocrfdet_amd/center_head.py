@@ -15,8 +15,11 @@ The training path (``get_targets`` + ``loss``) has two formulations of the same 
 Both keep the reference's integer outcomes (slot, radius, centre cell) and heatmap values bit for bit: the radius in
 float32 in the reference's operation order, the Gaussian in float64 as numpy computes it.
 
-Out of scope here: ``get_bboxes`` (decode, circle and rotated BEV NMS) belongs to the follow-up "native CenterHead
-decode and NMS" and raises ``NotImplementedError``; so does ``DCNSeparateHead``.
+``get_bboxes`` (top-K decode, circle and rotated BEV NMS, merge) is in ``center_decode.py``: fused by
+``csrc/center_decode.hip`` in four launches with no host synchronisation (``get_bboxes_padded``), or by its torch
+formulation on the CPU, for inputs that are not float32 CUDA tensors and with ``fused_decode = False``.  A head built
+without ``bbox_coder`` or ``test_cfg`` (training only) cannot decode and raises ``NotImplementedError``; so does
+``DCNSeparateHead``.
 """
 import copy
 import ctypes
@@ -25,6 +28,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from . import center_decode as cd
 
 __all__ = ['ConvBNReLU', 'SeparateHead', 'DCNSeparateHead', 'CenterHead', 'HeatmapLoss', 'RegLoss', 'clip_sigmoid',
            'gaussian_focal_loss', 'targets_torch', 'heatmap_loss_torch', 'reg_loss_torch', 'pack_boxes', 'reduce_counts']
@@ -463,7 +467,14 @@ class CenterHead(nn.Module):
         if loss_bbox.get('type') != 'L1Loss' or loss_bbox.get('reduction', 'mean') not in ('mean', 'none'):
             raise NotImplementedError(f'loss_bbox {loss_bbox}: only L1Loss with reduction mean or none')
         self.loss_cls_cfg, self.loss_bbox_cfg = dict(loss_cls), dict(loss_bbox)
+        if isinstance(bbox_coder, dict):
+            coder = dict(bbox_coder)
+            kind = coder.pop('type', 'CenterPointBBoxCoder')
+            if kind != 'CenterPointBBoxCoder':
+                raise NotImplementedError(f'bbox_coder type {kind}: only CenterPointBBoxCoder')
+            bbox_coder = cd.CenterPointBBoxCoder(**coder)
         self.bbox_coder = bbox_coder
+        self.fused_decode = True
         self.num_anchor_per_locs = [n for n in num_classes]
         self.fp16_enabled = False
         self.fused_loss = True
@@ -578,6 +589,32 @@ class CenterHead(nn.Module):
                 loss_dict['loss'] += hm[task_id]
         return loss_dict
 
+    # ----------------------------------------------------------------------------------------- decode
+    def _decode_cfg(self):
+        if self.bbox_coder is None or self.test_cfg is None:
+            raise NotImplementedError('CenterHead decoding needs both bbox_coder and test_cfg; this head was built '
+                                      'for training only')
+        return cd.DecodeConfig(self.bbox_coder, self.test_cfg, self.num_classes)
+
+    def get_bboxes_padded(self, preds_dicts):
+        """Every sample's detections, padded and without a host synchronisation: boxes (B, M, 9 | 7) f32 with
+        bottom-centre z, scores (B, M) f32, labels (B, M) int32 and counts (B,) int32, M = T * post_max_size; rows past
+        a sample's count are zero."""
+        cfg = self._decode_cfg()
+        if self.fused_decode and cd.fused_ok(preds_dicts):
+            return cd.decode_fused(preds_dicts, cfg, self.norm_bbox)
+        return cd.decode_torch(preds_dicts, cfg, self.norm_bbox)
+
     def get_bboxes(self, preds_dicts, img_metas, img=None, rescale=False):
-        raise NotImplementedError('CenterHead.get_bboxes (decode, circle and rotated BEV NMS) is the follow-up '
-                                  '"native CenterHead decode and NMS"; this module covers the training path')
+        """The reference's list over samples of [bboxes, scores, labels]: bboxes through ``img_metas[i]['box_type_3d']``
+        (box_dim 9, or 7 without velocity) when the metas provide it, else a plain (n, 9 | 7) float32 tensor; labels
+        int32.  Reads the B counts back once."""
+        boxes, scores, labels, counts = self.get_bboxes_padded(preds_dicts)
+        ret = []
+        for i, n in enumerate(cd.read_counts(counts)):
+            b = boxes[i, :n]
+            meta = img_metas[i] if img_metas is not None and i < len(img_metas) else None
+            if isinstance(meta, dict) and 'box_type_3d' in meta:
+                b = meta['box_type_3d'](b, b.shape[1])
+            ret.append([b, scores[i, :n], labels[i, :n]])
+        return ret

@@ -146,6 +146,10 @@ const char* ocrf_kernel_name(int kernel_id) {
     case OCRF_K_CH_HM_LOSS_BWD: return "ch_hm_loss_backward_kernel";
     case OCRF_K_CH_REG_LOSS: return "ch_reg_loss_partial_kernel";
     case OCRF_K_CH_REG_LOSS_BWD: return "ch_reg_loss_backward_kernel";
+    case OCRF_K_CD_SELECT: return "cd_select_kernel";
+    case OCRF_K_CD_MASK: return "cd_mask_kernel";
+    case OCRF_K_CD_SCAN: return "cd_scan_kernel";
+    case OCRF_K_CD_WRITE: return "cd_write_kernel";
     default: return "";
   }
 }
