@@ -1,12 +1,14 @@
 """Loader for ``libocrf_hip.so`` — the C-ABI HIP library behind every op in this package.
 
-There is no CPU or PyTorch fallback anywhere in ``ocrfdet_amd``: if the library cannot be loaded
-the ops raise.  ``build()`` compiles it in-tree with hipcc for gfx950 (cross-compiles without a
-GPU); the built ``.so`` is git-ignored but travels with the source tree.
+``lib()`` never falls back: if the library cannot be loaded it raises, and so does every op that
+launches through it.  Its entry points are declared from ``include/ocrf_hip.h`` itself, and ``launch()``
+is how the ops call them.  ``build()`` compiles it in-tree with hipcc for gfx950 (cross-compiles
+without a GPU); the built ``.so`` is git-ignored but travels with the source tree.
 """
 import contextlib
 import ctypes
 import os
+import re
 import subprocess
 
 import torch
@@ -32,308 +34,108 @@ def build(force=False, verbose=False):
 
 
 def lib():
-    """The loaded library.  Raises ``OcrfHipError`` if it is missing — never falls back."""
+    """The loaded library, its entry points declared from ``include/ocrf_hip.h``.  Raises ``OcrfHipError`` if it is
+    missing — never falls back."""
     global _LIB
     if _LIB is None:
         if not os.path.exists(_SO):
             raise OcrfHipError(
                 f"{_SO} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `make -C ocrfdet_amd/csrc` (hipcc, gfx950). ocrfdet_amd has no fallback path.")
+        protos = prototypes()
         try:
-            _LIB = ctypes.CDLL(_SO)
+            L = ctypes.CDLL(_SO)
         except OSError as e:  # pragma: no cover
             raise OcrfHipError(f"cannot load {_SO}: {e}") from e
-        _declare(_LIB)
-        _declare_step(_LIB)
+        for name, (restype, argtypes) in protos.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _LIB = L
     rec = getattr(_RECORDER, 'rec', None)
     if rec is not None:
         return _RecordingLib(_LIB, rec)
     return _LIB
 
 
-def _declare(L):
-    c_int, c_size_t, c_void_p, c_float = ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_float
-    L.ocrf_version.restype = ctypes.c_char_p
-    L.ocrf_version.argtypes = []
-    L.bev_pool_v2.restype = None
-    L.bev_pool_v2.argtypes = [c_int, c_int] + [c_void_p] * 8
-    L.bev_pool_v2_grad.restype = None
-    L.bev_pool_v2_grad.argtypes = [c_int, c_int] + [c_void_p] * 10
-    c_long = ctypes.c_long
-    L.ocrf_bev_pool_v2.restype = c_int
-    L.ocrf_bev_pool_v2.argtypes = [c_int, c_int, c_int, c_long] + [c_void_p] * 8 + [c_void_p, c_size_t, c_void_p]
-    L.ocrf_bev_pool_v2_workspace_bytes.restype = c_size_t
-    L.ocrf_bev_pool_v2_workspace_bytes.argtypes = [c_int, c_int, c_long]
-    L.ocrf_bev_pool_v2_nchw.restype = c_int
-    L.ocrf_bev_pool_v2_nchw.argtypes = ([c_int, c_int, c_int] + [c_void_p] * 8 + [c_int] * 5 +
-                                        [c_void_p, c_size_t, c_void_p])
-    L.ocrf_bev_pool_v2_nchw_dyn.restype = c_int
-    L.ocrf_bev_pool_v2_nchw_dyn.argtypes = ([c_int, c_int, c_int] + [c_void_p] * 9 + [c_int] * 5 +
-                                            [c_void_p, c_size_t, c_void_p])
-    L.ocrf_bev_pool_v2_nchw_workspace_bytes.restype = c_size_t
-    L.ocrf_bev_pool_v2_nchw_workspace_bytes.argtypes = [c_int] * 7
-    L.ocrf_bev_pool_plan_bytes.restype = c_size_t
-    L.ocrf_bev_pool_plan_bytes.argtypes = [c_int] * 6
-    L.ocrf_bev_pool_plan_build.restype = c_int
-    L.ocrf_bev_pool_plan_build.argtypes = [c_int] * 3 + [c_void_p] * 3 + [c_int] * 4 + [c_void_p, c_size_t, c_void_p]
-    L.ocrf_bev_pool_planned_workspace_bytes.restype = c_size_t
-    L.ocrf_bev_pool_planned_workspace_bytes.argtypes = [c_int, c_int]
-    L.ocrf_bev_pool_v2_nchw_planned.restype = c_int
-    L.ocrf_bev_pool_v2_nchw_planned.argtypes = ([c_int] * 2 + [c_void_p] * 6 + [c_int] * 5 +
-                                                [c_void_p, c_size_t, c_size_t, c_size_t, c_void_p])
-    L.ocrf_bev_pool_mfma_panel_rows.restype = c_int
-    L.ocrf_bev_pool_mfma_panel_rows.argtypes = []
-    L.ocrf_diag_pool_mfma_stamps.restype = c_int
-    L.ocrf_diag_pool_mfma_stamps.argtypes = [c_void_p]
-    L.ocrf_bev_pool_mfma_tile_side.restype = c_int
-    L.ocrf_bev_pool_mfma_tile_side.argtypes = []
-    L.ocrf_bev_pool_mfma_slab_bytes.restype = c_size_t
-    L.ocrf_bev_pool_mfma_slab_bytes.argtypes = [c_int, c_int]
-    L.ocrf_bev_pool_v2_nchw_mfma.restype = c_int
-    L.ocrf_bev_pool_mfma_max_unit_panels.restype = c_int
-    L.ocrf_diag_pool_panel_stamps.restype = c_int
-    L.ocrf_diag_pool_panel_stamps.argtypes = [c_void_p]
-    L.ocrf_bev_pool_cell_weights.restype = c_int
-    L.ocrf_bev_pool_cell_weights.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.ocrf_bev_pool_v2_nchw_panel.restype = c_int
-    L.ocrf_bev_pool_v2_nchw_panel.argtypes = [c_int, c_int] + [c_void_p] * 10 + [c_int] * 5 + [c_void_p] * 2 + [c_size_t, c_void_p]
-    L.ocrf_bev_pool_mfma_max_unit_panels.argtypes = []
-    L.ocrf_bev_pool_v2_nchw_mfma.argtypes = [c_int, c_int] + [c_void_p] * 10 + [c_int] * 5 + [c_void_p] * 3
-    L.ocrf_tune_set.restype = c_int
-    L.ocrf_tune_set.argtypes = [c_int, c_int]
-    L.ocrf_bev_pool_max_units.restype = c_int
-    L.ocrf_bev_pool_max_units.argtypes = [c_int] * 6
-    L.ocrf_diag_bev_pool_stamps.restype = c_int
-    L.ocrf_diag_bev_pool_stamps.argtypes = [c_int] * 2 + [c_void_p] * 6 + [c_int] * 5 + [c_void_p] * 3
-    L.ocrf_bev_pool_v2_check_intervals.restype = c_int
-    L.ocrf_bev_pool_v2_check_intervals.argtypes = [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.ocrf_bev_pool_v2_grad.restype = c_int
-    L.ocrf_bev_pool_v2_grad.argtypes = [c_int, c_int] + [c_void_p] * 10 + [c_void_p]
-    L.ocrf_rasterize_forward.restype = c_int
-    L.ocrf_rasterize_forward.argtypes = ([c_int] * 4 + [c_void_p] * 4 + [c_float] + [c_void_p] * 4 +
-                                         [c_int] + [c_void_p] * 7 + [c_void_p, c_size_t, c_void_p])
-    L.ocrf_rasterize_forward_sets.restype = c_int
-    L.ocrf_rasterize_forward_sets.argtypes = ([c_int] * 5 + [c_void_p] * 4 + [c_float] + [c_void_p] * 4 +
-                                              [c_int] + [c_void_p] * 7 + [c_void_p, c_size_t, c_void_p])
-    L.ocrf_raster_plan_count_workspace_bytes.restype = c_size_t
-    L.ocrf_raster_plan_count_workspace_bytes.argtypes = [c_int]
-    L.ocrf_raster_plan_count.restype = c_int
-    L.ocrf_raster_plan_count.argtypes = [c_int] * 4 + [c_void_p] * 2 + [c_float] + [c_void_p] * 3 + [c_size_t, c_void_p]
-    L.ocrf_raster_plan_build_workspace_bytes.restype = c_size_t
-    L.ocrf_raster_plan_build_workspace_bytes.argtypes = [c_int, c_int, c_long]
-    L.ocrf_raster_plan_bytes.restype = c_size_t
-    L.ocrf_raster_plan_bytes.argtypes = [c_int, c_int, c_long]
-    L.ocrf_raster_plan_build.restype = c_int
-    L.ocrf_raster_plan_build.argtypes = ([c_int] * 4 + [c_void_p] * 2 + [c_float, c_long] +
-                                         [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p])
-    L.ocrf_rasterize_planned_workspace_bytes.restype = c_size_t
-    L.ocrf_rasterize_planned_workspace_bytes.argtypes = [c_long, c_int]
-    L.ocrf_rasterize_planned.restype = c_int
-    L.ocrf_rasterize_planned.argtypes = ([c_void_p, c_size_t, c_int, c_int, c_long] + [c_int] * 4 + [c_void_p] * 4 +
-                                         [c_float] + [c_void_p] * 2 + [c_int] + [c_void_p] * 6 + [c_size_t, c_int] +
-                                         [c_void_p] * 2 + [c_size_t, c_int, c_void_p, c_int, c_void_p, c_int] +
-                                         [c_void_p, c_size_t, c_int, c_int, c_long, c_void_p, c_void_p])
-    L.ocrf_rasterize_planned_bins_workspace_bytes.restype = c_size_t
-    L.ocrf_rasterize_planned_bins_workspace_bytes.argtypes = [c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_long]
-    L.ocrf_raster_plan_bins_bytes.restype = c_size_t
-    L.ocrf_raster_plan_bins_bytes.argtypes = [c_int] * 5 + [c_long]
-    L.ocrf_raster_plan_bins_workspace_bytes.restype = c_size_t
-    L.ocrf_raster_plan_bins_workspace_bytes.argtypes = [c_int] * 6 + [c_long]
-    L.ocrf_raster_plan_bins_build.restype = c_int
-    L.ocrf_raster_plan_bins_build.argtypes = ([c_void_p, c_size_t, c_int, c_int, c_long, c_int, c_int, c_float, c_int, c_int,
-                                               c_long, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p])
-    L.ocrf_stream_write_value32.restype = c_int
-    L.ocrf_stream_write_value32.argtypes = [c_void_p, c_int, c_void_p]
-    L.ocrf_lss_prepare.restype = c_int
-    L.ocrf_lss_prepare.argtypes = ([c_int] * 5 + [c_void_p] * 4 + [c_int] * 3 + [c_void_p] * 6 +
-                                   [c_void_p, c_size_t, c_void_p])
-    L.ocrf_lss_prepare_workspace_bytes.restype = c_size_t
-    L.ocrf_lss_prepare_workspace_bytes.argtypes = [c_int] * 8
-    L.ocrf_ht_prepare.restype = c_int
-    L.ocrf_ht_prepare.argtypes = ([c_int] * 7 + [c_void_p] * 3 + [c_float] * 4 + [c_void_p] * 6 +
-                                  [c_void_p, c_size_t, c_void_p])
-    L.ocrf_geometry_blocks.restype = c_int
-    L.ocrf_geometry_blocks.argtypes = [c_int, c_int] + [c_void_p] * 7 + [c_int, c_int, c_float, c_float] + [c_void_p] * 4
-    L.ocrf_ht_prepare_workspace_bytes.restype = c_size_t
-    L.ocrf_ht_prepare_workspace_bytes.argtypes = [c_int, c_int]
-    L.ocrf_rasterize_backward.restype = c_int
-    L.ocrf_rasterize_backward.argtypes = ([c_int] * 4 + [c_void_p] * 4 + [c_float] + [c_void_p] * 13 +
-                                          [c_void_p, c_size_t, c_void_p])
-    L.ocrf_rasterize_backward_cov3d.restype = c_int
-    L.ocrf_rasterize_backward_cov3d.argtypes = [c_int] * 4 + [c_void_p] * 16 + [c_size_t, c_void_p]
-    L.ocrf_rasterize_backward_workspace_bytes.restype = c_size_t
-    L.ocrf_rasterize_backward_workspace_bytes.argtypes = [c_int, c_int]
-    L.ocrf_rasterize_workspace_bytes.restype = c_size_t
-    L.ocrf_rasterize_workspace_bytes.argtypes = [c_int, c_int]
-    L.ocrf_hoa_channel_stats.restype = c_int
-    L.ocrf_hoa_channel_stats.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
-    L.ocrf_hoa_opacity_mask_gate.restype = c_int
-    L.ocrf_hoa_opacity_mask_gate.argtypes = [c_void_p] * 4 + [c_int] * 5 + [c_void_p] * 3
-    L.ocrf_hoa_height_attention.restype = c_int
-    L.ocrf_hoa_height_attention.argtypes = ([c_void_p] + [c_int] * 5 + [c_void_p] * 4 +
-                                            [c_void_p, c_size_t, c_void_p])
-    L.ocrf_hoa_height_attention_workspace_bytes.restype = c_size_t
-    L.ocrf_hoa_height_attention_workspace_bytes.argtypes = [c_int, c_int]
-    L.ocrf_hoa_unet_block.restype = c_int
-    L.ocrf_hoa_unet_block.argtypes = ([c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
-                                       c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                       c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p])
-    L.ocrf_hoa_v2b_weights_len.restype = c_int
-    L.ocrf_hoa_v2b_weights_len.argtypes = []
-    L.ocrf_hoa_v2b_workspace_bytes.restype = c_size_t
-    L.ocrf_hoa_v2b_workspace_bytes.argtypes = [c_int] * 3
-    L.ocrf_hoa_v2b_forward.restype = c_int
-    L.ocrf_hoa_v2b_forward.argtypes = [c_void_p] * 3 + [c_int] * 3 + [c_void_p, c_size_t, c_void_p, c_void_p]
-    L.ocrf_hoa_unet_tiles.restype = c_int
-    L.ocrf_hoa_unet_tiles.argtypes = [c_int, c_int]
-    L.ocrf_hoa_height_gate_from_tiles.restype = c_int
-    L.ocrf_hoa_height_gate_from_tiles.argtypes = [c_int] * 4 + [c_void_p] * 5
-    L.ocrf_hoa_gated_conv1x1.restype = c_int
-    L.ocrf_hoa_gated_conv1x1.argtypes = [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 4
-    L.ocrf_hoa1_forward.restype = c_int
-    L.ocrf_hoa1_forward.argtypes = [c_void_p] * 3 + [c_int] * 3 + [c_float] + [c_void_p] * 3
-    L.ocrf_hoa1_weights_len.restype = c_int
-    L.ocrf_hoa1_weights_len.argtypes = []
-    L.ocrf_ht_project.restype = c_int
-    L.ocrf_ht_project.argtypes = [c_int] * 4 + [c_void_p] * 3 + [c_float] * 4 + [c_void_p] * 4
-    L.ocrf_prefilter.restype = c_int
-    L.ocrf_prefilter.argtypes = [c_void_p] + [c_int] * 4 + [c_float] * 2 + [c_void_p] * 5
-    L.ocrf_pillar_sample_mean.restype = c_int
-    L.ocrf_pillar_sample_mean.argtypes = [c_void_p] * 4 + [c_int] * 6 + [c_void_p]
-    L.ocrf_retain_valid_pixels.restype = c_int
-    L.ocrf_retain_valid_pixels.argtypes = [c_void_p] * 5 + [c_int] * 6 + [c_void_p]
-    L.ocrf_gauss_heads.restype = c_int
-    L.ocrf_gauss_heads.argtypes = [c_void_p] * 3 + [c_int] * 4 + [c_void_p] * 5
-    L.ocrf_gauss_heads_params_len.restype = c_int
-    L.ocrf_gauss_heads_params_len.argtypes = [c_int, c_int]
-    c_double = ctypes.c_double
-    L.ocrf_depth_labels.restype = c_int
-    L.ocrf_depth_labels.argtypes = [c_int] * 5 + [c_double] * 3 + [c_void_p] * 5
-    L.ocrf_depth_semantic_loss_workspace_bytes.restype = c_size_t
-    L.ocrf_depth_semantic_loss_workspace_bytes.argtypes = [c_int]
-    L.ocrf_depth_semantic_loss.restype = c_int
-    L.ocrf_depth_semantic_loss.argtypes = [c_int] * 3 + [c_void_p] * 4 + [c_float] * 2 + [c_void_p] * 3 + [c_size_t, c_void_p]
-    L.ocrf_depth_semantic_loss_backward.restype = c_int
-    L.ocrf_depth_semantic_loss_backward.argtypes = [c_int] * 3 + [c_void_p] * 4 + [c_float] * 2 + [c_void_p] * 5
-    L.ocrf_render_losses_workspace_bytes.restype = c_size_t
-    L.ocrf_render_losses_workspace_bytes.argtypes = [c_int] * 4
-    _render = [c_int] * 5 + [c_void_p] * 6 + [c_int] * 2 + [c_void_p, c_int] + [c_void_p] * 3 + [c_float] * 5
-    L.ocrf_render_losses.restype = c_int
-    L.ocrf_render_losses.argtypes = _render + [c_void_p] * 4 + [c_size_t, c_void_p]
-    L.ocrf_render_losses_backward.restype = c_int
-    L.ocrf_render_losses_backward.argtypes = _render + [c_void_p] * 9 + [c_void_p]
-    c_longlong = ctypes.c_longlong
-    L.ocrf_stereo_cost_volume.restype = c_int
-    L.ocrf_stereo_cost_volume.argtypes = ([c_int] * 5 + [c_void_p] * 2 + [c_void_p, c_longlong] * 3 + [c_void_p] * 4 +
-                                          [c_float, c_int, c_void_p, c_void_p])
-    L.ocrf_center_head_targets_workspace_bytes.restype = c_size_t
-    L.ocrf_center_head_targets_workspace_bytes.argtypes = [c_int]
-    L.ocrf_center_head_targets.restype = c_int
-    L.ocrf_center_head_targets.argtypes = ([c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int] + [c_void_p] * 3 +
-                                           [c_int] * 5 + [c_void_p] * 2 + [c_int, ctypes.c_double, c_int] +
-                                           [c_void_p] * 6 + [c_size_t, c_void_p])
-    L.ocrf_center_head_heatmap_loss_workspace_bytes.restype = c_size_t
-    L.ocrf_center_head_heatmap_loss_workspace_bytes.argtypes = [c_int, c_int, c_void_p, c_int]
-    L.ocrf_center_head_heatmap_loss.restype = c_int
-    L.ocrf_center_head_heatmap_loss.argtypes = ([c_int, c_int, c_void_p, c_int] + [c_void_p] * 3 + [c_float] +
-                                                [c_void_p] * 4 + [c_size_t, c_void_p])
-    L.ocrf_center_head_heatmap_loss_backward.restype = c_int
-    L.ocrf_center_head_heatmap_loss_backward.argtypes = ([c_int, c_int, c_void_p, c_int] + [c_void_p] * 4 + [c_float] +
-                                                         [c_void_p] * 2)
-    L.ocrf_center_head_reg_loss_workspace_bytes.restype = c_size_t
-    L.ocrf_center_head_reg_loss_workspace_bytes.argtypes = [c_int, c_int]
-    L.ocrf_center_head_reg_loss.restype = c_int
-    L.ocrf_center_head_reg_loss.argtypes = [c_int] * 5 + [c_void_p] * 6 + [c_float] + [c_void_p] * 3 + [c_size_t, c_void_p]
-    L.ocrf_center_head_reg_loss_backward.restype = c_int
-    L.ocrf_center_head_reg_loss_backward.argtypes = [c_int] * 5 + [c_void_p] * 7 + [c_float] + [c_void_p] * 2
-    L.ocrf_center_decode_workspace_bytes.restype = c_size_t
-    L.ocrf_center_decode_workspace_bytes.argtypes = [c_int] * 4
-    L.ocrf_center_decode.restype = c_int
-    L.ocrf_center_decode.argtypes = ([c_int, c_int, c_void_p, c_int, c_int, c_void_p] + [c_int] * 5 + [c_float] +
-                                     [c_void_p] * 2 + [c_int, c_float, c_void_p, c_int, c_float] + [c_void_p] * 8 +
-                                     [c_void_p, c_size_t, c_void_p])
-    L.ocrf_sh_to_rgb.restype = c_int
-    L.ocrf_sh_to_rgb.argtypes = [c_int] * 3 + [c_void_p] * 6
-    L.ocrf_sh_to_rgb_backward.restype = c_int
-    L.ocrf_sh_to_rgb_backward.argtypes = [c_int] * 3 + [c_void_p] * 8
-    L.ocrf_gauss_heads_backward_workspace_bytes.restype = c_size_t
-    L.ocrf_gauss_heads_backward_workspace_bytes.argtypes = [c_int] * 4
-    L.ocrf_gauss_heads_backward.restype = c_int
-    L.ocrf_gauss_heads_backward.argtypes = [c_void_p] * 3 + [c_int] * 4 + [c_void_p] * 7 + [c_size_t, c_void_p]
-    L.ocrf_nerf_alpha.restype = c_int
-    L.ocrf_nerf_alpha.argtypes = [c_void_p] * 4 + [c_int] * 3 + [c_void_p]
-    L.ocrf_nerf_render.restype = c_int
-    L.ocrf_nerf_render.argtypes = [c_void_p] * 5 + [c_int] * 4 + [c_void_p] * 3
-    L.ocrf_nerf_render_params_len.restype = c_int
-    L.ocrf_nerf_render_params_len.argtypes = []
-    L.ocrf_dual_feat_fusion.restype = c_int
-    L.ocrf_dual_feat_fusion.argtypes = [c_void_p] * 5 + [c_int] * 4 + [c_void_p]
-    L.ocrf_dual_feat_fusion_plus.restype = c_int
-    L.ocrf_dual_feat_fusion_plus.argtypes = [c_void_p] * 7 + [c_int] * 4 + [c_void_p]
-    L.ocrf_plane_stats_pair.restype = c_int
-    L.ocrf_plane_stats_pair.argtypes = [c_void_p] * 2 + [c_int] * 5 + [c_void_p] * 3
-    L.ocrf_plane_bias_act_stats.restype = c_int
-    L.ocrf_plane_bias_act_stats.argtypes = [c_void_p] * 2 + [c_int] * 8 + [c_void_p] * 3
-    L.ocrf_channel_mlp.restype = c_int
-    L.ocrf_channel_mlp.argtypes = [c_void_p] * 2 + [c_int] * 3 + [c_float] + [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 2
-    L.ocrf_scaled_channel_stats.restype = c_int
-    L.ocrf_scaled_channel_stats.argtypes = [c_void_p] * 2 + [c_int] * 3 + [c_void_p] * 2
-    L.ocrf_cbam_tail.restype = c_int
-    L.ocrf_cbam_tail.argtypes = [c_void_p] * 4 + [c_int] + [c_void_p] * 2 + [c_float] + [c_int] * 4 + [c_void_p] * 3
-    L.ocrf_hoa_dw3x3.restype = c_int
-    L.ocrf_hoa_dw3x3.argtypes = [c_void_p] * 3 + [c_int] * 4 + [c_void_p] * 2
-    L.ocrf_hoa_dw3x3_wgrad_bands.restype = c_int
-    L.ocrf_hoa_dw3x3_wgrad_bands.argtypes = [c_int]
-    L.ocrf_hoa_dw3x3_wgrad.restype = c_int
-    L.ocrf_hoa_dw3x3_wgrad.argtypes = [c_void_p] * 2 + [c_int] * 4 + [c_void_p] * 2
-    L.ocrf_diag_stamp.restype = c_int
-    L.ocrf_diag_stamp.argtypes = [c_void_p, c_void_p]
-    L.ocrf_diag_plan_stats.restype = c_int
-    L.ocrf_diag_plan_stats.argtypes = [c_void_p]
-    L.ocrf_diag_plan_resident.restype = c_int
-    L.ocrf_diag_plan_resident.argtypes = []
-    L.ocrf_diag_where.restype = c_int
-    L.ocrf_diag_where.argtypes = [c_int, c_void_p, c_int, c_void_p]
-    L.ocrf_kernel_name.restype = ctypes.c_char_p
-    L.ocrf_kernel_name.argtypes = [c_int]
-    L.ocrf_graph_node_census.restype = c_int
-    L.ocrf_graph_node_census.argtypes = [c_void_p] + [ctypes.POINTER(c_int)] * 4
-    L.ocrf_stream_create.restype = c_int
-    L.ocrf_stream_create.argtypes = [c_void_p, c_int, c_int, ctypes.POINTER(c_void_p)]
-    L.ocrf_stream_destroy.restype = c_int
-    L.ocrf_stream_destroy.argtypes = [c_void_p]
-    L.ocrf_timer_create.restype = c_int
-    L.ocrf_timer_create.argtypes = [c_int, ctypes.POINTER(c_void_p)]
-    L.ocrf_timer_arm.restype = c_int
-    L.ocrf_timer_arm.argtypes = [c_void_p, c_int]
-    L.ocrf_timer_read.restype = c_int
-    L.ocrf_timer_read.argtypes = [c_void_p, ctypes.POINTER(c_float), c_int, ctypes.POINTER(c_int)]
-    L.ocrf_timer_destroy.restype = c_int
-    L.ocrf_timer_destroy.argtypes = [c_void_p]
+# ---------------------------------------------------------------------------------------------------------------
+# The C ABI as include/ocrf_hip.h states it: the ctypes declarations, kernel ids and constants are read from there.
+# ---------------------------------------------------------------------------------------------------------------
+_HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'ocrf_hip.h')
+_SCALARS = {'int': ctypes.c_int, 'long': ctypes.c_long, 'long long': ctypes.c_longlong, 'size_t': ctypes.c_size_t,
+            'float': ctypes.c_float, 'double': ctypes.c_double, 'ocrf_stream_t': ctypes.c_void_p}
+# what a pointer may point at; every pointer is passed as c_void_p (device buffers, host out-parameters, handles)
+_POINTEES = set(_SCALARS) | {'void', 'char', 'unsigned', 'unsigned char', 'unsigned short', 'unsigned long long',
+                             'uint32_t', 'uint64_t', 'ocrf_step'}
+_PROTO = re.compile(r'^[ \t]*(\w[\w \t*]*?)\s*\b((?:ocrf_|bev_pool_v2)\w*)\s*\(([^()]*)\)\s*;', re.M)
 
 
-def _declare_step(L):
-    c_int, c_void_p = ctypes.c_int, ctypes.c_void_p
-    L.ocrf_step_fn_id.restype = c_int
-    L.ocrf_step_fn_id.argtypes = [ctypes.c_char_p]
-    L.ocrf_step_fn_args.restype = c_int
-    L.ocrf_step_fn_args.argtypes = [c_int]
-    L.ocrf_step_create.restype = c_int
-    L.ocrf_step_create.argtypes = [ctypes.POINTER(c_void_p)]
-    L.ocrf_step_destroy.restype = None
-    L.ocrf_step_destroy.argtypes = [c_void_p]
-    L.ocrf_step_add_call.restype = c_int
-    L.ocrf_step_add_call.argtypes = [c_void_p, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_uint64)]
-    L.ocrf_step_add_fork.restype = c_int
-    L.ocrf_step_add_fork.argtypes = [c_void_p, c_int, c_int]
-    L.ocrf_step_add_join.restype = c_int
-    L.ocrf_step_add_join.argtypes = [c_void_p, c_int, c_int]
-    L.ocrf_step_size.restype = c_int
-    L.ocrf_step_size.argtypes = [c_void_p]
-    L.ocrf_step_run.restype = c_int
-    L.ocrf_step_run.argtypes = [c_void_p, ctypes.POINTER(c_void_p), c_int]
-    L.ocrf_hotpath_step.restype = c_int
-    L.ocrf_hotpath_step.argtypes = [c_void_p, c_void_p, c_void_p]
+def _header_text(path=_HEADER):
+    """The header without its ``/* */`` and ``//`` comments."""
+    with open(path) as f:
+        text = re.sub(r'/\*.*?\*/', ' ', f.read(), flags=re.S)
+    return re.sub(r'//[^\n]*', '', text)
+
+
+def _ctype(spelling, proto, ret=False):
+    """ctypes type of one C type spelling (``const float *const *``, ``size_t`` ...)."""
+    words = spelling.replace('*', ' * ').split()
+    base = ' '.join(w for w in words if w not in ('const', '*'))
+    stars = words.count('*')
+    if stars == 0 and base in _SCALARS:
+        return _SCALARS[base]
+    if stars == 0 and base == 'void' and ret:
+        return None
+    if stars == 1 and base == 'char':
+        return ctypes.c_char_p
+    if stars and base in _POINTEES:
+        return ctypes.c_void_p
+    raise OcrfHipError(f'ocrf_hip.h: no ctypes type for {spelling.strip()!r} in {proto!r}')
+
+
+def parse_prototypes(text):
+    """{name: (restype, [argtypes])} of every ``ocrf_*`` / ``bev_pool_v2*`` prototype in C source ``text`` (comments
+    already stripped).  A type without a mapping raises ``OcrfHipError`` naming the prototype."""
+    out = {}
+    for m in _PROTO.finditer(text):
+        ret, name, params = m.groups()
+        proto = ' '.join(m.group(0).split())
+        params = [] if params.strip() in ('', 'void') else params.split(',')
+        # a parameter's name is its last identifier; what is in front of it is its type
+        out[name] = (_ctype(ret, proto, ret=True), [_ctype(re.sub(r'\b\w+\s*$', '', p), proto) for p in params])
+    return out
+
+
+def prototypes():
+    """The declarations of the library's entry points, from include/ocrf_hip.h."""
+    return parse_prototypes(_header_text())
+
+
+def _constants(text):
+    """``#define OCRF_X <int>`` as ``OCRF_X`` and the kernel ids ``OCRF_K_X = <int>`` as ``K_X``."""
+    consts = {k: int(v) for k, v in re.findall(r'^[ \t]*#[ \t]*define[ \t]+(OCRF_\w+)[ \t]+(-?\d+)[ \t]*$', text, re.M)}
+    consts.update((k[len('OCRF_'):], int(v)) for k, v in re.findall(r'\b(OCRF_K_\w+)\s*=\s*(\d+)', text))
+    return consts
+
+
+globals().update(_constants(_header_text()))      # K_BEV_POOL_FWD, OCRF_CD_MAX_TASKS, ...
+
+
+# passed as they are without the isinstance(a, torch.Tensor) check (~70 ns each): scalars, NULL, pre-built pointers
+_PLAIN = frozenset((int, float, type(None), ctypes.c_void_p))
+_Tensor = torch.Tensor
+
+
+def launch(name, device, *args, stream=None):
+    """Call the enqueueing entry point ``name`` on ``device``: a tensor is passed as its data pointer (0 when empty),
+    anything else as it is (scalars as Python numbers), then ``stream`` (default: torch's current stream of ``device``).
+    A non-zero hipError_t raises.  ``name`` is looked up through ``lib()`` on every call, so that a step being recorded
+    (``StepRecorder``) sees the call."""
+    with on_device(device):
+        err = getattr(lib(), name)(*[a if type(a) in _PLAIN else (a.data_ptr() if a.numel() > 0 else 0)
+                                     if isinstance(a, _Tensor) else a for a in args],
+                                   stream_ptr(device) if stream is None else stream)
+    if err != 0:
+        raise OcrfHipError(f'{name} failed with hipError_t {err}')
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -539,19 +341,15 @@ def masked_stream(device, cu_bits=None, priority=0):
             words = (ctypes.c_uint32 * n_words)()
             for b in bits:
                 words[b // 32] |= 1 << (b % 32)
-            check(lib().ocrf_stream_create(ctypes.cast(words, c_void_p_t), n_words, 0, ctypes.byref(h)), 'ocrf_stream_create')
+            check(lib().ocrf_stream_create(words, n_words, 0, ctypes.byref(h)), 'ocrf_stream_create')
     return torch.cuda.ExternalStream(h.value, device=device)
-
-
-c_void_p_t = ctypes.c_void_p
 
 
 def diag_stamp(stamps, index):
     """Diagnostic: store the device clock (100 MHz) into ``stamps[index]`` (int64, cuda) when torch's current
     stream reaches this point — works inside a captured graph (``ocrf_diag_stamp``)."""
     require_cuda(stamps)
-    check(lib().ocrf_diag_stamp(ctypes.c_void_p(stamps.data_ptr() + 8 * index), stream_ptr(stamps.device)),
-          'ocrf_diag_stamp')
+    launch('ocrf_diag_stamp', stamps.device, stamps.data_ptr() + 8 * index)
 
 
 class Workspace:
@@ -608,16 +406,6 @@ class Workspace:
 
 
 workspace = Workspace()
-
-
-K_BEV_POOL_FWD, K_BEV_POOL_FIXUP, K_BEV_POOL_INTERVAL, K_BEV_POOL_GRAD, K_BEV_POOL_NCHW = 1, 2, 3, 4, 5
-K_BEV_POOL_MFMA, K_BEV_POOL_PANEL, K_BEV_POOL_CELL_WEIGHTS = 6, 7, 8
-K_RASTER_PREPROCESS, K_RASTER_BLEND, K_RASTER_GATHER = 10, 11, 12
-K_RASTER_SCAN, K_RASTER_BLEND_BWD, K_RASTER_PRE_BWD = 13, 15, 16
-K_RASTER_PLAN_UPDATE, K_RASTER_BLEND_SORTED, K_RASTER_BLEND_SECOND = 17, 18, 19
-K_LSS_KEYS, K_RADIX_HIST, K_SCAN, K_RADIX_SCATTER, K_LSS_BOUNDS, K_LSS_EMIT, K_HT_COUNT, K_HT_EMIT = range(40, 48)
-K_HOA_STATS, K_HOA_MASK_GATE, K_HOA_HEIGHT_MAX, K_HOA_HEIGHT_GATE = 20, 21, 22, 23
-K_HOA_UNET_BLOCK, K_HOA_OUT_CONV, K_HOA1_ATTN, K_HOA1_KV = 24, 25, 26, 29
 
 
 class KernelTimer:

@@ -17,7 +17,6 @@ interval_lengths)``  -> ``(B, C, Z, Y, X)`` contiguous fp32                     
 All compute is in ``csrc/bev_pool.hip`` behind the C ABI of ``include/ocrf_hip.h``.  There is no
 CPU path: CPU tensors raise ``OcrfHipError``.
 """
-import ctypes
 import os
 
 import torch
@@ -71,28 +70,19 @@ class _ExtensionAPI:
         n_pts = ranks_depth.numel()
         if ranks_feat.numel() != n_pts or ranks_bev.numel() != n_pts or interval_starts.numel() != n_iv:
             raise _lib.OcrfHipError('rank / interval vectors disagree in length')
-        L = _lib.lib()
-        dev = depth.device
-        with _lib.on_device(dev):                  # OptionalCUDAGuard, bev_pool.cpp:42
-            stream = _lib.stream_ptr(dev)
-            if os.environ.get('OCRF_CHECK_INTERVALS', '0') == '1':
-                flag = torch.zeros(1, dtype=torch.int32, device=dev)
-                _lib.check(L.ocrf_bev_pool_v2_check_intervals(
-                    n_iv, n_pts, _lib.ptr(interval_starts), _lib.ptr(interval_lengths),
-                    _lib.ptr(flag), stream), 'ocrf_bev_pool_v2_check_intervals')
-                bad = int(flag.item())
-                if bad:
-                    raise _lib.OcrfHipError(
-                        f'intervals are not an ascending non-overlapping cover (flag={bad}); the '
-                        'C entry point bev_pool_v2() accepts arbitrary layouts')
-            n_vox = out.numel() // max(channels, 1)
-            need = L.ocrf_bev_pool_v2_workspace_bytes(channels, n_pts, n_vox)
-            scratch = _lib.workspace.get(dev, need, 'bev_pool')
-            _lib.check(L.ocrf_bev_pool_v2(
-                channels, n_iv, n_pts, n_vox, _lib.ptr(depth), _lib.ptr(feat), _lib.ptr(ranks_depth),
-                _lib.ptr(ranks_feat), _lib.ptr(ranks_bev), _lib.ptr(interval_starts),
-                _lib.ptr(interval_lengths), _lib.ptr(out), _lib.ptr(scratch),
-                ctypes.c_size_t(scratch.numel()), stream), 'ocrf_bev_pool_v2')
+        dev = depth.device                         # launch() is the OptionalCUDAGuard, bev_pool.cpp:42
+        if os.environ.get('OCRF_CHECK_INTERVALS', '0') == '1':
+            flag = torch.zeros(1, dtype=torch.int32, device=dev)
+            _lib.launch('ocrf_bev_pool_v2_check_intervals', dev, n_iv, n_pts, interval_starts, interval_lengths, flag)
+            bad = int(flag.item())
+            if bad:
+                raise _lib.OcrfHipError(
+                    f'intervals are not an ascending non-overlapping cover (flag={bad}); the '
+                    'C entry point bev_pool_v2() accepts arbitrary layouts')
+        n_vox = out.numel() // max(channels, 1)
+        scratch = _lib.workspace.get(dev, _lib.lib().ocrf_bev_pool_v2_workspace_bytes(channels, n_pts, n_vox), 'bev_pool')
+        _lib.launch('ocrf_bev_pool_v2', dev, channels, n_iv, n_pts, n_vox, depth, feat, ranks_depth, ranks_feat, ranks_bev,
+                    interval_starts, interval_lengths, out, scratch, scratch.numel())
 
     @staticmethod
     def bev_pool_v2_backward(out_grad, depth_grad, feat_grad, depth, feat, ranks_depth,
@@ -107,14 +97,8 @@ class _ExtensionAPI:
                         ('interval_starts', interval_starts)):
             _want(t, torch.int32, name)
         channels = out_grad.size(4)                   # `c = _out_grad.size(4)`, bev_pool.cpp:86
-        L = _lib.lib()
-        dev = out_grad.device
-        with _lib.on_device(dev):
-            _lib.check(L.ocrf_bev_pool_v2_grad(
-                channels, interval_lengths.size(0), _lib.ptr(out_grad), _lib.ptr(depth),
-                _lib.ptr(feat), _lib.ptr(ranks_depth), _lib.ptr(ranks_feat), _lib.ptr(ranks_bev),
-                _lib.ptr(interval_starts), _lib.ptr(interval_lengths), _lib.ptr(depth_grad),
-                _lib.ptr(feat_grad), _lib.stream_ptr(dev)), 'ocrf_bev_pool_v2_grad')
+        _lib.launch('ocrf_bev_pool_v2_grad', out_grad.device, channels, interval_lengths.size(0), out_grad, depth, feat,
+                    ranks_depth, ranks_feat, ranks_bev, interval_starts, interval_lengths, depth_grad, feat_grad)
 
 
 bev_pool_v2_ext = _ExtensionAPI()
@@ -183,15 +167,10 @@ class _FusedPool(torch.autograd.Function):
         dev = d32.device
         out = torch.empty((B, C, Z, Y, X) if layout == 0 else (B, Z * C, Y, X),
                           dtype=torch.float32, device=dev)
-        L = _lib.lib()
-        with _lib.on_device(dev):
-            need = L.ocrf_bev_pool_v2_nchw_workspace_bytes(C, n_iv, n_pts, B, Z, Y, X)
-            scratch = _lib.workspace.get(dev, need, 'bev_pool_nchw')
-            _lib.check(L.ocrf_bev_pool_v2_nchw(
-                C, n_iv, n_pts, _lib.ptr(d32), _lib.ptr(f32), _lib.ptr(rd), _lib.ptr(rf),
-                _lib.ptr(rb), _lib.ptr(starts), _lib.ptr(lengths), _lib.ptr(out), B, Z, Y, X,
-                int(layout), _lib.ptr(scratch), ctypes.c_size_t(scratch.numel()),
-                _lib.stream_ptr(dev)), 'ocrf_bev_pool_v2_nchw')
+        need = _lib.lib().ocrf_bev_pool_v2_nchw_workspace_bytes(C, n_iv, n_pts, B, Z, Y, X)
+        scratch = _lib.workspace.get(dev, need, 'bev_pool_nchw')
+        _lib.launch('ocrf_bev_pool_v2_nchw', dev, C, n_iv, n_pts, d32, f32, rd, rf, rb, starts, lengths, out, B, Z, Y, X,
+                    int(layout), scratch, scratch.numel())
         ctx.save_for_backward(rb, d32, f32, rf, rd)
         ctx.geom = (B, Z, Y, X, C, int(layout))
         return out
@@ -245,15 +224,10 @@ def bev_pool_v2_device_counts(depth, feat, ranks_depth, ranks_feat, ranks_bev, b
     cap_pts, cap_iv = ranks_depth.numel(), interval_starts.numel()
     dev = d32.device
     out = torch.empty((B, C, Z, Y, X) if layout == 0 else (B, Z * C, Y, X), dtype=torch.float32, device=dev)
-    L = _lib.lib()
-    with _lib.on_device(dev):
-        need = L.ocrf_bev_pool_v2_nchw_workspace_bytes(C, cap_iv, cap_pts, B, Z, Y, X)
-        scratch = _lib.workspace.get(dev, need, scratch_tag)
-        _lib.check(L.ocrf_bev_pool_v2_nchw_dyn(
-            C, cap_iv, cap_pts, _lib.ptr(counts), _lib.ptr(d32), _lib.ptr(f32), _lib.ptr(ranks_depth),
-            _lib.ptr(ranks_feat), _lib.ptr(ranks_bev), _lib.ptr(interval_starts), _lib.ptr(interval_lengths),
-            _lib.ptr(out), B, Z, Y, X, int(layout), _lib.ptr(scratch), ctypes.c_size_t(scratch.numel()),
-            _lib.stream_ptr(dev)), 'ocrf_bev_pool_v2_nchw_dyn')
+    need = _lib.lib().ocrf_bev_pool_v2_nchw_workspace_bytes(C, cap_iv, cap_pts, B, Z, Y, X)
+    scratch = _lib.workspace.get(dev, need, scratch_tag)
+    _lib.launch('ocrf_bev_pool_v2_nchw_dyn', dev, C, cap_iv, cap_pts, counts, d32, f32, ranks_depth, ranks_feat, ranks_bev,
+                interval_starts, interval_lengths, out, B, Z, Y, X, int(layout), scratch, scratch.numel())
     return out
 
 
@@ -322,15 +296,12 @@ class DevicePoolPlan:
         dev = rb.device
         L = _lib.lib()
         self.plan = torch.empty(L.ocrf_bev_pool_plan_bytes(C, self.n_points, B, Z, Y, X), dtype=torch.uint8, device=dev)
-        with _lib.on_device(dev):
-            _lib.check(L.ocrf_bev_pool_plan_build(C, self.n_intervals, self.n_points, _lib.ptr(rb), _lib.ptr(st), _lib.ptr(ln),
-                                                  B, Z, Y, X, _lib.ptr(self.plan),
-                                                  ctypes.c_size_t(self.plan.numel()), _lib.stream_ptr(dev)),
-                       'ocrf_bev_pool_plan_build')
-            # the slabs of cut tiles: owned by the plan (its lifetime, not the process-wide grow-only workspace), so a
-            # plan can run beside another plan's launch and a dropped plan returns its memory
-            self.scratch = torch.empty(max(int(L.ocrf_bev_pool_planned_workspace_bytes(C, self.n_points)), 256),
-                                       dtype=torch.uint8, device=dev)
+        _lib.launch('ocrf_bev_pool_plan_build', dev, C, self.n_intervals, self.n_points, rb, st, ln, B, Z, Y, X, self.plan,
+                    self.plan.numel())
+        # the slabs of cut tiles: owned by the plan (its lifetime, not the process-wide grow-only workspace), so a
+        # plan can run beside another plan's launch and a dropped plan returns its memory
+        self.scratch = torch.empty(max(int(L.ocrf_bev_pool_planned_workspace_bytes(C, self.n_points)), 256),
+                                   dtype=torch.uint8, device=dev)
 
 
 @torch.no_grad()
@@ -350,14 +321,9 @@ def bev_pool_v2_planned(depth, feat, plan, layout=1, out=None):
         out = torch.empty(shape, dtype=torch.float32, device=dev)
     elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * C * Z * Y * X or out.device != dev:
         raise _lib.OcrfHipError('out must be a contiguous fp32 tensor of B*C*Z*Y*X elements on the inputs\' device')
-    L = _lib.lib()
-    with _lib.on_device(dev):
-        scratch = plan.scratch
-        _lib.check(L.ocrf_bev_pool_v2_nchw_planned(
-            C, plan.n_points, _lib.ptr(d32), _lib.ptr(f32), _lib.ptr(plan.ranks_depth),
-            _lib.ptr(plan.ranks_feat), _lib.ptr(plan.plan), _lib.ptr(out), B, Z, Y, X, int(layout), _lib.ptr(scratch),
-            ctypes.c_size_t(scratch.numel()), ctypes.c_size_t(d32.numel() * 4), ctypes.c_size_t(f32.numel() * 4),
-            _lib.stream_ptr(dev)), 'ocrf_bev_pool_v2_nchw_planned')
+    _lib.launch('ocrf_bev_pool_v2_nchw_planned', dev, C, plan.n_points, d32, f32, plan.ranks_depth, plan.ranks_feat,
+                plan.plan, out, B, Z, Y, X, int(layout), plan.scratch, plan.scratch.numel(), d32.numel() * 4,
+                f32.numel() * 4)
     return out
 
 
@@ -534,12 +500,9 @@ def bev_pool_v2_mfma(depth, feat, plan, layout=1, out=None):
         out = torch.empty(shape, dtype=torch.float32, device=dev)
     elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * C * Z * Y * X or out.device != dev:
         raise _lib.OcrfHipError('out must be a contiguous fp32 tensor of B*C*Z*Y*X elements on the inputs\' device')
-    L = _lib.lib()
-    with _lib.on_device(dev):
-        _lib.check(L.ocrf_bev_pool_v2_nchw_mfma(
-            C, plan.n_units, _lib.ptr(plan.units), _lib.ptr(plan.unit_slab), _lib.ptr(plan.panel_rows),
-            _lib.ptr(plan.panel_nrows), _lib.ptr(plan.panel_cell_off), _lib.ptr(plan.cells), _lib.ptr(plan.rd_sorted), _lib.ptr(d32), _lib.ptr(f32), _lib.ptr(out), B, Z, Y, X, int(layout),
-            _lib.ptr(plan.arrive), _lib.ptr(plan.slabs), _lib.stream_ptr(dev)), 'ocrf_bev_pool_v2_nchw_mfma')
+    _lib.launch('ocrf_bev_pool_v2_nchw_mfma', dev, C, plan.n_units, plan.units, plan.unit_slab, plan.panel_rows,
+                plan.panel_nrows, plan.panel_cell_off, plan.cells, plan.rd_sorted, d32, f32, out, B, Z, Y, X, int(layout),
+                plan.arrive, plan.slabs)
     return out
 
 
@@ -550,15 +513,10 @@ def bev_pool_cell_weights(depth, plan, plan2=None):
     d32 = depth.float().contiguous()
     _check_32bit_offsets(d32)
     _lib.require_cuda(d32)
-    L = _lib.lib()
     n2 = plan2.n_cells if (plan2 is not None and plan2.n_points) else 0
     n1 = plan.n_cells if plan.n_points else 0
-    null = ctypes.c_void_p(0)
-    with _lib.on_device(d32.device):
-        _lib.check(L.ocrf_bev_pool_cell_weights(
-            n1, _lib.ptr(plan.cells), _lib.ptr(plan.rd_sorted), _lib.ptr(plan.cw),
-            n2, _lib.ptr(plan2.cells) if n2 else null, _lib.ptr(plan2.rd_sorted) if n2 else null,
-            _lib.ptr(plan2.cw) if n2 else null, _lib.ptr(d32), _lib.stream_ptr(d32.device)), 'ocrf_bev_pool_cell_weights')
+    _lib.launch('ocrf_bev_pool_cell_weights', d32.device, n1, plan.cells, plan.rd_sorted, plan.cw,
+                n2, plan2.cells if n2 else None, plan2.rd_sorted if n2 else None, plan2.cw if n2 else None, d32)
     return d32
 
 
@@ -581,14 +539,9 @@ def bev_pool_v2_panel(depth, feat, plan, layout=1, out=None, weights_ready=False
         out = torch.empty(shape, dtype=torch.float32, device=dev)
     elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * C * Z * Y * X or out.device != dev:
         raise _lib.OcrfHipError('out must be a contiguous fp32 tensor of B*C*Z*Y*X elements on the inputs\' device')
-    L = _lib.lib()
-    with _lib.on_device(dev):
-        _lib.check(L.ocrf_bev_pool_v2_nchw_panel(
-            C, plan.n_units, _lib.ptr(plan.units), _lib.ptr(plan.unit_slab), _lib.ptr(plan.panel_rows),
-            _lib.ptr(plan.panel_nrows), _lib.ptr(plan.panel_cell_off), _lib.ptr(plan.panel_voff), _lib.ptr(plan.cell_code),
-            _lib.ptr(plan.cw), _lib.ptr(f32), _lib.ptr(out), B, Z, Y, X, int(layout),
-            _lib.ptr(plan.arrive), _lib.ptr(plan.slabs), ctypes.c_size_t(f32.numel() * 4), _lib.stream_ptr(dev)),
-            'ocrf_bev_pool_v2_nchw_panel')
+    _lib.launch('ocrf_bev_pool_v2_nchw_panel', dev, C, plan.n_units, plan.units, plan.unit_slab, plan.panel_rows,
+                plan.panel_nrows, plan.panel_cell_off, plan.panel_voff, plan.cell_code, plan.cw, f32, out, B, Z, Y, X,
+                int(layout), plan.arrive, plan.slabs, f32.numel() * 4)
     return out
 
 

@@ -37,8 +37,8 @@ from . import _lib
 __all__ = ['CenterPointBBoxCoder', 'DecodeConfig', 'box_corners', 'box_iou_rotated_bev', 'iou_rotated_pairs',
            'nms_bev', 'circle_nms', 'xywhr2xyxyr', 'decode_torch', 'decode_fused', 'MAX_CLASSES']
 
-MAX_TASKS = 8                 # OCRF_CD_MAX_TASKS
-MAX_CLASSES = 8               # OCRF_CD_MAX_CLASSES
+MAX_TASKS = _lib.OCRF_CD_MAX_TASKS
+MAX_CLASSES = _lib.OCRF_CD_MAX_CLASSES
 HEAD_KEYS = ('heatmap', 'reg', 'height', 'dim', 'rot', 'vel')
 _POLY_CAP = 12
 
@@ -408,20 +408,17 @@ def decode_fused(preds_dicts, cfg, norm_bbox=True):
     scores = torch.empty(B, M, device=dev)
     labels = torch.empty(B, M, dtype=torch.int32, device=dev)
     counts = torch.empty(B, dtype=torch.int32, device=dev)
-    L = _lib.lib()
-    ws = _lib.workspace.get(dev, L.ocrf_center_decode_workspace_bytes(B, T, cfg.K, cfg.post_max), 'center_decode')
+    ws = _lib.workspace.get(dev, _lib.lib().ocrf_center_decode_workspace_bytes(B, T, cfg.K, cfg.post_max), 'center_decode')
     coder = cfg.coder
     f2 = lambda v: (ctypes.c_float * len(v))(*[float(x) for x in v])  # noqa: E731
     ptrs = (ctypes.c_void_p * len(flat))(*[t.data_ptr() if t is not None else 0 for t in flat])
-    with _lib.on_device(dev):
-        _lib.check(L.ocrf_center_decode(
-            B, T, (ctypes.c_int * T)(*cfg.ncls), H, W, ptrs, int(with_vel), int(norm_bbox), cfg.K, cfg.pre_max,
-            cfg.post_max, float(coder.out_size_factor), f2(coder.voxel_size[:2]), f2(coder.pc_range[:2]),
-            int(cfg.coder_thr is not None), cfg.coder_thr or 0.0, f2(cfg.center) if cfg.center else None,
-            int(cfg.score_thr is not None), cfg.score_thr or 0.0, f2(cfg.limit) if cfg.limit else None,
-            (ctypes.c_int * T)(*[int(c) for c in cfg.circle]), (ctypes.c_double * T)(*cfg.thr),
-            cfg.factor.ctypes.data_as(ctypes.c_void_p), _lib.ptr(boxes), _lib.ptr(scores), _lib.ptr(labels),
-            _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), 'ocrf_center_decode')
+    _lib.launch('ocrf_center_decode', dev,
+                B, T, (ctypes.c_int * T)(*cfg.ncls), H, W, ptrs, int(with_vel), int(norm_bbox), cfg.K, cfg.pre_max,
+                cfg.post_max, float(coder.out_size_factor), f2(coder.voxel_size[:2]), f2(coder.pc_range[:2]),
+                int(cfg.coder_thr is not None), cfg.coder_thr or 0.0, f2(cfg.center) if cfg.center else None,
+                int(cfg.score_thr is not None), cfg.score_thr or 0.0, f2(cfg.limit) if cfg.limit else None,
+                (ctypes.c_int * T)(*[int(c) for c in cfg.circle]), (ctypes.c_double * T)(*cfg.thr),
+                cfg.factor.ctypes.data_as(ctypes.c_void_p), boxes, scores, labels, counts, ws, ws.numel())
     return boxes, scores, labels, counts
 
 

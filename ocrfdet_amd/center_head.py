@@ -328,17 +328,13 @@ def targets_fused(boxes, labels, offsets, table, ncls, cfg, with_velocity, norm_
     ind = torch.empty(T, B, M, dtype=torch.int64, device=dev)
     mask = torch.empty(T, B, M, dtype=torch.uint8, device=dev)
     counts = torch.empty(2 * T, device=dev)
-    L = _lib.lib()
-    ws = _lib.workspace.get(dev, L.ocrf_center_head_targets_workspace_bytes(N), 'center_head_targets')
+    ws = _lib.workspace.get(dev, _lib.lib().ocrf_center_head_targets_workspace_bytes(N), 'center_head_targets')
     vs = (ctypes.c_float * 2)(*[float(v) for v in cfg['voxel_size'][:2]])
     pc = (ctypes.c_float * 2)(*[float(v) for v in cfg['point_cloud_range'][:2]])
     boxes, labels = boxes.contiguous(), labels.contiguous()
-    with _lib.on_device(dev):
-        _lib.check(L.ocrf_center_head_targets(
-            B, T, _ints(ncls), table.shape[0], _lib.ptr(table), N, D, _lib.ptr(boxes), _lib.ptr(labels),
-            _lib.ptr(offsets), H, W, M, int(with_velocity), int(norm_bbox), vs, pc, int(cfg['out_size_factor']),
-            float(cfg['gaussian_overlap']), int(cfg['min_radius']), _lib.ptr(heat), _lib.ptr(anno), _lib.ptr(ind),
-            _lib.ptr(mask), _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), 'ocrf_center_head_targets')
+    _lib.launch('ocrf_center_head_targets', dev, B, T, _ints(ncls), table.shape[0], table, N, D, boxes, labels, offsets,
+                H, W, M, int(with_velocity), int(norm_bbox), vs, pc, int(cfg['out_size_factor']),
+                float(cfg['gaussian_overlap']), int(cfg['min_radius']), heat, anno, ind, mask, counts, ws, ws.numel())
     return heat, anno, ind, mask, counts
 
 
@@ -355,14 +351,10 @@ class HeatmapLoss(torch.autograd.Function):
         clipped = [torch.empty_like(l) for l in x]
         out = torch.empty(len(x), device=dev)
         dens = torch.empty(len(x), device=dev)
-        L = _lib.lib()
-        ws = _lib.workspace.get(dev, L.ocrf_center_head_heatmap_loss_workspace_bytes(B, len(x), _ints(ncls), HW),
+        ws = _lib.workspace.get(dev, _lib.lib().ocrf_center_head_heatmap_loss_workspace_bytes(B, len(x), _ints(ncls), HW),
                                 'center_head_hm')
-        with _lib.on_device(dev):
-            _lib.check(L.ocrf_center_head_heatmap_loss(B, len(x), _ints(ncls), HW, _ptrs(x), _lib.ptr(heat),
-                                                       _lib.ptr(counts), float(loss_weight), _ptrs(clipped),
-                                                       _lib.ptr(out), _lib.ptr(dens), _lib.ptr(ws), ws.numel(),
-                                                       _lib.stream_ptr(dev)), 'ocrf_center_head_heatmap_loss')
+        _lib.launch('ocrf_center_head_heatmap_loss', dev, B, len(x), _ints(ncls), HW, _ptrs(x), heat, counts,
+                    float(loss_weight), _ptrs(clipped), out, dens, ws, ws.numel())
         ctx.save_for_backward(heat, dens, *x)
         ctx.loss_weight = float(loss_weight)
         ctx.mark_non_differentiable(*clipped)
@@ -376,10 +368,8 @@ class HeatmapLoss(torch.autograd.Function):
         dev = x[0].device
         grads = [torch.empty_like(l) for l in x]
         go = g_out.float().contiguous()
-        with _lib.on_device(dev):
-            _lib.check(_lib.lib().ocrf_center_head_heatmap_loss_backward(
-                B, len(x), _ints(ncls), HW, _ptrs(x), _lib.ptr(heat), _lib.ptr(dens), _lib.ptr(go), ctx.loss_weight,
-                _ptrs(grads), _lib.stream_ptr(dev)), 'ocrf_center_head_heatmap_loss_backward')
+        _lib.launch('ocrf_center_head_heatmap_loss_backward', dev, B, len(x), _ints(ncls), HW, _ptrs(x), heat, dens, go,
+                    ctx.loss_weight, _ptrs(grads))
         return (None, None, None, *grads)
 
 
@@ -396,13 +386,9 @@ class RegLoss(torch.autograd.Function):
         out = torch.empty(T, 6, device=dev)
         dens = torch.empty(T, 2, device=dev)
         cw = (ctypes.c_float * C)(*[float(v) for v in code_weights[:C]])
-        L = _lib.lib()
-        ws = _lib.workspace.get(dev, L.ocrf_center_head_reg_loss_workspace_bytes(B, T), 'center_head_reg')
-        with _lib.on_device(dev):
-            _lib.check(L.ocrf_center_head_reg_loss(B, T, HW, M, int(with_velocity), _ptrs(h), _lib.ptr(anno),
-                                                   _lib.ptr(ind), _lib.ptr(mask), cw, _lib.ptr(counts),
-                                                   float(loss_weight), _lib.ptr(out), _lib.ptr(dens), _lib.ptr(ws),
-                                                   ws.numel(), _lib.stream_ptr(dev)), 'ocrf_center_head_reg_loss')
+        ws = _lib.workspace.get(dev, _lib.lib().ocrf_center_head_reg_loss_workspace_bytes(B, T), 'center_head_reg')
+        _lib.launch('ocrf_center_head_reg_loss', dev, B, T, HW, M, int(with_velocity), _ptrs(h), anno, ind, mask, cw, counts,
+                    float(loss_weight), out, dens, ws, ws.numel())
         ctx.save_for_backward(anno, ind, mask, dens, *[v for v in h if v is not None])
         ctx.present = [v is not None for v in h]
         ctx.args = ([float(v) for v in code_weights[:C]], float(loss_weight), int(with_velocity))
@@ -424,11 +410,8 @@ class RegLoss(torch.autograd.Function):
             o += n
         cw, lw, wv = ctx.args
         go = g_out.float().contiguous()
-        with _lib.on_device(dev):
-            _lib.check(_lib.lib().ocrf_center_head_reg_loss_backward(
-                B, T, HW, M, wv, _ptrs(h), _lib.ptr(anno), _lib.ptr(ind), _lib.ptr(mask), (ctypes.c_float * C)(*cw),
-                _lib.ptr(dens), _lib.ptr(go), lw, _ptrs(grads), _lib.stream_ptr(dev)),
-                'ocrf_center_head_reg_loss_backward')
+        _lib.launch('ocrf_center_head_reg_loss_backward', dev, B, T, HW, M, wv, _ptrs(h), anno, ind, mask,
+                    (ctypes.c_float * C)(*cw), dens, go, lw, _ptrs(grads))
         return (None,) * 7 + tuple(grads)
 
 

@@ -221,11 +221,8 @@ def stereo_cost_volume_hip(metas, bias, raw=False):
     fr = metas['frustum'].detach().to(dev, torch.float32)
     u, v, d = fr[0, 0, :, 0], fr[0, :, 0, 1], fr[:, 0, 0, 2]
     out = torch.empty(BN, D, H, W, device=dev)
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().ocrf_stereo_cost_volume(
-            BN, C, H, W, D, _lib.ptr(prev), _lib.ptr(curr), _lib.ptr(u), u.stride(0), _lib.ptr(v), v.stride(0),
-            _lib.ptr(d), d.stride(0), *(_lib.ptr(t) for t in cal), float(bias), 1 if raw else 0, _lib.ptr(out),
-            _lib.stream_ptr(dev)), 'ocrf_stereo_cost_volume')
+    _lib.launch('ocrf_stereo_cost_volume', dev, BN, C, H, W, D, prev, curr, u, u.stride(0), v, v.stride(0), d, d.stride(0),
+                *cal, float(bias), 1 if raw else 0, out)
     return out
 
 

@@ -27,7 +27,6 @@ depth has no backward in the fork either (diff-gaussian-rasterization-w-depth/RE
 ``raster_settings.sh_degree`` / ``campos``; OcRFDet itself passes ``shs=None``) are evaluated by ``ocrf_sh_to_rgb`` into the
 (P,3) colours of the ordinary pipeline, forward and backward (``forward.cu:20-71``, ``backward.cu:20-140``).
 """
-import ctypes
 from typing import NamedTuple
 
 import torch
@@ -89,9 +88,7 @@ def sh_to_rgb(means3D, campos, shs, degree):
     dev = means3D.device
     colors = torch.empty(P, 3, device=dev)
     clamped = torch.empty(P, 3, dtype=torch.uint8, device=dev)
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().ocrf_sh_to_rgb(P, degree, M, _lib.ptr(means3D), _lib.ptr(campos), _lib.ptr(shs),
-                                             _lib.ptr(colors), _lib.ptr(clamped), _lib.stream_ptr(dev)), 'ocrf_sh_to_rgb')
+    _lib.launch('ocrf_sh_to_rgb', dev, P, degree, M, means3D, campos, shs, colors, clamped)
     return colors, clamped
 
 
@@ -107,10 +104,8 @@ def sh_to_rgb_backward(means3D, campos, shs, degree, clamped, dL_dcolors, dL_dme
     elif not (dL_dmeans3D.is_contiguous() and dL_dmeans3D.dtype == torch.float32 and dL_dmeans3D.numel() == 3 * P):
         raise RuntimeError('dL_dmeans3D must be a contiguous float32 (P,3) tensor')
     d_sh = torch.empty(P, M, 3, device=dev)
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().ocrf_sh_to_rgb_backward(
-            P, int(degree), M, _lib.ptr(means3D), _lib.ptr(campos), _lib.ptr(shs), _lib.ptr(clamped.contiguous()),
-            _lib.ptr(g), _lib.ptr(dL_dmeans3D), _lib.ptr(d_sh), _lib.stream_ptr(dev)), 'ocrf_sh_to_rgb_backward')
+    _lib.launch('ocrf_sh_to_rgb_backward', dev, P, int(degree), M, means3D, campos, shs, clamped.contiguous(), g,
+                dL_dmeans3D, d_sh)
     return dL_dmeans3D, d_sh
 
 
@@ -146,16 +141,10 @@ def rasterize_views_backward(grad_color, fwd, means3D, colors, opacities, scales
         if m2d is not None:
             out['means2D'] = m2d
         return out
-    L = _lib.lib()
-    with _lib.on_device(dev):
-        need = L.ocrf_rasterize_backward_workspace_bytes(P, V)
-        ws = _lib.workspace.get(dev, need, 'raster')
-        _lib.check(L.ocrf_rasterize_backward(
-            P, V, H, W, _lib.ptr(means3D), _lib.ptr(colors), _lib.ptr(opac), _lib.ptr(sc),
-            ctypes.c_float(scale_modifier), _lib.ptr(rot), _lib.ptr(cams), _lib.ptr(bg), _lib.ptr(fc), _lib.ptr(ft),
-            _lib.ptr(fn), _lib.ptr(g), _lib.ptr(out['means3D']), _lib.ptr(out['colors']), _lib.ptr(out['opacities']),
-            _lib.ptr(out['scales']), _lib.ptr(out['rotations']), _lib.ptr(m2d), _lib.ptr(ws),
-            ctypes.c_size_t(ws.numel()), _lib.stream_ptr(dev)), 'ocrf_rasterize_backward')
+    ws = _lib.workspace.get(dev, _lib.lib().ocrf_rasterize_backward_workspace_bytes(P, V), 'raster')
+    _lib.launch('ocrf_rasterize_backward', dev, P, V, H, W, means3D, colors, opac, sc, float(scale_modifier), rot, cams, bg,
+                fc, ft, fn, g, out['means3D'], out['colors'], out['opacities'], out['scales'], out['rotations'], m2d,
+                ws, ws.numel())
     if m2d is not None:
         out['means2D'] = m2d
     return out
@@ -197,16 +186,10 @@ def rasterize_views(means3D, colors, opacities, scales, rotations, viewmatrices,
         out['n_contrib'] = torch.empty(V, H, W, dtype=torch.int32, device=dev)
     tt = torch.empty(V, P, dtype=torch.int32, device=dev) if want_tiles_touched else None
     status = torch.empty(1, dtype=torch.int32, device=dev)      # zeroed on the device by the bucket scan kernel
-    L = _lib.lib()
-    with _lib.on_device(dev):
-        need = L.ocrf_rasterize_workspace_bytes(P, V)
-        ws = _lib.workspace.get(dev, need, workspace_tag)
-        _lib.check(L.ocrf_rasterize_forward(
-            P, V, H, W, _lib.ptr(means3D), _lib.ptr(colors), _lib.ptr(opac), _lib.ptr(sc),
-            ctypes.c_float(scale_modifier), _lib.ptr(rot), _lib.ptr(cov), _lib.ptr(cams), _lib.ptr(bg),
-            {'median': 0, 'mean': 1}[depth_mode], _lib.ptr(out['color']), _lib.ptr(out['depth']),
-            _lib.ptr(out['final_T']), _lib.ptr(out.get('n_contrib')), _lib.ptr(out['radii']), _lib.ptr(tt),
-            _lib.ptr(status), _lib.ptr(ws), ctypes.c_size_t(ws.numel()), _lib.stream_ptr(dev)), 'ocrf_rasterize_forward')
+    ws = _lib.workspace.get(dev, _lib.lib().ocrf_rasterize_workspace_bytes(P, V), workspace_tag)
+    _lib.launch('ocrf_rasterize_forward', dev, P, V, H, W, means3D, colors, opac, sc, float(scale_modifier), rot, cov, cams,
+                bg, {'median': 0, 'mean': 1}[depth_mode], out['color'], out['depth'], out['final_T'], out.get('n_contrib'),
+                out['radii'], tt, status, ws, ws.numel())
     if tt is not None:
         out['tiles_touched'] = tt
     out['status'] = status     # device int, informational: 2 = the exact streaming path ran for some tile
@@ -236,16 +219,10 @@ def rasterize_sets(means3D, colors, opacities, scales, rotations, packed_cameras
     if want_n_contrib:
         out['n_contrib'] = torch.empty(NV, H, W, dtype=torch.int32, device=dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
-    L = _lib.lib()
-    with _lib.on_device(dev):
-        need = L.ocrf_rasterize_workspace_bytes(P, NV)
-        ws = _lib.workspace.get(dev, need, workspace_tag)
-        _lib.check(L.ocrf_rasterize_forward_sets(
-            P, S, NV // S, H, W, _lib.ptr(means3D), _lib.ptr(colors), _lib.ptr(opac), _lib.ptr(sc),
-            ctypes.c_float(scale_modifier), _lib.ptr(rot), _lib.ptr(None), _lib.ptr(cams), _lib.ptr(bg),
-            {'median': 0, 'mean': 1}[depth_mode], _lib.ptr(out['color']), _lib.ptr(out['depth']), _lib.ptr(out['final_T']),
-            _lib.ptr(out.get('n_contrib')), _lib.ptr(out['radii']), _lib.ptr(None), _lib.ptr(status), _lib.ptr(ws),
-            ctypes.c_size_t(ws.numel()), _lib.stream_ptr(dev)), 'ocrf_rasterize_forward_sets')
+    ws = _lib.workspace.get(dev, _lib.lib().ocrf_rasterize_workspace_bytes(P, NV), workspace_tag)
+    _lib.launch('ocrf_rasterize_forward_sets', dev, P, S, NV // S, H, W, means3D, colors, opac, sc, float(scale_modifier),
+                rot, None, cams, bg, {'median': 0, 'mean': 1}[depth_mode], out['color'], out['depth'], out['final_T'],
+                out.get('n_contrib'), out['radii'], None, status, ws, ws.numel())
     out['status'] = status
     return out
 
@@ -269,14 +246,9 @@ def _backward_cov3d(grad_color, fwd, means3D, colors, opacities, cov3D, viewmatr
                opacities=torch.empty(P, 1, device=dev), cov3D=torch.empty(P, 6, device=dev))
     m2d = torch.empty(V, P, 3, device=dev) if want_means2D else None
     if P:
-        L = _lib.lib()
-        with _lib.on_device(dev):
-            ws = _lib.workspace.get(dev, L.ocrf_rasterize_backward_workspace_bytes(P, V), 'raster')
-            _lib.check(L.ocrf_rasterize_backward_cov3d(
-                P, V, H, W, _lib.ptr(means3D), _lib.ptr(colors), _lib.ptr(opac), _lib.ptr(cov), _lib.ptr(cams),
-                _lib.ptr(bg), _lib.ptr(fc), _lib.ptr(ft), _lib.ptr(fn), _lib.ptr(g), _lib.ptr(out['means3D']),
-                _lib.ptr(out['colors']), _lib.ptr(out['opacities']), _lib.ptr(out['cov3D']), _lib.ptr(m2d),
-                _lib.ptr(ws), ctypes.c_size_t(ws.numel()), _lib.stream_ptr(dev)), 'ocrf_rasterize_backward_cov3d')
+        ws = _lib.workspace.get(dev, _lib.lib().ocrf_rasterize_backward_workspace_bytes(P, V), 'raster')
+        _lib.launch('ocrf_rasterize_backward_cov3d', dev, P, V, H, W, means3D, colors, opac, cov, cams, bg, fc, ft, fn, g,
+                    out['means3D'], out['colors'], out['opacities'], out['cov3D'], m2d, ws, ws.numel())
     if m2d is not None:
         out['means2D'] = m2d
     return out

@@ -19,8 +19,6 @@ channel mean/max + 7x7 conv + sigmoid + gate for HOA-3, global max + quarter MLP
 deformable attention stay PyTorch-ROCm ops (plumbing; SURVEY.md 8a rows a24-a25 note they are
 ~40 tiny launches, not custom-kernel targets of the reference either).  GPU tensors only.
 """
-import ctypes
-
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -83,12 +81,8 @@ class HeightAttention(nn.Module):
         w1, w2 = self._packed()
         gate = torch.empty(B, C, device=x.device)
         gated = torch.empty_like(x) if want_gated else None
-        L = _lib.lib()
-        with _lib.on_device(x.device):
-            ws = _lib.workspace.get(x.device, L.ocrf_hoa_height_attention_workspace_bytes(B, C), 'hoa')
-            _lib.check(L.ocrf_hoa_height_attention(
-                _lib.ptr(x), B, C, self.hid, Y, X, _lib.ptr(w1), _lib.ptr(w2), _lib.ptr(gate), _lib.ptr(gated),
-                _lib.ptr(ws), ctypes.c_size_t(ws.numel()), _lib.stream_ptr(x.device)), 'ocrf_hoa_height_attention')
+        ws = _lib.workspace.get(x.device, _lib.lib().ocrf_hoa_height_attention_workspace_bytes(B, C), 'hoa')
+        _lib.launch('ocrf_hoa_height_attention', x.device, x, B, C, self.hid, Y, X, w1, w2, gate, gated, ws, ws.numel())
         return gate.view(B, C, 1, 1), gated
 
     def _needs_grad(self, x):
@@ -133,9 +127,7 @@ class HeightAttention(nn.Module):
 def _dw3x3(x, w9, bias):
     B, C, Y, X = x.shape
     y = torch.empty_like(x)
-    with _lib.on_device(x.device):
-        _lib.check(_lib.lib().ocrf_hoa_dw3x3(_lib.ptr(x), _lib.ptr(w9), _lib.ptr(bias), B, C, Y, X, _lib.ptr(y),
-                                             _lib.stream_ptr(x.device)), 'ocrf_hoa_dw3x3')
+    _lib.launch('ocrf_hoa_dw3x3', x.device, x, w9, bias, B, C, Y, X, y)
     return y
 
 
@@ -165,12 +157,8 @@ class _DepthwiseConv3x3(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             gx = _dw3x3(gy, _f32c(weight.detach().flip(2, 3)).reshape(C, 9), None)
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            L = _lib.lib()
-            nb = L.ocrf_hoa_dw3x3_wgrad_bands(Y)
-            partial = torch.empty(B, C, nb, 10, device=x.device)
-            with _lib.on_device(x.device):
-                _lib.check(L.ocrf_hoa_dw3x3_wgrad(_lib.ptr(x), _lib.ptr(gy), B, C, Y, X, _lib.ptr(partial),
-                                                  _lib.stream_ptr(x.device)), 'ocrf_hoa_dw3x3_wgrad')
+            partial = torch.empty(B, C, _lib.lib().ocrf_hoa_dw3x3_wgrad_bands(Y), 10, device=x.device)
+            _lib.launch('ocrf_hoa_dw3x3_wgrad', x.device, x, gy, B, C, Y, X, partial)
             sums = partial.sum((0, 2))                                   # (C, 10)
             gw = sums[:, :9].reshape(C, 1, 3, 3).to(weight.dtype)
             gb = sums[:, 9] if ctx.has_bias else None
@@ -353,15 +341,11 @@ class OpacityVoxelToBEVConverter(nn.Module):
         x, position = _f32c(x), _f32c(position)
         B, _, H, W = x.shape
         dev = x.device
-        L = _lib.lib()
         if self._is_reference_architecture() and H % 4 == 0 and W % 4 == 0:
             w = self._packed_v2b()
             out = torch.empty(B, 1, H, W, device=dev)
-            with _lib.on_device(dev):
-                ws = _lib.workspace.get(dev, L.ocrf_hoa_v2b_workspace_bytes(B, H, W), 'hoa_v2b')
-                _lib.check(L.ocrf_hoa_v2b_forward(_lib.ptr(x), _lib.ptr(position), _lib.ptr(w), B, H, W, _lib.ptr(ws),
-                                                  ctypes.c_size_t(ws.numel()), _lib.ptr(out), _lib.stream_ptr(dev)),
-                           'ocrf_hoa_v2b_forward')
+            ws = _lib.workspace.get(dev, _lib.lib().ocrf_hoa_v2b_workspace_bytes(B, H, W), 'hoa_v2b')
+            _lib.launch('ocrf_hoa_v2b_forward', dev, x, position, w, B, H, W, ws, ws.numel(), out)
             return out
         return self._forward_blocks(x, position)
 
@@ -369,21 +353,18 @@ class OpacityVoxelToBEVConverter(nn.Module):
         """Any other channel configuration: block by block (5 block kernels + 5 gate kernels + the output conv)."""
         B, _, H, W = x.shape
         dev = x.device
-        L = _lib.lib()
         plan = self._plan(B, H, W, dev)
         out = torch.empty(B, 1, H, W, device=dev)
-        with _lib.on_device(dev):
-            st = _lib.stream_ptr(dev)
-            for call in plan['calls']:
-                if call[0] == 'block':
-                    args = call[1]
-                    if call[2]:                   # the first block reads the caller's tensors
-                        args = list(args)
-                        args[0], args[17] = _lib.ptr(x), _lib.ptr(position)
-                    _lib.check(L.ocrf_hoa_unet_block(*args, st), 'ocrf_hoa_unet_block')
-                else:
-                    _lib.check(L.ocrf_hoa_height_gate_from_tiles(*call[1], st), 'ocrf_hoa_height_gate_from_tiles')
-            _lib.check(L.ocrf_hoa_gated_conv1x1(*plan['out_args'], _lib.ptr(out), st), 'ocrf_hoa_gated_conv1x1')
+        for call in plan['calls']:
+            if call[0] == 'block':
+                args = call[1]
+                if call[2]:                   # the first block reads the caller's tensors
+                    args = list(args)
+                    args[0], args[17] = _lib.ptr(x), _lib.ptr(position)
+                _lib.launch('ocrf_hoa_unet_block', dev, *args)
+            else:
+                _lib.launch('ocrf_hoa_height_gate_from_tiles', dev, *call[1])
+        _lib.launch('ocrf_hoa_gated_conv1x1', dev, *plan['out_args'], out)
         return out
 
 
@@ -394,9 +375,7 @@ def channel_stats(x):
     B, C, Y, X = x.shape
     x = _f32c(x)
     stats = torch.empty(B, 2, Y, X, device=x.device)
-    with _lib.on_device(x.device):
-        _lib.check(_lib.lib().ocrf_hoa_channel_stats(_lib.ptr(x), B, C, Y, X, _lib.ptr(stats), _lib.stream_ptr(x.device)),
-                   'ocrf_hoa_channel_stats')
+    _lib.launch('ocrf_hoa_channel_stats', x.device, x, B, C, Y, X, stats)
     return stats
 
 
@@ -419,15 +398,10 @@ def spatial_gate(weight, x, addend, want_gated, stats=None, in_place=False):
         raise _lib.OcrfHipError('stats must be the contiguous fp32 (B,2,Y,X) result of channel_stats(x)')
     mask = torch.empty(B, 1, Y, X, device=x.device)
     gated = (x if in_place else torch.empty_like(x)) if want_gated else None
-    L = _lib.lib()
-    with _lib.on_device(x.device):
-        st = _lib.stream_ptr(x.device)
-        if stats is None:
-            stats = torch.empty(B, 2, Y, X, device=x.device)
-            _lib.check(L.ocrf_hoa_channel_stats(_lib.ptr(x), B, C, Y, X, _lib.ptr(stats), st), 'ocrf_hoa_channel_stats')
-        _lib.check(L.ocrf_hoa_opacity_mask_gate(_lib.ptr(x), _lib.ptr(stats), _lib.ptr(ob), _lib.ptr(w), k, B, C,
-                                                Y, X, _lib.ptr(mask), _lib.ptr(gated), st),
-                   'ocrf_hoa_opacity_mask_gate')
+    if stats is None:
+        stats = torch.empty(B, 2, Y, X, device=x.device)
+        _lib.launch('ocrf_hoa_channel_stats', x.device, x, B, C, Y, X, stats)
+    _lib.launch('ocrf_hoa_opacity_mask_gate', x.device, x, stats, ob, w, k, B, C, Y, X, mask, gated)
     return mask, gated
 
 
@@ -590,15 +564,11 @@ def hoa1(defor_cross_attention, opacity, alpha_lidar, heights, Y, X):
         _lib.require_cuda(o, alpha_lidar)
         o32, a32 = _f32c(o), _f32c(alpha_lidar)
         B = o32.shape[0]
-        L = _lib.lib()
         w = _hoa1_packed(m)
-        assert w.numel() == L.ocrf_hoa1_weights_len()
+        assert w.numel() == _lib.lib().ocrf_hoa1_weights_len()
         att = torch.empty(B * ((heights + 8) * (Y // 6) * (X // 6) + 18 * 128), device=o.device)   # att | q | kv
         out = torch.empty_like(o32)
-        with _lib.on_device(o.device):
-            _lib.check(L.ocrf_hoa1_forward(_lib.ptr(o32), _lib.ptr(a32), _lib.ptr(w), B, Y, X,
-                                           ctypes.c_float(float(m.to_offsets[4].scale)), _lib.ptr(att), _lib.ptr(out),
-                                           _lib.stream_ptr(o.device)), 'ocrf_hoa1_forward')
+        _lib.launch('ocrf_hoa1_forward', o.device, o32, a32, w, B, Y, X, float(m.to_offsets[4].scale), att, out)
         return out
     size = (int(Y / 6), int(X / 6))
     o_up = F.interpolate(o, size=size, mode='bilinear', align_corners=True)

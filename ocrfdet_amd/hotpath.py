@@ -340,8 +340,7 @@ class HotPath:
 
     def _set_busy(self, value):
         if self._use_busy():
-            _lib.check(_lib.lib().ocrf_stream_write_value32(_lib.ptr(self._busy), int(value), _lib.stream_ptr(self.device)),
-                       'ocrf_stream_write_value32')
+            _lib.launch('ocrf_stream_write_value32', self.device, self._busy, int(value))
 
     def _render_planned(self, entry, phase='both', out=None):
         plan, f0, nf, g = entry
@@ -1075,8 +1074,7 @@ class ShardedHotPath:
 
     def _set_busy(self, value):
         if self._busy is not None:
-            _lib.check(_lib.lib().ocrf_stream_write_value32(_lib.ptr(self._busy), int(value), _lib.stream_ptr(self.device)),
-                       'ocrf_stream_write_value32')
+            _lib.launch('ocrf_stream_write_value32', self.device, self._busy, int(value))
 
     @property
     def bev_voxels_per_step(self):

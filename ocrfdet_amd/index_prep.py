@@ -25,7 +25,6 @@ preparations as fused device kernels (csrc/index_prep.hip, C ABI ``ocrf_lss_prep
 sort at all (HT), intervals — a dozen launches instead of ~40 torch passes and two argsorts, with
 identical outputs (tests/test_index_prep_gpu.py).
 """
-import ctypes
 
 import torch
 
@@ -290,14 +289,9 @@ def voxel_pooling_prepare_v2_hip(frustum, cam_block, B, N, grid_lower_bound, gri
     interval = _host_floats(grid_interval.detach().float().cpu().tolist())
     n_pts = B * N * D * H * W
     bufs = (buffers if buffers is not None else _RankBuffers()).get(dev, n_pts, min(n_pts, B * gz * gy * gx))
-    L = _lib.lib()
-    with _lib.on_device(dev):
-        need = L.ocrf_lss_prepare_workspace_bytes(B, N, D, H, W, gx, gy, gz)
-        ws = _lib.workspace.get(dev, need, _prep_tag(dev))
-        _lib.check(L.ocrf_lss_prepare(
-            B, N, D, H, W, _lib.ptr(frustum.contiguous()), _lib.ptr(cam_block), ctypes.c_void_p(lower.data_ptr()),
-            ctypes.c_void_p(interval.data_ptr()), gx, gy, gz, *[_lib.ptr(b) for b in bufs], _lib.ptr(ws),
-            ctypes.c_size_t(ws.numel()), _lib.stream_ptr(dev)), 'ocrf_lss_prepare')
+    ws = _lib.workspace.get(dev, _lib.lib().ocrf_lss_prepare_workspace_bytes(B, N, D, H, W, gx, gy, gz), _prep_tag(dev))
+    _lib.launch('ocrf_lss_prepare', dev, B, N, D, H, W, frustum.contiguous(), cam_block, lower, interval, gx, gy, gz, *bufs,
+                ws, ws.numel())
     if not sync:
         return bufs[:5], bufs[5]
     return _trim(bufs, bufs[5].cpu())
@@ -316,15 +310,10 @@ def fast_sample_prepare_hip(ref_template, cam_block, B, N, pc_range, image_shape
     pc = _host_floats(pc_range)
     n_pts = B * N * Z * Nq
     bufs = (buffers if buffers is not None else _RankBuffers()).get(dev, n_pts, B * Nq)
-    L = _lib.lib()
-    with _lib.on_device(dev):
-        need = L.ocrf_ht_prepare_workspace_bytes(B, Nq)
-        ws = _lib.workspace.get(dev, need, _prep_tag(dev))
-        _lib.check(L.ocrf_ht_prepare(
-            B, N, Z, Nq, int(W), int(H), int(D), _lib.ptr(ref_template.contiguous()), _lib.ptr(cam_block),
-            ctypes.c_void_p(pc.data_ptr()), ctypes.c_float(image_shapes[1]), ctypes.c_float(image_shapes[0]),
-            ctypes.c_float(depth_range[0]), ctypes.c_float(depth_range[1]), *[_lib.ptr(b) for b in bufs], _lib.ptr(ws),
-            ctypes.c_size_t(ws.numel()), _lib.stream_ptr(dev)), 'ocrf_ht_prepare')
+    ws = _lib.workspace.get(dev, _lib.lib().ocrf_ht_prepare_workspace_bytes(B, Nq), _prep_tag(dev))
+    _lib.launch('ocrf_ht_prepare', dev, B, N, Z, Nq, int(W), int(H), int(D), ref_template.contiguous(), cam_block, pc,
+                float(image_shapes[1]), float(image_shapes[0]), float(depth_range[0]), float(depth_range[1]), *bufs,
+                ws, ws.numel())
     if not sync:
         return bufs[:5], bufs[5]
     return _trim(bufs, bufs[5].cpu())
@@ -344,11 +333,8 @@ def geometry_blocks_hip(rots, trans, intrins, post_rots, post_trans, bda, c2w, i
     lss = torch.empty(B * N, 33, device=dev)
     ht = torch.empty(B * N, 24, device=dev)
     cam = torch.empty(B, N, 36, device=dev) if c2w_d is not None else None
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().ocrf_geometry_blocks(
-            B, N, *[_lib.ptr(t) for t in ts], _lib.ptr(c2w_d), int(image_shapes[0]), int(image_shapes[1]),
-            ctypes.c_float(znear), ctypes.c_float(zfar), _lib.ptr(lss), _lib.ptr(ht), _lib.ptr(cam),
-            _lib.stream_ptr(dev)), 'ocrf_geometry_blocks')
+    _lib.launch('ocrf_geometry_blocks', dev, B, N, *ts, c2w_d, int(image_shapes[0]), int(image_shapes[1]), float(znear),
+                float(zfar), lss, ht, cam)
     return lss, ht, cam
 
 
@@ -363,10 +349,6 @@ def ht_project_hip(ref_template, cam_block, B, N, pc_range, image_shapes, depth_
     pix = torch.empty(B, N, Z, Nq, 2, device=dev)
     mask = torch.empty(B, N, Z, Nq, dtype=torch.bool, device=dev)
     voxel = torch.empty(B, Z, Nq, 3, device=dev)
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().ocrf_ht_project(
-            B, N, Z, Nq, _lib.ptr(ref_template.contiguous()), _lib.ptr(cam_block), ctypes.c_void_p(pc.data_ptr()),
-            ctypes.c_float(image_shapes[1]), ctypes.c_float(image_shapes[0]), ctypes.c_float(depth_range[0]),
-            ctypes.c_float(depth_range[1]), _lib.ptr(pix), _lib.ptr(mask), _lib.ptr(voxel), _lib.stream_ptr(dev)),
-            'ocrf_ht_project')
+    _lib.launch('ocrf_ht_project', dev, B, N, Z, Nq, ref_template.contiguous(), cam_block, pc, float(image_shapes[1]),
+                float(image_shapes[0]), float(depth_range[0]), float(depth_range[1]), pix, mask, voxel)
     return pix, mask, voxel

@@ -84,10 +84,7 @@ def depth_labels(gt_depth, gt_semantic, depth_cfg, D, ds):
     labels = torch.empty(R, D, device=gd.device)
     sem = torch.empty(R, 2, device=gd.device)
     d0, d1, step = (float(v) for v in depth_cfg[:3])
-    with _lib.on_device(gd.device):
-        _lib.check(_lib.lib().ocrf_depth_labels(B * N, H, W, ds, D, d0, d1, step, _lib.ptr(gd), _lib.ptr(gs),
-                                                _lib.ptr(labels), _lib.ptr(sem), _lib.stream_ptr(gd.device)),
-                   'ocrf_depth_labels')
+    _lib.launch('ocrf_depth_labels', gd.device, B * N, H, W, ds, D, d0, d1, step, gd, gs, labels, sem)
     return labels, sem
 
 
@@ -123,14 +120,9 @@ class DepthSemanticLoss(torch.autograd.Function):
         d, s = depth.detach().contiguous(), semantic.detach().contiguous()
         out = torch.empty(2, device=dev)
         denoms = torch.empty(2, device=dev)
-        L = _lib.lib()
-        nbytes = L.ocrf_depth_semantic_loss_workspace_bytes(BN * h * w)
-        ws = _lib.workspace.get(dev, nbytes, 'losses_ds')
-        with _lib.on_device(dev):
-            _lib.check(L.ocrf_depth_semantic_loss(BN, h * w, D, _lib.ptr(dl), _lib.ptr(sl), _lib.ptr(d), _lib.ptr(s),
-                                                  float(w_depth), float(w_semantic), _lib.ptr(out), _lib.ptr(denoms),
-                                                  _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)),
-                       'ocrf_depth_semantic_loss')
+        ws = _lib.workspace.get(dev, _lib.lib().ocrf_depth_semantic_loss_workspace_bytes(BN * h * w), 'losses_ds')
+        _lib.launch('ocrf_depth_semantic_loss', dev, BN, h * w, D, dl, sl, d, s, float(w_depth), float(w_semantic), out,
+                    denoms, ws, ws.numel())
         ctx.save_for_backward(d, s, dl, sl, denoms)
         ctx.weights = (float(w_depth), float(w_semantic))
         return out[0], out[1]
@@ -142,10 +134,7 @@ class DepthSemanticLoss(torch.autograd.Function):
         dev = d.device
         go = torch.stack((g_depth.reshape(()), g_sem.reshape(()))).float().contiguous()
         gd, gs = torch.empty_like(d), torch.empty_like(s)
-        with _lib.on_device(dev):
-            _lib.check(_lib.lib().ocrf_depth_semantic_loss_backward(
-                BN, h * w, D, _lib.ptr(dl), _lib.ptr(sl), _lib.ptr(d), _lib.ptr(s), *ctx.weights, _lib.ptr(denoms),
-                _lib.ptr(go), _lib.ptr(gd), _lib.ptr(gs), _lib.stream_ptr(dev)), 'ocrf_depth_semantic_loss_backward')
+        _lib.launch('ocrf_depth_semantic_loss_backward', dev, BN, h * w, D, dl, sl, d, s, *ctx.weights, denoms, go, gd, gs)
         return gd, gs, None, None, None, None
 
 
@@ -324,15 +313,11 @@ class RenderLosses(torch.autograd.Function):
         out = torch.empty(3, device=dev)
         saved = torch.empty(B * C * K * 3 * H * W, device=dev)
         stats = torch.empty(2 * B, device=dev)
-        L = _lib.lib()
-        ws = _lib.workspace.get(dev, L.ocrf_render_losses_workspace_bytes(B, C, H, W), 'losses_render')
+        ws = _lib.workspace.get(dev, _lib.lib().ocrf_render_losses_workspace_bytes(B, C, H, W), 'losses_render')
         n_cams = gd.shape[1] if has_depth else 0
-        args = [B, K, C, H, W, _lib.ptr(gt)] + [_lib.ptr(t) for t in rs] + [_lib.ptr(boxes), _lib.ptr(meta), n_max,
-                                                                              int(use_mask), _lib.ptr(gd), n_cams]
-        args += [_lib.ptr(t) for t in rds] + [float(depth_range[0]), float(depth_range[1])] + [float(w) for w in weights]
-        with _lib.on_device(dev):
-            _lib.check(L.ocrf_render_losses(*args, _lib.ptr(out), _lib.ptr(saved), _lib.ptr(stats), _lib.ptr(ws),
-                                            ws.numel(), _lib.stream_ptr(dev)), 'ocrf_render_losses')
+        args = [B, K, C, H, W, gt, *rs, boxes, meta, n_max, int(use_mask), gd, n_cams, *rds,
+                float(depth_range[0]), float(depth_range[1])] + [float(w) for w in weights]
+        _lib.launch('ocrf_render_losses', dev, *args, out, saved, stats, ws, ws.numel())
         keep = [gt, boxes, meta, gd, saved, stats] + rs + rds
         ctx.save_for_backward(*[t if t is not None else torch.empty(0) for t in keep])
         ctx.present = [t is not None for t in keep]
@@ -351,13 +336,9 @@ class RenderLosses(torch.autograd.Function):
         grads = [torch.empty_like(r) if (r is not None and need) else None for r, need in zip(rs, ctx.need[:3])]
         dgrads = [torch.empty_like(r) if (r is not None and need and gd is not None) else None
                   for r, need in zip(rds, ctx.need[3:])]
-        args = [B, K, C, H, W, _lib.ptr(gt)] + [_lib.ptr(t) for t in rs] + [_lib.ptr(boxes), _lib.ptr(meta), n_max,
-                                                                              use_mask, _lib.ptr(gd), n_cams]
-        args += [_lib.ptr(t) for t in rds] + [float(depth_range[0]), float(depth_range[1])] + [float(w) for w in weights]
-        with _lib.on_device(dev):
-            _lib.check(_lib.lib().ocrf_render_losses_backward(
-                *args, _lib.ptr(saved), _lib.ptr(stats), _lib.ptr(go), *[_lib.ptr(g) for g in grads],
-                *[_lib.ptr(g) for g in dgrads], _lib.stream_ptr(dev)), 'ocrf_render_losses_backward')
+        args = [B, K, C, H, W, gt, *rs, boxes, meta, n_max, use_mask, gd, n_cams, *rds,
+                float(depth_range[0]), float(depth_range[1])] + [float(w) for w in weights]
+        _lib.launch('ocrf_render_losses_backward', dev, *args, saved, stats, go, *grads, *dgrads)
         return (None, *grads, *dgrads) + (None,) * 9
 
 

@@ -6,7 +6,6 @@ current stream and raises ``OcrfHipError`` on CPU tensors — there is no fallba
 ``compose_*`` helpers turn the reference's ``state_dict`` layout into the flat parameter blocks the
 kernels read; they are pure torch and run anywhere.
 """
-import ctypes
 
 import torch
 import torch.nn.functional as F
@@ -41,10 +40,8 @@ def prefilter(x, D, C, depth_threshold, semantic_threshold):
     fdepth = torch.empty_like(depth)
     sem = torch.empty(BN, 2, H, W, device=dev)
     feat = torch.empty(BN, H, W, C, device=dev)
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().ocrf_prefilter(_lib.ptr(x), BN, D, C, H * W, ctypes.c_float(depth_threshold),
-                                             ctypes.c_float(semantic_threshold), _lib.ptr(depth), _lib.ptr(fdepth),
-                                             _lib.ptr(sem), _lib.ptr(feat), _lib.stream_ptr(dev)), 'ocrf_prefilter')
+    _lib.launch('ocrf_prefilter', dev, x, BN, D, C, H * W, float(depth_threshold), float(semantic_threshold), depth,
+                fdepth, sem, feat)
     return depth, fdepth, sem, feat
 
 
@@ -70,10 +67,7 @@ def pillar_sample_mean(imgs, pix, mask, view_hw=None):
     imgs, pix = _f32c(imgs), _f32c(pix)
     m = _mask_bytes(mask, (B, N, Zh * Q))
     avg = torch.empty(B, Zh, Q, C, device=imgs.device)
-    with _lib.on_device(imgs.device):
-        _lib.check(_lib.lib().ocrf_pillar_sample_mean(_lib.ptr(imgs), _lib.ptr(pix), _lib.ptr(m), _lib.ptr(avg), B, N, C,
-                                                      H, W, Zh * Q, _lib.stream_ptr(imgs.device)),
-                   'ocrf_pillar_sample_mean')
+    _lib.launch('ocrf_pillar_sample_mean', imgs.device, imgs, pix, m, avg, B, N, C, H, W, Zh * Q)
     return avg
 
 
@@ -95,10 +89,7 @@ def retain_valid_pixels(image_matrix, pseudo_point_cloud, mask, cam_sel=None):
         out = torch.empty(B, C, H, W, device=dev)
     else:
         out = torch.empty(B, N, C, H, W, device=dev)
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().ocrf_retain_valid_pixels(_lib.ptr(imgs), _lib.ptr(pix), _lib.ptr(m), _lib.ptr(cam_sel),
-                                                       _lib.ptr(out), B, N, C, H, W, ZQ, _lib.stream_ptr(dev)),
-                   'ocrf_retain_valid_pixels')
+    _lib.launch('ocrf_retain_valid_pixels', dev, imgs, pix, m, cam_sel, out, B, N, C, H, W, ZQ)
     return out
 
 
@@ -128,17 +119,13 @@ def gauss_heads(bev, rgb_avg, params, num_height):
     _lib.require_cuda(bev, rgb_avg, params)
     B, C, Y, X = bev.shape
     bev, rgb_avg = _f32c(bev), _f32c(rgb_avg)
-    L = _lib.lib()
-    if params.numel() != L.ocrf_gauss_heads_params_len(C, num_height):
+    if params.numel() != _lib.lib().ocrf_gauss_heads_params_len(C, num_height):
         raise ValueError('gauss_heads: parameter block does not match (C, num_height)')
     P = num_height * Y * X
     dev = bev.device
     op, sc = torch.empty(B, P, 1, device=dev), torch.empty(B, P, 3, device=dev)
     rot, col = torch.empty(B, P, 4, device=dev), torch.empty(B, P, 3, device=dev)
-    with _lib.on_device(dev):
-        _lib.check(L.ocrf_gauss_heads(_lib.ptr(bev), _lib.ptr(rgb_avg), _lib.ptr(params), B, C, num_height, Y * X,
-                                      _lib.ptr(op), _lib.ptr(sc), _lib.ptr(rot), _lib.ptr(col), _lib.stream_ptr(dev)),
-                   'ocrf_gauss_heads')
+    _lib.launch('ocrf_gauss_heads', dev, bev, rgb_avg, params, B, C, num_height, Y * X, op, sc, rot, col)
     return op, sc, rot, col
 
 
@@ -225,11 +212,8 @@ def gauss_heads_backward(bev, rgb_avg, params, num_height, g_opacity=None, g_sca
         raise ValueError(f'gauss_heads_backward: num_height {num_height} has no register tile')
     scratch = _lib.workspace.get(dev, need, 'gauss_heads_backward')
     d_bev, d_params = torch.empty_like(bev), torch.empty_like(params)
-    with _lib.on_device(dev):
-        _lib.check(L.ocrf_gauss_heads_backward(
-            _lib.ptr(bev), _lib.ptr(rgb_avg), _lib.ptr(params), B, C, num_height, Y * X,
-            *[_lib.ptr(g) if g is not None else None for g in grads], _lib.ptr(d_bev), _lib.ptr(d_params),
-            _lib.ptr(scratch), scratch.numel(), _lib.stream_ptr(dev)), 'ocrf_gauss_heads_backward')
+    _lib.launch('ocrf_gauss_heads_backward', dev, bev, rgb_avg, params, B, C, num_height, Y * X, *grads, d_bev, d_params,
+                scratch, scratch.numel())
     return d_bev, d_params
 
 
@@ -314,9 +298,7 @@ def nerf_alpha(z, w_sigma, c_sigma):
     if ci != 32 or w_sigma.numel() != 32 * 64 or c_sigma.numel() != 64:
         raise ValueError('nerf_alpha: z must have 32 channels and the maps 32x64 / 64 entries')
     alpha = torch.empty(M, 8 * h2, 8 * w2, device=z.device)
-    with _lib.on_device(z.device):
-        _lib.check(_lib.lib().ocrf_nerf_alpha(_lib.ptr(z), _lib.ptr(w_sigma), _lib.ptr(c_sigma), _lib.ptr(alpha), M,
-                                              h2, w2, _lib.stream_ptr(z.device)), 'ocrf_nerf_alpha')
+    _lib.launch('ocrf_nerf_alpha', z.device, z, w_sigma, c_sigma, alpha, M, h2, w2)
     return alpha
 
 
@@ -328,16 +310,12 @@ def nerf_render(z, cam_sel, alpha, sparse_rgb, params, n_cams):
     z, alpha, sparse_rgb = _f32c(z), _f32c(alpha), _f32c(sparse_rgb)
     M, _, h2, w2 = z.shape
     B = M // n_cams
-    L = _lib.lib()
-    if params.numel() != L.ocrf_nerf_render_params_len() or tuple(sparse_rgb.shape) != (B, 3, 8 * h2, 8 * w2):
+    if params.numel() != _lib.lib().ocrf_nerf_render_params_len() or tuple(sparse_rgb.shape) != (B, 3, 8 * h2, 8 * w2):
         raise ValueError('nerf_render: parameter block or sparse_rgb shape mismatch')
     cam_sel = cam_sel.to(torch.int32).contiguous()
     img = torch.empty(B, 3, 8 * h2, 8 * w2, device=z.device)
     dep = torch.empty(B, 1, 8 * h2, 8 * w2, device=z.device)
-    with _lib.on_device(z.device):
-        _lib.check(L.ocrf_nerf_render(_lib.ptr(z), _lib.ptr(cam_sel), _lib.ptr(alpha), _lib.ptr(sparse_rgb),
-                                      _lib.ptr(params), B, n_cams, h2, w2, _lib.ptr(img), _lib.ptr(dep),
-                                      _lib.stream_ptr(z.device)), 'ocrf_nerf_render')
+    _lib.launch('ocrf_nerf_render', z.device, z, cam_sel, alpha, sparse_rgb, params, B, n_cams, h2, w2, img, dep)
     return img, dep
 
 
@@ -378,19 +356,13 @@ def dual_feat_fusion(x1, x2, params, global_vec, hidden, addend=None):
     if params.numel() != 2 * C * hidden + hidden + C * hidden + C:
         raise ValueError('dual_feat_fusion: parameter block does not match (C, hidden)')
     out = torch.empty_like(x1)
-    with _lib.on_device(x1.device):
-        if addend is not None:
-            if tuple(addend.shape) != tuple(x1.shape):
-                raise ValueError('dual_feat_fusion: addend must have the shape of the inputs')
-            add, plus = _f32c(addend), torch.empty_like(x1)
-            _lib.check(_lib.lib().ocrf_dual_feat_fusion_plus(_lib.ptr(x1), _lib.ptr(x2), _lib.ptr(params), _lib.ptr(gv),
-                                                             _lib.ptr(out), _lib.ptr(add), _lib.ptr(plus), B, C, hidden,
-                                                             Y * X, _lib.stream_ptr(x1.device)),
-                       'ocrf_dual_feat_fusion_plus')
-            return out, plus
-        _lib.check(_lib.lib().ocrf_dual_feat_fusion(_lib.ptr(x1), _lib.ptr(x2), _lib.ptr(params), _lib.ptr(gv),
-                                                    _lib.ptr(out), B, C, hidden, Y * X, _lib.stream_ptr(x1.device)),
-                   'ocrf_dual_feat_fusion')
+    if addend is not None:
+        if tuple(addend.shape) != tuple(x1.shape):
+            raise ValueError('dual_feat_fusion: addend must have the shape of the inputs')
+        add, plus = _f32c(addend), torch.empty_like(x1)
+        _lib.launch('ocrf_dual_feat_fusion_plus', x1.device, x1, x2, params, gv, out, add, plus, B, C, hidden, Y * X)
+        return out, plus
+    _lib.launch('ocrf_dual_feat_fusion', x1.device, x1, x2, params, gv, out, B, C, hidden, Y * X)
     return out
 
 
@@ -409,10 +381,8 @@ def plane_bias_act_stats(y, bias=None, relu=False, write=True, stats=None, c_off
     B, C, Y, X = y.shape
     psum, pmax = stats if stats is not None else (None, None)
     out_C, S = (psum.shape[1], psum.shape[2]) if psum is not None else (C, _SPLITS)
-    with _lib.on_device(y.device):
-        _lib.check(_lib.lib().ocrf_plane_bias_act_stats(_lib.ptr(y), _lib.ptr(bias), B, C, Y * X, int(relu), int(write),
-                                                        S, out_C, c_off, _lib.ptr(psum), _lib.ptr(pmax),
-                                                        _lib.stream_ptr(y.device)), 'ocrf_plane_bias_act_stats')
+    _lib.launch('ocrf_plane_bias_act_stats', y.device, y, bias, B, C, Y * X, int(relu), int(write), S, out_C, c_off, psum,
+                pmax)
     return y
 
 
@@ -423,11 +393,8 @@ def channel_mlp(psum, pmax, inv_n, w1, b1, w2, b2, use_max, sigmoid):
     B, K, S = psum.shape
     M, N = w1.shape[0], w2.shape[0]
     out = torch.empty(B, N, device=psum.device)
-    with _lib.on_device(psum.device):
-        _lib.check(_lib.lib().ocrf_channel_mlp(_lib.ptr(psum), _lib.ptr(pmax), B, K, S, ctypes.c_float(inv_n),
-                                               _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2), _lib.ptr(b2), M, N,
-                                               int(use_max), int(sigmoid), _lib.ptr(out),
-                                               _lib.stream_ptr(psum.device)), 'ocrf_channel_mlp')
+    _lib.launch('ocrf_channel_mlp', psum.device, psum, pmax, B, K, S, float(inv_n), w1, b1, w2, b2, M, N, int(use_max),
+                int(sigmoid), out)
     return out
 
 
@@ -436,9 +403,7 @@ def scaled_channel_stats(x, scale):
     _lib.require_cuda(x, scale)
     B, C, Y, X = x.shape
     stats = torch.empty(B, 2, Y, X, device=x.device)
-    with _lib.on_device(x.device):
-        _lib.check(_lib.lib().ocrf_scaled_channel_stats(_lib.ptr(x), _lib.ptr(scale), B, C, Y * X, _lib.ptr(stats),
-                                                        _lib.stream_ptr(x.device)), 'ocrf_scaled_channel_stats')
+    _lib.launch('ocrf_scaled_channel_stats', x.device, x, scale, B, C, Y * X, stats)
     return stats
 
 
@@ -449,11 +414,7 @@ def cbam_tail(y, scale, stats, sa_weight, res, wm, bm, want_block_out=False):
     k = sa_weight.shape[-1]
     logit = torch.empty(B, 1, Y, X, device=y.device)
     block = torch.empty_like(y) if want_block_out else None
-    with _lib.on_device(y.device):
-        _lib.check(_lib.lib().ocrf_cbam_tail(_lib.ptr(y), _lib.ptr(scale), _lib.ptr(stats), _lib.ptr(sa_weight), k,
-                                             _lib.ptr(res), _lib.ptr(wm), ctypes.c_float(bm), B, C, Y, X,
-                                             _lib.ptr(logit), _lib.ptr(block), _lib.stream_ptr(y.device)),
-                   'ocrf_cbam_tail')
+    _lib.launch('ocrf_cbam_tail', y.device, y, scale, stats, sa_weight, k, res, wm, float(bm), B, C, Y, X, logit, block)
     return (logit, block) if want_block_out else logit
 
 
@@ -474,9 +435,8 @@ def global_att_vector(x1, x2, packed):
     x1, x2 = _f32c(x1), _f32c(x2)
     psum = torch.empty(B, 2 * C, _SPLITS, device=x1.device)
     pmax = torch.empty_like(psum)
-    with _lib.on_device(x1.device):          # both inputs in ONE launch (no cat: the kernel reads the second tensor itself)
-        _lib.check(_lib.lib().ocrf_plane_stats_pair(_lib.ptr(x1), _lib.ptr(x2), B, C, C, Y * X, _SPLITS, _lib.ptr(psum),
-                                                    _lib.ptr(pmax), _lib.stream_ptr(x1.device)), 'ocrf_plane_stats_pair')
+    # both inputs in ONE launch (no cat: the kernel reads the second tensor itself)
+    _lib.launch('ocrf_plane_stats_pair', x1.device, x1, x2, B, C, C, Y * X, _SPLITS, psum, pmax)
     w1, b1, w2, b2 = packed
     return channel_mlp(psum, None, 1.0 / (Y * X), w1, b1, w2, b2, use_max=False, sigmoid=False)
 

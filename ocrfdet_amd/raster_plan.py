@@ -13,7 +13,6 @@ the parameters do, graph-capturable); ``guard='host'`` only raises status bit 4,
 exception — the caller decides when to pay that synchronisation.  A plan is also keyed by its cameras on the device:
 a call that passes the cameras it means (``render(cameras=...)``) is checked against the plan's there.
 """
-import ctypes
 
 import torch
 
@@ -71,11 +70,10 @@ class RasterPlan:
             capacity = int(sum(self.kept) * float(headroom)) + 1024
         self.capacity = max(1, min(int(capacity), self.P * self.V))
         self.total_kept = self.capacity        # (name kept for the tools: strides and scratch sizes follow the capacity)
-        with _lib.on_device(dev):
-            self._build_ws = torch.empty(int(L.ocrf_raster_plan_build_workspace_bytes(self.P, self.V, self.capacity)),
-                                         dtype=torch.uint8, device=dev)
-            self.plan = torch.empty(max(int(L.ocrf_raster_plan_bytes(self.P, self.V, self.capacity)), 256),
-                                    dtype=torch.uint8, device=dev)
+        self._build_ws = torch.empty(int(L.ocrf_raster_plan_build_workspace_bytes(self.P, self.V, self.capacity)),
+                                     dtype=torch.uint8, device=dev)
+        self.plan = torch.empty(max(int(L.ocrf_raster_plan_bytes(self.P, self.V, self.capacity)), 256),
+                                dtype=torch.uint8, device=dev)
         # sticky status word (bit 4: extent bound exceeded in some call, bit 8: bad view index / unusable plan,
         # bit 16: a call's cameras were not the plan's)
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -91,53 +89,41 @@ class RasterPlan:
         self.rebuild()
         if self.bins is not None:
             bw, bh = self.bins
-            with _lib.on_device(dev):
-                need = int(L.ocrf_raster_plan_bins_workspace_bytes(self.P, self.V, self.H, self.W, bw, bh,
-                                                                   ctypes.c_long(self.capacity)))
-                if need == 0:
-                    raise _lib.OcrfHipError(f'RasterPlan: bins {self.bins} do not fit this image (at most 255 bins per axis)')
-                self._bins_ws = torch.empty(need, dtype=torch.uint8, device=dev)
-                if cand_capacity is None:
-                    total = torch.zeros(1, dtype=torch.int32, device=dev)
-                    self._build_bins(sizing=total)
-                    self.candidates = int(total.item())           # the second synchronisation
-                    cand_capacity = int(self.candidates * float(headroom)) + 4096
-                self.cand_capacity = max(1, int(cand_capacity))
-                self._bins_buf = torch.zeros(int(L.ocrf_raster_plan_bins_bytes(self.V, self.H, self.W, bw, bh,
-                                                                               ctypes.c_long(self.cand_capacity))),
-                                             dtype=torch.uint8, device=dev)
+            need = int(L.ocrf_raster_plan_bins_workspace_bytes(self.P, self.V, self.H, self.W, bw, bh, self.capacity))
+            if need == 0:
+                raise _lib.OcrfHipError(f'RasterPlan: bins {self.bins} do not fit this image (at most 255 bins per axis)')
+            self._bins_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            if cand_capacity is None:
+                total = torch.zeros(1, dtype=torch.int32, device=dev)
+                self._build_bins(sizing=total)
+                self.candidates = int(total.item())           # the second synchronisation
+                cand_capacity = int(self.candidates * float(headroom)) + 4096
+            self.cand_capacity = max(1, int(cand_capacity))
+            self._bins_buf = torch.zeros(int(L.ocrf_raster_plan_bins_bytes(self.V, self.H, self.W, bw, bh, self.cand_capacity)),
+                                         dtype=torch.uint8, device=dev)
             self._build_bins()
             self._record_built()
 
     def count(self, packed_cameras=None):
         """Synchronising: kept (Gaussian, view) records per view for ``packed_cameras`` (default: the plan's)."""
-        L = _lib.lib()
         cams = self.cameras if packed_cameras is None else _f32c(packed_cameras).reshape(-1, 36)
-        with _lib.on_device(self.device):
-            ws = torch.empty(int(L.ocrf_raster_plan_count_workspace_bytes(self.P)), dtype=torch.uint8, device=self.device)
-            mask = torch.empty(self.P, dtype=torch.int32, device=self.device)
-            total = torch.empty(1, dtype=torch.int32, device=self.device)
-            _lib.check(L.ocrf_raster_plan_count(self.P, self.V, self.H, self.W, _lib.ptr(self.means3D), _lib.ptr(cams),
-                                                ctypes.c_float(self.extent_bound), _lib.ptr(mask), _lib.ptr(total),
-                                                _lib.ptr(ws), ctypes.c_size_t(ws.numel()), _lib.stream_ptr(self.device)),
-                       'ocrf_raster_plan_count')
+        ws = torch.empty(int(_lib.lib().ocrf_raster_plan_count_workspace_bytes(self.P)), dtype=torch.uint8, device=self.device)
+        mask = torch.empty(self.P, dtype=torch.int32, device=self.device)
+        total = torch.empty(1, dtype=torch.int32, device=self.device)
+        _lib.launch('ocrf_raster_plan_count', self.device, self.P, self.V, self.H, self.W, self.means3D, cams,
+                    self.extent_bound, mask, total, ws, ws.numel())
         per_view = torch.stack([((mask >> v) & 1).sum() for v in range(self.V)]).cpu()
         kept = [int(v) for v in per_view]
         assert sum(kept) == int(total.item())
         return kept
 
     def _build_bins(self, sizing=None):
-        L = _lib.lib()
         bw, bh = self.bins
-        with _lib.on_device(self.device):
-            _lib.check(L.ocrf_raster_plan_bins_build(
-                _lib.ptr(self.plan), ctypes.c_size_t(self.plan.numel()), self.P, self.V, ctypes.c_long(self.capacity),
-                self.H, self.W, ctypes.c_float(self.extent_bound), bw, bh,
-                ctypes.c_long(0 if sizing is not None else self.cand_capacity),
-                _lib.ptr(None if sizing is not None else self._bins_buf),
-                ctypes.c_size_t(0 if sizing is not None else self._bins_buf.numel()), _lib.ptr(sizing),
-                _lib.ptr(self._bins_ws), ctypes.c_size_t(self._bins_ws.numel()), _lib.stream_ptr(self.device)),
-                'ocrf_raster_plan_bins_build')
+        lists = sizing is None                   # a sizing pass only counts the candidates into ``sizing``
+        _lib.launch('ocrf_raster_plan_bins_build', self.device, self.plan, self.plan.numel(), self.P, self.V, self.capacity,
+                    self.H, self.W, self.extent_bound, bw, bh, self.cand_capacity if lists else 0,
+                    self._bins_buf if lists else None, self._bins_buf.numel() if lists else 0, sizing,
+                    self._bins_ws, self._bins_ws.numel())
 
     def _record_built(self):
         # renders issued on ANOTHER stream must not overtake the build (a half-built plan holds wild record indices)
@@ -160,13 +146,8 @@ class RasterPlan:
             if means3D.shape != self.means3D.shape:
                 raise _lib.OcrfHipError('rebuild: the Gaussian count of a plan is fixed')
             self.means3D.copy_(_f32c(means3D), non_blocking=True)
-        L = _lib.lib()
-        with _lib.on_device(self.device):
-            _lib.check(L.ocrf_raster_plan_build(
-                self.P, self.V, self.H, self.W, _lib.ptr(self.means3D), _lib.ptr(self.cameras),
-                ctypes.c_float(self.extent_bound), ctypes.c_long(self.capacity), _lib.ptr(self._build_ws),
-                ctypes.c_size_t(self._build_ws.numel()), _lib.ptr(self.plan), ctypes.c_size_t(self.plan.numel()),
-                _lib.stream_ptr(self.device)), 'ocrf_raster_plan_build')
+        _lib.launch('ocrf_raster_plan_build', self.device, self.P, self.V, self.H, self.W, self.means3D, self.cameras,
+                    self.extent_bound, self.capacity, self._build_ws, self._build_ws.numel(), self.plan, self.plan.numel())
         if self._bins_buf is not None:
             self._build_bins()                   # the candidate lists belong to THESE lists (stale ones would be wrong)
         self._record_built()
@@ -175,10 +156,10 @@ class RasterPlan:
     def _scratch(self, n_sets):
         L = _lib.lib()
         if self._bins_buf is not None:
-            need = L.ocrf_rasterize_planned_bins_workspace_bytes(ctypes.c_long(self.capacity), n_sets, self.V, self.H, self.W,
-                                                                 self.bins[0], self.bins[1], ctypes.c_long(self.cand_capacity))
+            need = L.ocrf_rasterize_planned_bins_workspace_bytes(self.capacity, n_sets, self.V, self.H, self.W,
+                                                                 self.bins[0], self.bins[1], self.cand_capacity)
         else:
-            need = L.ocrf_rasterize_planned_workspace_bytes(ctypes.c_long(self.capacity), n_sets)
+            need = L.ocrf_rasterize_planned_workspace_bytes(self.capacity, n_sets)
         if self._dyn is None or self._dyn.numel() < need:
             # zero-filled: the guard flag lives in it between calls (include/ocrf_hip.h, ocrf_rasterize_planned)
             self._dyn = torch.zeros(max(int(need), 256), dtype=torch.uint8, device=self.device)
@@ -254,7 +235,6 @@ class RasterPlan:
             if getattr(self, '_chain_radii', None) is None or self._chain_radii.numel() < n_items * P:
                 self._chain_radii = torch.empty(n_items * P, dtype=torch.int32, device=dev)
             radii = self._chain_radii
-        L = _lib.lib()
         cur = torch.cuda.current_stream(dev)
         if self._built[1] != cur and cur.cuda_stream not in self._ordered_after_build \
                 and not torch.cuda.is_current_stream_capturing():
@@ -265,27 +245,21 @@ class RasterPlan:
             cur.wait_event(self._built[0])
             self._ordered_after_build.add(cur.cuda_stream)
         disjoint = S == 1 or (bool(views_disjoint) and item_view is not None)
-        with _lib.on_device(dev):
-            dyn = self._scratch(1 if disjoint else S)
-            chain = None
-            if use_guard:
-                need = L.ocrf_rasterize_workspace_bytes(P, n_items)
-                if self._chain_ws is None or self._chain_ws.numel() < need:
-                    self._chain_ws = torch.empty(int(need), dtype=torch.uint8, device=dev)
-                chain = self._chain_ws
-            _lib.check(L.ocrf_rasterize_planned(
-                _lib.ptr(self.plan), ctypes.c_size_t(self.plan.numel()), P, self.V, ctypes.c_long(self.capacity),
-                H, W, S, n_items, _lib.ptr(item_view), _lib.ptr(colors), _lib.ptr(opac), _lib.ptr(sc),
-                ctypes.c_float(scale_modifier), _lib.ptr(rot), _lib.ptr(bg), {'median': 0, 'mean': 1}[depth_mode],
-                _lib.ptr(out['color']), _lib.ptr(out['depth']), _lib.ptr(out['final_T']), _lib.ptr(radii),
-                _lib.ptr(self.status), _lib.ptr(dyn), ctypes.c_size_t(dyn.numel()), use_guard,
-                _lib.ptr(self.means3D), _lib.ptr(chain), ctypes.c_size_t(chain.numel() if chain is not None else 0),
-                int(blend_workgroups), _lib.ptr(yield_if), {'both': 0, 'update': 1, 'blend': 2}[phase],
-                _lib.ptr(cameras), int(disjoint), _lib.ptr(self._bins_buf),
-                ctypes.c_size_t(self._bins_buf.numel() if self._bins_buf is not None else 0),
-                self.bins[0] if self.bins else 0, self.bins[1] if self.bins else 0, ctypes.c_long(self.cand_capacity),
-                ctypes.c_void_p(self._hint.data_ptr() if self._hint is not None else 0), _lib.stream_ptr(dev)),
-                'ocrf_rasterize_planned')
+        dyn = self._scratch(1 if disjoint else S)
+        chain = None
+        if use_guard:
+            need = _lib.lib().ocrf_rasterize_workspace_bytes(P, n_items)
+            if self._chain_ws is None or self._chain_ws.numel() < need:
+                self._chain_ws = torch.empty(int(need), dtype=torch.uint8, device=dev)
+            chain = self._chain_ws
+        _lib.launch('ocrf_rasterize_planned', dev,
+                    self.plan, self.plan.numel(), P, self.V, self.capacity, H, W, S, n_items, item_view, colors, opac, sc,
+                    float(scale_modifier), rot, bg, {'median': 0, 'mean': 1}[depth_mode],
+                    out['color'], out['depth'], out['final_T'], radii, self.status, dyn, dyn.numel(), use_guard,
+                    self.means3D, chain, chain.numel() if chain is not None else 0,
+                    int(blend_workgroups), yield_if, {'both': 0, 'update': 1, 'blend': 2}[phase],
+                    cameras, int(disjoint), self._bins_buf, self._bins_buf.numel() if self._bins_buf is not None else 0,
+                    self.bins[0] if self.bins else 0, self.bins[1] if self.bins else 0, self.cand_capacity, self._hint)
         out['status'] = self.status
         return out
 

@@ -10,14 +10,90 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def declared_symbols():
-    text = open(os.path.join(ROOT, 'include', 'ocrf_hip.h')).read()
-    text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    return sorted(set(re.findall(r'\b((?:ocrf_|bev_pool_v2)\w*)\s*\(', text)))
+    return sorted(_lib.prototypes())
 
 
 def test_header_declares_entry_points():
     syms = declared_symbols()
     assert 'bev_pool_v2' in syms and 'bev_pool_v2_grad' in syms and 'ocrf_bev_pool_v2' in syms
+    # the parser sees every entry point the header names (a looser scan: any such name followed by a parenthesis)
+    assert set(re.findall(r'\b((?:ocrf_|bev_pool_v2)\w*)\s*\(', _lib._header_text())) == set(syms)
+
+
+def test_every_prototype_is_declared_on_the_library():
+    """restype / argtypes of every entry point come from include/ocrf_hip.h: one argtype per parameter, the C types mapped
+    as the parser maps them (every pointer c_void_p, ``const char *`` c_char_p, ``void`` None)."""
+    lib = _lib.lib()
+    protos = _lib.prototypes()
+    assert len(protos) > 100
+    for name, (restype, argtypes) in protos.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+    assert lib.ocrf_version.restype is ctypes.c_char_p and list(lib.ocrf_version.argtypes) == []
+    assert lib.ocrf_kernel_name.restype is ctypes.c_char_p and list(lib.ocrf_kernel_name.argtypes) == [ctypes.c_int]
+    assert lib.ocrf_step_destroy.restype is None and lib.bev_pool_v2.restype is None
+    assert lib.ocrf_bev_pool_v2_workspace_bytes.restype is ctypes.c_size_t
+    assert list(lib.ocrf_bev_pool_v2_workspace_bytes.argtypes) == [ctypes.c_int, ctypes.c_int, ctypes.c_long]
+    assert lib.ocrf_stereo_cost_volume.argtypes[8] is ctypes.c_longlong
+    assert list(lib.ocrf_depth_labels.argtypes[5:8]) == [ctypes.c_double] * 3
+    assert lib.ocrf_rasterize_planned.argtypes[-1] is ctypes.c_void_p          # ocrf_stream_t
+
+
+def test_prototype_parser_maps_c_types():
+    text = """
+        int ocrf_a(int n, long m, long long k, size_t s, float f, double d, ocrf_stream_t stream);
+        const char *ocrf_b(void);
+        void ocrf_c(const float *const *x, unsigned long long *y, ocrf_step **out,
+                    const char *name);
+        size_t ocrf_d();
+    """
+    c = ctypes
+    assert _lib.parse_prototypes(text) == {
+        'ocrf_a': (c.c_int, [c.c_int, c.c_long, c.c_longlong, c.c_size_t, c.c_float, c.c_double, c.c_void_p]),
+        'ocrf_b': (c.c_char_p, []),
+        'ocrf_c': (None, [c.c_void_p, c.c_void_p, c.c_void_p, c.c_char_p]),
+        'ocrf_d': (c.c_size_t, []),
+    }
+    import pytest
+    with pytest.raises(_lib.OcrfHipError, match='ocrf_e'):
+        _lib.parse_prototypes('int ocrf_e(int a, short b);')
+    with pytest.raises(_lib.OcrfHipError, match='ocrf_f'):
+        _lib.parse_prototypes('half ocrf_f(int a);')
+
+
+def test_header_constants():
+    assert (_lib.K_BEV_POOL_FWD, _lib.K_RASTER_BLEND, _lib.K_RASTER_BLEND_SORTED, _lib.K_HOA1_KV) == (1, 11, 18, 29)
+    assert _lib.K_BEV_POOL_MFMA == 6 and _lib.K_BEV_POOL_PANEL == 7 and _lib.K_BEV_POOL_CELL_WEIGHTS == 8
+    from ocrfdet_amd import center_decode
+    assert (center_decode.MAX_TASKS, center_decode.MAX_CLASSES) == (_lib.OCRF_CD_MAX_TASKS, _lib.OCRF_CD_MAX_CLASSES)
+
+
+def test_launch_passes_tensors_as_pointers_and_the_stream_last(monkeypatch):
+    import pytest
+    import torch
+    calls = []
+
+    class FakeLib:
+        def __init__(self, err):
+            self.err = err
+
+        def __getattr__(self, name):
+            def fn(*args):
+                calls.append((name, args))
+                return self.err
+            return fn
+    stream = ctypes.c_void_p(1234)
+    monkeypatch.setattr(_lib, 'stream_ptr', lambda device=None: stream)
+    monkeypatch.setattr(_lib, 'lib', lambda: FakeLib(0))
+    a, empty = torch.zeros(4), torch.zeros(0)
+    cpu = torch.device('cpu')
+    _lib.launch('ocrf_x', cpu, a, empty, None, 3, 1.5, a[1:])
+    assert calls == [('ocrf_x', (a.data_ptr(), 0, None, 3, 1.5, a.data_ptr() + 4, stream))]
+    _lib.launch('ocrf_y', cpu, a, stream=77)
+    assert calls[-1] == ('ocrf_y', (a.data_ptr(), 77))
+    monkeypatch.setattr(_lib, 'lib', lambda: FakeLib(700))
+    with pytest.raises(_lib.OcrfHipError, match='ocrf_z failed with hipError_t 700'):
+        _lib.launch('ocrf_z', cpu, a)
 
 
 def test_library_exports_every_declared_symbol():
@@ -69,11 +145,13 @@ def test_step_object_host_logic():
              'ocrf_hoa_channel_stats', 'ocrf_hoa_opacity_mask_gate', 'ocrf_stream_write_value32', 'ocrf_raster_plan_build',
              'ocrf_rasterize_forward', 'ocrf_bev_pool_v2_nchw_dyn', 'ocrf_lss_prepare', 'ocrf_ht_prepare',
              'ocrf_geometry_blocks', 'ocrf_rasterize_forward_sets']
-    for name in names:
+    held = [s for s in declared_symbols() if L.ocrf_step_fn_id(s.encode()) >= 0]
+    assert set(names) <= set(held)
+    for name in held:
         fid = L.ocrf_step_fn_id(name.encode())
-        assert fid >= 0, name
         fn = getattr(L, name)
         assert fn.argtypes is not None, f'{name} has no ctypes declaration'
+        assert fn.argtypes[-1] is ctypes.c_void_p, f'{name}: the last argument is the stream'
         assert L.ocrf_step_fn_args(fid) == len(fn.argtypes) - 1, name
     assert L.ocrf_step_fn_id(b'ocrf_version') == -1 and L.ocrf_step_fn_args(-1) == -1 and L.ocrf_step_fn_args(999) == -1
     h = ctypes.c_void_p()
