@@ -567,7 +567,7 @@ int ocrf_center_head_reg_loss_backward(int B, int T, int HW, int max_objs, int w
  *
  * ocrf_center_decode: heads[6T] (host table of device f32 pointers, per task heatmap logits (B, ncls[t], H, W), reg
  *   (B, 2, H, W), height (B, 1, H, W), dim (B, 3, H, W), rot (B, 2, H, W) and vel (B, 2, H, W), vel NULL without
- *   velocity).  Host scalars: max_num = K (<= 1024, <= H * W), pre_max_size, post_max_size (> 0), out_size_factor,
+ *   velocity).  Host scalars: max_num = K (<= OCRF_CD_MAX_NUM, <= H * W), pre_max_size, post_max_size (> 0), out_size_factor,
  *   voxel_size[2], pc_range[2], the coder's score threshold (applied when has_coder_score_threshold) and
  *   post_center_range[6] (NULL = none), the test cfg's score threshold (>=, when has_score_threshold) and
  *   post_center_limit_range[6] (NULL = none), per task nms_circle[T] (1 = circle NMS), nms_threshold[T] (the IoU
@@ -578,6 +578,7 @@ int ocrf_center_head_reg_loss_backward(int B, int T, int HW, int max_objs, int w
  */
 #define OCRF_CD_MAX_TASKS 8
 #define OCRF_CD_MAX_CLASSES 8
+#define OCRF_CD_MAX_NUM 1024
 size_t ocrf_center_decode_workspace_bytes(int B, int T, int max_num, int post_max_size);
 int ocrf_center_decode(int B, int T, const int *ncls, int H, int W, const float *const *heads, int with_velocity,
                        int norm_bbox, int max_num, int pre_max_size, int post_max_size, float out_size_factor,

@@ -39,6 +39,7 @@ __all__ = ['CenterPointBBoxCoder', 'DecodeConfig', 'box_corners', 'box_iou_rotat
 
 MAX_TASKS = _lib.OCRF_CD_MAX_TASKS
 MAX_CLASSES = _lib.OCRF_CD_MAX_CLASSES
+MAX_NUM = _lib.OCRF_CD_MAX_NUM
 HEAD_KEYS = ('heatmap', 'reg', 'height', 'dim', 'rot', 'vel')
 _POLY_CAP = 12
 
@@ -278,6 +279,8 @@ class DecodeConfig:
             raise ValueError(f'at most {MAX_TASKS} tasks of {MAX_CLASSES} classes, got {ncls}')
         self.ncls = list(ncls)
         self.K = int(coder.max_num)
+        if not 0 < self.K <= MAX_NUM:
+            raise ValueError(f'max_num must be in [1, {MAX_NUM}], got {self.K}')
         self.coder = coder
         nms_type = test_cfg.get('nms_type')
         self.circle = [(nms_type[t] if isinstance(nms_type, list) else nms_type) == 'circle' for t in range(T)]
@@ -389,6 +392,8 @@ def decode_fused(preds_dicts, cfg, norm_bbox=True):
     T = len(preds_dicts)
     p0 = preds_dicts[0][0]
     B, _, H, W = p0['heatmap'].shape
+    if cfg.K > H * W:
+        raise ValueError(f'max_num {cfg.K} exceeds the map size {H} x {W}')
     dev = p0['heatmap'].device
     with_vel = 'vel' in p0
     keys = HEAD_KEYS if with_vel else HEAD_KEYS[:5]

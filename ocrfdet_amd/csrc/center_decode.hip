@@ -26,7 +26,7 @@
 namespace {
 
 constexpr int kSelThreads = 1024;
-constexpr int kMaxK = 1024;
+constexpr int kMaxK = OCRF_CD_MAX_NUM;
 constexpr int kWriteThreads = 256;
 constexpr int kScanLdsBytes = 64 * 1024;
 

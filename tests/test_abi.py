@@ -66,6 +66,7 @@ def test_header_constants():
     assert _lib.K_BEV_POOL_MFMA == 6 and _lib.K_BEV_POOL_PANEL == 7 and _lib.K_BEV_POOL_CELL_WEIGHTS == 8
     from ocrfdet_amd import center_decode
     assert (center_decode.MAX_TASKS, center_decode.MAX_CLASSES) == (_lib.OCRF_CD_MAX_TASKS, _lib.OCRF_CD_MAX_CLASSES)
+    assert center_decode.MAX_NUM == _lib.OCRF_CD_MAX_NUM == 1024
 
 
 def test_launch_passes_tensors_as_pointers_and_the_stream_last(monkeypatch):
