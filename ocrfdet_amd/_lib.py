@@ -5,6 +5,7 @@ launches through it.  Its entry points are declared from ``include/ocrf_hip.h`` 
 is how the ops call them.  ``build()`` compiles it in-tree with hipcc for gfx950 (cross-compiles
 without a GPU); the built ``.so`` is git-ignored but travels with the source tree.
 """
+import collections
 import contextlib
 import ctypes
 import os
@@ -92,17 +93,26 @@ def _ctype(spelling, proto, ret=False):
     raise OcrfHipError(f'ocrf_hip.h: no ctypes type for {spelling.strip()!r} in {proto!r}')
 
 
-def parse_prototypes(text):
-    """{name: (restype, [argtypes])} of every ``ocrf_*`` / ``bev_pool_v2*`` prototype in C source ``text`` (comments
-    already stripped).  A type without a mapping raises ``OcrfHipError`` naming the prototype."""
-    out = {}
+def _declarations(text):
+    """(return type, name, prototype, [parameter types]) of every ``ocrf_*`` / ``bev_pool_v2*`` prototype in C source
+    ``text`` (comments already stripped), the types as they are spelled."""
     for m in _PROTO.finditer(text):
         ret, name, params = m.groups()
-        proto = ' '.join(m.group(0).split())
         params = [] if params.strip() in ('', 'void') else params.split(',')
         # a parameter's name is its last identifier; what is in front of it is its type
-        out[name] = (_ctype(ret, proto, ret=True), [_ctype(re.sub(r'\b\w+\s*$', '', p), proto) for p in params])
-    return out
+        yield ret, name, ' '.join(m.group(0).split()), [' '.join(re.sub(r'\b\w+\s*$', '', p).split()) for p in params]
+
+
+def parse_prototypes(text):
+    """{name: (restype, [argtypes])} of every prototype in ``text`` (``_declarations``).  A type without a mapping raises
+    ``OcrfHipError`` naming the prototype."""
+    return {name: (_ctype(ret, proto, ret=True), [_ctype(p, proto) for p in params])
+            for ret, name, proto, params in _declarations(text)}
+
+
+def parse_enqueueing(text):
+    """Names of the prototypes in ``text`` that enqueue work: exactly those whose last parameter is an ``ocrf_stream_t``."""
+    return frozenset(name for _, name, _, params in _declarations(text) if params[-1:] == ['ocrf_stream_t'])
 
 
 def prototypes():
@@ -118,6 +128,7 @@ def _constants(text):
 
 
 globals().update(_constants(_header_text()))      # K_BEV_POOL_FWD, OCRF_CD_MAX_TASKS, ...
+_ENQUEUEING = parse_enqueueing(_header_text())    # what a step being recorded logs (``_RecordingLib``)
 
 
 # passed as they are without the isinstance(a, torch.Tensor) check (~70 ns each): scalars, NULL, pre-built pointers
@@ -146,10 +157,6 @@ import threading  # noqa: E402
 
 _RECORDER = threading.local()      # .rec: the StepRecorder of THIS thread (another thread calling lib()
                                    # while a step is recorded must not get its calls spliced into that step)
-# entry points that enqueue nothing (sizes, lengths, knobs, timers): passed through while a step is being recorded
-_QUERY_SUFFIXES = ('_bytes', '_len', '_rows', '_side', '_panels', '_tiles', '_bands', '_resident', '_version', '_name',
-                   '_max_units')
-_QUERY_PREFIXES = ('ocrf_timer_', 'ocrf_tune_', 'ocrf_step_', 'ocrf_diag_', 'ocrf_kernel_')
 
 
 class StepNotRecordable(OcrfHipError):
@@ -222,14 +229,15 @@ class StepRecorder:
 
 
 class _RecordingLib:
-    """What ``lib()`` hands out while a step is recorded: every enqueueing entry point is logged, then called."""
+    """What ``lib()`` hands out while a step is recorded: every entry point that enqueues work (its last parameter is an
+    ``ocrf_stream_t``, ``_ENQUEUEING``) is logged, then called; every other one is passed through."""
 
     def __init__(self, L, rec):
         self._L, self._rec = L, rec
 
     def __getattr__(self, name):
         fn = getattr(self._L, name)
-        if (not name.startswith('ocrf_') or name.endswith(_QUERY_SUFFIXES) or name.startswith(_QUERY_PREFIXES)):
+        if name not in _ENQUEUEING:
             return fn
         rec = self._rec
 
@@ -278,6 +286,86 @@ class CompiledStep:
                 self._h = None
         except Exception:
             pass
+
+
+_Recorded = collections.namedtuple('_Recorded', 'step outputs pool generation')
+_BITS = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+
+
+def _same_bits(a, b):
+    """``a`` and ``b`` hold the same bits (a NaN equals the same NaN, 0.0 differs from -0.0)."""
+    as_int = _BITS[a.element_size()]
+    return torch.equal(a.view(as_int), b.view(as_int))
+
+
+class StepCache:
+    """Recorded steps (``CompiledStep``) by key: whatever decides a step's launches and pointers.  ``cache(key, streams,
+    fn)``, where ``fn(rec)`` issues the step eagerly on ``streams`` (slot 0 = the caller's) and returns its outputs: the
+    first sighting of a key runs eagerly (plans and scratch get built), the second is recorded (``StepRecorder``) with its
+    allocations in a memory pool of its own, from the third the recording is replayed and returns the same outputs.
+
+    A recording holds while ``workspace.generation`` stays where it was before recording: a replaced scratch buffer
+    means stale pointers, and the key is recorded anew.  ``check(outputs)``, if given, yields the tensors the first replay
+    must reproduce bit for bit: the recorder sees the library's calls only, so a torch kernel inside the step would be
+    missing from the replay.  A step that cannot be recorded or does not reproduce itself is refused
+    (``refused``: why) and every later call runs eagerly.  At most ``size`` recordings and ``seen_size`` first sightings
+    are kept: a caller that hands over new tensors every step never repeats a key."""
+
+    def __init__(self, device, size, seen_size, check=None):
+        self.device, self.size, self.seen_size, self.check = device, int(size), int(seen_size), check
+        self._recorded = {}                    # key -> _Recorded
+        self._seen = set()
+        self.refused = None
+
+    def __len__(self):
+        return len(self._recorded)
+
+    def values(self):
+        return self._recorded.values()
+
+    def clear(self):
+        self._recorded.clear()
+        self._seen.clear()
+
+    def __call__(self, key, streams, fn):
+        if self.refused is not None or torch.cuda.is_current_stream_capturing():
+            return fn(None)
+        generation = workspace.generation(self.device)
+        hit = self._recorded.get(key)
+        if hit is not None:
+            if hit.generation == generation:
+                hit.step.run(*[st.cuda_stream for st in streams])
+                return hit.outputs
+            del self._recorded[key]            # a scratch buffer it baked in was replaced since: record anew
+        elif key not in self._seen:
+            if len(self._seen) >= self.seen_size:
+                self._seen.clear()
+            self._seen.add(key)
+            return fn(None)
+        return self._record(key, streams, fn, generation)
+
+    def _record(self, key, streams, fn, generation):
+        rec, pool = StepRecorder(streams), torch.cuda.MemPool()
+        with torch.cuda.use_mem_pool(pool, self.device), rec:
+            out = fn(rec)
+        if not rec.ok:
+            self.refused = rec.why
+            return out
+        if workspace.generation(self.device) != generation:
+            return out                         # a scratch buffer was replaced while recording: record again next time
+        step = rec.build()
+        if self.check is not None:
+            got = list(self.check(out))
+            want = [t.clone() for t in got]
+            step.run(*[st.cuda_stream for st in streams])
+            torch.cuda.synchronize(self.device)
+            if not all(_same_bits(a, b) for a, b in zip(got, want)):
+                self.refused = 'the first replay of the recorded step did not reproduce the step issued call by call'
+                return fn(None)
+        while len(self._recorded) >= self.size:
+            self._recorded.pop(next(iter(self._recorded)))
+        self._recorded[key] = _Recorded(step, out, pool, generation)
+        return out
 
 
 def check(err, what):
@@ -382,8 +470,9 @@ class Workspace:
             users.add(_raw_stream(idx))
         if buf is None or buf.numel() < nbytes:
             if buf is not None:
-                # whoever baked the old buffer's address into a recorded step (HotPath._compiled, ShardedHotPath._segments)
-                # sees the generation move and records anew instead of replaying into freed memory
+                # whoever baked the old buffer's address into a recorded step (StepCache: HotPath._compiled,
+                # ShardedHotPath._segments) sees the generation move and records anew instead of replaying into freed
+                # memory
                 self._generation[idx] = self._generation.get(idx, 0) + 1
                 for raw in self._users.get(key, ()):
                     if raw:                    # 0 = the legacy default stream, the allocator's own

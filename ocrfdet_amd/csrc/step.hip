@@ -8,165 +8,99 @@
 // entry points, the same arguments, the caller's streams.  Nothing is captured into a hipGraph (replaying the step as a
 // graph was measured slower: 0.28 vs 0.23 ms) — the launches are issued eagerly, only without the interpreter.
 //
+// Which entry points a step can hold is one list (kFns); how many argument words each takes and how each word is
+// converted back to its parameter's type are derived from the prototypes in ocrf_hip.h at compile time (Signature).
+//
 // Every pointer argument is used as recorded: the caller keeps the tensors alive and in place (persistent inputs,
 // outputs and scratch), exactly as for a captured graph.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstring>
+#include <tuple>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "ocrf_hip.h"
 
 namespace {
 
-enum Fn : int {
-  kPoolPlanned = 0,
-  kPoolMfma,
-  kPoolCellWeights,
-  kPoolPanel,
-  kRasterizePlanned,
-  kHoa1,
-  kHoaV2b,
-  kHoaStats,
-  kHoaMaskGate,
-  kStreamWrite32,
-  kRasterPlanBuild,
-  kRasterizeForward,
-  kPoolDyn,
-  kLssPrepare,
-  kHtPrepare,
-  kGeometryBlocks,
-  kRasterizeForwardSets,
-  kFnCount
+constexpr int kMaxArgs = 40;
+constexpr int kMaxStreams = 8;
+
+// A recorded argument word as the declared type of its parameter: a pointer from its address, a float from its bit
+// pattern (the low 32 bits), an integer from its 64-bit two's complement.  Any other parameter type does not compile.
+template <typename T>
+T word_as(uint64_t w) {
+  if constexpr (std::is_pointer_v<T>) {
+    return reinterpret_cast<T>(static_cast<uintptr_t>(w));
+  } else if constexpr (std::is_same_v<T, float>) {
+    const uint32_t b = static_cast<uint32_t>(w);
+    float f;
+    std::memcpy(&f, &b, 4);
+    return f;
+  } else {
+    static_assert(std::is_integral_v<T>, "a step argument is a pointer, a float or an integer");
+    return static_cast<T>(static_cast<int64_t>(w));
+  }
+}
+
+// What a step needs of an entry point, derived from its prototype: how many argument words it takes (the trailing
+// stream excluded) and how to call it with them.
+template <typename F>
+struct Signature;
+template <typename R, typename... A>
+struct Signature<R (*)(A...)> {
+  static constexpr int n_args = int(sizeof...(A)) - 1;
+  static_assert(std::is_same_v<R, int>, "an entry point a step holds returns its hipError_t as int");
+  static_assert(std::is_same_v<std::tuple_element_t<sizeof...(A), std::tuple<void, A...>>, ocrf_stream_t>,
+                "an entry point a step holds takes its ocrf_stream_t last");
+  static_assert(n_args <= kMaxArgs, "raise kMaxArgs");
+
+  template <R (*fn)(A...), size_t... I>
+  static int call(const uint64_t* a, ocrf_stream_t s, std::index_sequence<I...>) {
+    return fn(word_as<std::tuple_element_t<I, std::tuple<A...>>>(a[I])..., s);
+  }
 };
+
+template <auto fn>
+int invoke(const uint64_t* a, ocrf_stream_t s) {
+  using Sig = Signature<decltype(fn)>;
+  return Sig::template call<fn>(a, s, std::make_index_sequence<Sig::n_args>{});
+}
 
 struct FnInfo {
   const char* name;
   int n_args;          // without the trailing stream
+  int (*invoke)(const uint64_t* args, ocrf_stream_t stream);
 };
 
-const FnInfo kFns[kFnCount] = {
-    {"ocrf_bev_pool_v2_nchw_planned", 17}, {"ocrf_bev_pool_v2_nchw_mfma", 19},  {"ocrf_bev_pool_cell_weights", 9},
-    {"ocrf_bev_pool_v2_nchw_panel", 20},   {"ocrf_rasterize_planned", 39},      {"ocrf_hoa1_forward", 9},
-    {"ocrf_hoa_v2b_forward", 9},           {"ocrf_hoa_channel_stats", 6},       {"ocrf_hoa_opacity_mask_gate", 11},
-    {"ocrf_stream_write_value32", 2},      {"ocrf_raster_plan_build", 12},      {"ocrf_rasterize_forward", 23},
-    {"ocrf_bev_pool_v2_nchw_dyn", 19},     {"ocrf_lss_prepare", 20},            {"ocrf_ht_prepare", 22},
-    {"ocrf_geometry_blocks", 16},          {"ocrf_rasterize_forward_sets", 24},
-};
+#define OCRF_STEP_FN(fn) FnInfo{#fn, Signature<decltype(&fn)>::n_args, &invoke<&fn>}
 
-constexpr int kMaxArgs = 40;
-constexpr int kMaxStreams = 8;
+// The entry points a step can hold; a position in this list is the id ocrf_step_fn_id returns.  The per-sample step
+// (nothing calibration- or pose-dependent cached) adds the index preparation, pooling on device-side counts and the
+// per-call render; their host-pointer arguments (grid bounds, pc_range) are read at replay like at the call: the caller
+// keeps them alive (ocrfdet_amd.index_prep._host_floats).
+const FnInfo kFns[] = {
+    OCRF_STEP_FN(ocrf_bev_pool_v2_nchw_planned), OCRF_STEP_FN(ocrf_bev_pool_v2_nchw_mfma),
+    OCRF_STEP_FN(ocrf_bev_pool_cell_weights),    OCRF_STEP_FN(ocrf_bev_pool_v2_nchw_panel),
+    OCRF_STEP_FN(ocrf_rasterize_planned),        OCRF_STEP_FN(ocrf_hoa1_forward),
+    OCRF_STEP_FN(ocrf_hoa_v2b_forward),          OCRF_STEP_FN(ocrf_hoa_channel_stats),
+    OCRF_STEP_FN(ocrf_hoa_opacity_mask_gate),    OCRF_STEP_FN(ocrf_stream_write_value32),
+    OCRF_STEP_FN(ocrf_raster_plan_build),        OCRF_STEP_FN(ocrf_rasterize_forward),
+    OCRF_STEP_FN(ocrf_bev_pool_v2_nchw_dyn),     OCRF_STEP_FN(ocrf_lss_prepare),
+    OCRF_STEP_FN(ocrf_ht_prepare),               OCRF_STEP_FN(ocrf_geometry_blocks),
+    OCRF_STEP_FN(ocrf_rasterize_forward_sets),
+};
+#undef OCRF_STEP_FN
+constexpr int kFnCount = int(sizeof(kFns) / sizeof(kFns[0]));
 
 struct Cmd {
   int kind;            // 0: call, 1: fork (from -> to), 2: join (`to` waits for `from`)
   int fn, slot, from, to;
   uint64_t a[kMaxArgs];      // ints / pointers / sizes as 64-bit words, floats as their bit pattern
 };
-
-// typed views of a recorded argument word
-template <typename T>
-inline T P(uint64_t v) { return reinterpret_cast<T>(static_cast<uintptr_t>(v)); }
-inline int I(uint64_t v) { return static_cast<int>(static_cast<int64_t>(v)); }
-inline long L(uint64_t v) { return static_cast<long>(static_cast<int64_t>(v)); }
-inline size_t Z(uint64_t v) { return static_cast<size_t>(v); }
-inline float F(uint64_t v) {
-  const uint32_t b = static_cast<uint32_t>(v);
-  float f;
-  std::memcpy(&f, &b, 4);
-  return f;
-}
-
-int call(const Cmd& c, ocrf_stream_t s) {
-  const uint64_t* a = c.a;
-  switch (c.fn) {
-    case kPoolPlanned:
-      return ocrf_bev_pool_v2_nchw_planned(I(a[0]), I(a[1]), P<const float*>(a[2]), P<const float*>(a[3]),
-                                           P<const int*>(a[4]), P<const int*>(a[5]), P<void*>(a[6]), P<float*>(a[7]),
-                                           I(a[8]), I(a[9]), I(a[10]), I(a[11]), I(a[12]), P<void*>(a[13]), Z(a[14]), Z(a[15]),
-                                           Z(a[16]), s);
-    case kPoolMfma:
-      return ocrf_bev_pool_v2_nchw_mfma(I(a[0]), I(a[1]), P<const int*>(a[2]), P<const int*>(a[3]), P<const int*>(a[4]),
-                                        P<const int*>(a[5]), P<const int*>(a[6]), P<const int*>(a[7]),
-                                        P<const int*>(a[8]), P<const float*>(a[9]), P<const float*>(a[10]),
-                                        P<float*>(a[11]), I(a[12]), I(a[13]), I(a[14]), I(a[15]), I(a[16]),
-                                        P<int*>(a[17]), P<void*>(a[18]), s);
-    case kPoolCellWeights:
-      return ocrf_bev_pool_cell_weights(I(a[0]), P<const int*>(a[1]), P<const int*>(a[2]), P<float*>(a[3]), I(a[4]),
-                                        P<const int*>(a[5]), P<const int*>(a[6]), P<float*>(a[7]),
-                                        P<const float*>(a[8]), s);
-    case kPoolPanel:
-      return ocrf_bev_pool_v2_nchw_panel(I(a[0]), I(a[1]), P<const int*>(a[2]), P<const int*>(a[3]), P<const int*>(a[4]),
-                                         P<const int*>(a[5]), P<const int*>(a[6]), P<const int*>(a[7]),
-                                         P<const unsigned short*>(a[8]), P<const float*>(a[9]), P<const float*>(a[10]),
-                                         P<float*>(a[11]), I(a[12]), I(a[13]), I(a[14]), I(a[15]), I(a[16]),
-                                         P<int*>(a[17]), P<void*>(a[18]), Z(a[19]), s);
-    case kRasterizePlanned:
-      return ocrf_rasterize_planned(P<const void*>(a[0]), Z(a[1]), I(a[2]), I(a[3]), L(a[4]), I(a[5]), I(a[6]), I(a[7]),
-                                    I(a[8]), P<const int*>(a[9]), P<const float*>(a[10]), P<const float*>(a[11]),
-                                    P<const float*>(a[12]), F(a[13]), P<const float*>(a[14]), P<const float*>(a[15]),
-                                    I(a[16]), P<float*>(a[17]), P<float*>(a[18]), P<float*>(a[19]), P<int*>(a[20]),
-                                    P<int*>(a[21]), P<void*>(a[22]), Z(a[23]), I(a[24]), P<const float*>(a[25]),
-                                    P<void*>(a[26]), Z(a[27]), I(a[28]), P<const int*>(a[29]), I(a[30]),
-                                    P<const float*>(a[31]), I(a[32]), P<const void*>(a[33]), Z(a[34]), I(a[35]), I(a[36]),
-                                    L(a[37]), P<int*>(a[38]), s);
-    case kHoa1:
-      return ocrf_hoa1_forward(P<const float*>(a[0]), P<const float*>(a[1]), P<const float*>(a[2]), I(a[3]), I(a[4]),
-                               I(a[5]), F(a[6]), P<float*>(a[7]), P<float*>(a[8]), s);
-    case kHoaV2b:
-      return ocrf_hoa_v2b_forward(P<const float*>(a[0]), P<const float*>(a[1]), P<const float*>(a[2]), I(a[3]), I(a[4]),
-                                  I(a[5]), P<void*>(a[6]), Z(a[7]), P<float*>(a[8]), s);
-    case kHoaStats:
-      return ocrf_hoa_channel_stats(P<const float*>(a[0]), I(a[1]), I(a[2]), I(a[3]), I(a[4]), P<float*>(a[5]), s);
-    case kHoaMaskGate:
-      return ocrf_hoa_opacity_mask_gate(P<const float*>(a[0]), P<const float*>(a[1]), P<const float*>(a[2]),
-                                        P<const float*>(a[3]), I(a[4]), I(a[5]), I(a[6]), I(a[7]), I(a[8]),
-                                        P<float*>(a[9]), P<float*>(a[10]), s);
-    case kStreamWrite32:
-      return ocrf_stream_write_value32(P<int*>(a[0]), I(a[1]), s);
-    case kRasterPlanBuild:
-      return ocrf_raster_plan_build(I(a[0]), I(a[1]), I(a[2]), I(a[3]), P<const float*>(a[4]), P<const float*>(a[5]),
-                                    F(a[6]), L(a[7]), P<void*>(a[8]), Z(a[9]), P<void*>(a[10]), Z(a[11]), s);
-    // the per-sample step (nothing calibration- or pose-dependent cached): index preparation, pooling on device-side
-    // counts, the per-call render.  Host-pointer arguments (grid bounds, pc_range) are read at replay like at the call:
-    // the caller keeps them alive (ocrfdet_amd.index_prep._host_floats)
-    case kRasterizeForward:
-      return ocrf_rasterize_forward(I(a[0]), I(a[1]), I(a[2]), I(a[3]), P<const float*>(a[4]), P<const float*>(a[5]),
-                                    P<const float*>(a[6]), P<const float*>(a[7]), F(a[8]), P<const float*>(a[9]),
-                                    P<const float*>(a[10]), P<const float*>(a[11]), P<const float*>(a[12]), I(a[13]),
-                                    P<float*>(a[14]), P<float*>(a[15]), P<float*>(a[16]), P<uint32_t*>(a[17]),
-                                    P<int*>(a[18]), P<uint32_t*>(a[19]), P<int*>(a[20]), P<void*>(a[21]), Z(a[22]), s);
-    case kRasterizeForwardSets:
-      return ocrf_rasterize_forward_sets(I(a[0]), I(a[1]), I(a[2]), I(a[3]), I(a[4]), P<const float*>(a[5]),
-                                         P<const float*>(a[6]), P<const float*>(a[7]), P<const float*>(a[8]), F(a[9]),
-                                         P<const float*>(a[10]), P<const float*>(a[11]), P<const float*>(a[12]),
-                                         P<const float*>(a[13]), I(a[14]), P<float*>(a[15]), P<float*>(a[16]),
-                                         P<float*>(a[17]), P<uint32_t*>(a[18]), P<int*>(a[19]), P<uint32_t*>(a[20]),
-                                         P<int*>(a[21]), P<void*>(a[22]), Z(a[23]), s);
-    case kPoolDyn:
-      return ocrf_bev_pool_v2_nchw_dyn(I(a[0]), I(a[1]), I(a[2]), P<const int*>(a[3]), P<const float*>(a[4]),
-                                       P<const float*>(a[5]), P<const int*>(a[6]), P<const int*>(a[7]), P<const int*>(a[8]),
-                                       P<const int*>(a[9]), P<const int*>(a[10]), P<float*>(a[11]), I(a[12]), I(a[13]),
-                                       I(a[14]), I(a[15]), I(a[16]), P<void*>(a[17]), Z(a[18]), s);
-    case kLssPrepare:
-      return ocrf_lss_prepare(I(a[0]), I(a[1]), I(a[2]), I(a[3]), I(a[4]), P<const float*>(a[5]), P<const float*>(a[6]),
-                              P<const float*>(a[7]), P<const float*>(a[8]), I(a[9]), I(a[10]), I(a[11]), P<int*>(a[12]),
-                              P<int*>(a[13]), P<int*>(a[14]), P<int*>(a[15]), P<int*>(a[16]), P<int*>(a[17]),
-                              P<void*>(a[18]), Z(a[19]), s);
-    case kHtPrepare:
-      return ocrf_ht_prepare(I(a[0]), I(a[1]), I(a[2]), I(a[3]), I(a[4]), I(a[5]), I(a[6]), P<const float*>(a[7]),
-                             P<const float*>(a[8]), P<const float*>(a[9]), F(a[10]), F(a[11]), F(a[12]), F(a[13]),
-                             P<int*>(a[14]), P<int*>(a[15]), P<int*>(a[16]), P<int*>(a[17]), P<int*>(a[18]),
-                             P<int*>(a[19]), P<void*>(a[20]), Z(a[21]), s);
-    case kGeometryBlocks:
-      return ocrf_geometry_blocks(I(a[0]), I(a[1]), P<const float*>(a[2]), P<const float*>(a[3]), P<const float*>(a[4]),
-                                  P<const float*>(a[5]), P<const float*>(a[6]), P<const float*>(a[7]),
-                                  P<const float*>(a[8]), I(a[9]), I(a[10]), F(a[11]), F(a[12]), P<float*>(a[13]),
-                                  P<float*>(a[14]), P<float*>(a[15]), s);
-    default:
-      return (int)hipErrorInvalidValue;
-  }
-}
 
 }  // namespace
 
@@ -237,7 +171,7 @@ int ocrf_step_run(ocrf_step* s, const ocrf_stream_t* streams, int n_streams) {
   for (const Cmd& c : s->cmds) {
     if (c.kind == 0) {
       if (c.slot >= n_streams) return (int)hipErrorInvalidValue;
-      const int e = call(c, streams[c.slot]);
+      const int e = kFns[c.fn].invoke(c.a, streams[c.slot]);
       if (e != 0) return e;
     } else {
       if (c.from >= n_streams || c.to >= n_streams) return (int)hipErrorInvalidValue;

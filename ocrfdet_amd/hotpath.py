@@ -86,7 +86,7 @@ class HotPath:
         (``set_phase``; default: only for 'objects') — new parameters every step, as a network's heads produce them: the
         planned render's adaptive head then always works from the OTHER set's reach.
         ``one_call``: after its first, recorded, issue a step is ONE host call (``ocrf_hotpath_step``: the library calls
-        of the step replayed from C, ``_lib.StepRecorder``) instead of ~14 ctypes calls + torch stream / event calls
+        of the step replayed from C, ``_lib.StepCache``) instead of ~14 ctypes calls + torch stream / event calls
         (225 -> ~60 us of host work at cfg2).  The step's outputs are then the SAME tensors every step (overwritten by
         the next one, like a replayed graph's), and ``depth`` / ``feat`` have to be the tensors of the recorded call
         (another pair is recorded anew)."""
@@ -115,9 +115,8 @@ class HotPath:
         self.lss_pool_backend, self.lss_mfma_group = lss_pool_backend, int(lss_mfma_group)
         self.hoa_first = hoa_first
         self.one_call = bool(one_call) and self.device.type == 'cuda'
-        self._compiled = {}                    # key -> (_lib.CompiledStep, outputs, memory pool, scratch hold) of a recorded step
-        self._one_call_ok = True
-        self._warm_keys = set()
+        # the recorded steps: (two phases x two input pairs, with room)
+        self._compiled = _lib.StepCache(self.device, size=4, seen_size=16, check=self._flat_outputs)
         # planned renders: consecutive frames in one plan / one launch pair.  'auto': when ALL frames fit one plan
         # (<= 32 views; cfg2: 0.300 -> 0.285 ms — one update -> blend hand-over and one drain of the persistent grid
         # less); with more frames a launch pair per frame is faster (cfg4: 3.08 vs 3.18 ms in groups of five)
@@ -569,30 +568,24 @@ class HotPath:
         the returned tensors are the same objects every step (see ``__init__``)."""
         if self.cfg.render and self.render_mode == 'planned':
             self._plans()             # first step: built on the caller's stream BEFORE the side streams branch off it
-        if not (self.one_call and self._one_call_ok) or torch.cuda.is_current_stream_capturing():
+        if not self.one_call:
             return self._step_eager(depth, feat)
-        cur = torch.cuda.current_stream(self.device)
-        key = self._step_key(depth, feat)
-        hit = self._compiled.get(key)
-        if hit is not None and hit[3] != _lib.workspace.generation(self.device):
-            # a scratch buffer the recording baked in was replaced since (a larger request for its tag, by anyone in the
-            # process): its pointers are stale — record anew (ADVICE round 5)
-            del self._compiled[key]
-            hit = None
-        if hit is None:
-            if key not in self._warm_keys:
-                # the first step of a (tensors, mode) builds plans and scratch (launches that belong to no later step):
-                # issued call by call, the next one is recorded
-                if len(self._warm_keys) >= 16:
-                    self._warm_keys.clear()
-                self._warm_keys.add(key)
-                return self._step_eager(depth, feat)
-            return self._record_step(depth, feat, key, cur)
-        compiled, out, _pool, _gen = hit
-        compiled.run(*[st.cuda_stream for st in self._step_streams(cur)])
+        if (self._compiled.refused is None and self.index_prep_mode == 'per_step'
+                and not (self.device_geometry and hasattr(self, '_calib_dev'))):
+            # the per-step index preparation with the calibration algebra on the HOST (torch CPU ops + uploads per step,
+            # which a replay would not repeat): issued call by call
+            self._compiled.refused = 'per-step calibration algebra on the host is issued call by call'
+        out = self._compiled(self._step_key(depth, feat), self._step_streams(torch.cuda.current_stream(self.device)),
+                             lambda rec: self._step_eager(depth, feat, rec))
+        # a replay does not go through RasterPlan.render, which marks a host-guarded render for check_render_plans()
         for entry in (self.render_plans or []) if self.cfg.render and self.render_mode == 'planned' else []:
             entry[0]._host_guarded = entry[0]._host_guarded or self.render_guard == 'host'
         return out
+
+    @property
+    def one_call_refused(self):
+        """Why steps are issued call by call although ``one_call`` asked for one host call (None: they are not)."""
+        return self._compiled.refused
 
     def _step_key(self, depth, feat):
         """Everything ``_step_eager`` reads that decides WHICH launches a step is (a recorded step must not
@@ -625,38 +618,6 @@ class HotPath:
                 self._prep_stream2 = shared_stream(self.device, 'prep2')
             st += [self._prep_stream, self._prep_stream2]
         return st
-
-    def _record_step(self, depth, feat, key, cur):
-        """Issue the step eagerly once more, with the library calls logged (``_lib.StepRecorder``) and every tensor it
-        allocates drawn from a memory pool of its own (the recorded pointers stay valid: the pool is kept)."""
-        rec = _lib.StepRecorder(self._step_streams(cur))
-        pool = torch.cuda.MemPool()
-        with torch.cuda.use_mem_pool(pool, self.device), rec:
-            out = self._step_eager(depth, feat, rec)
-        if not rec.ok or (self.index_prep_mode == 'per_step' and not (self.device_geometry and hasattr(self, '_calib_dev'))):
-            # a step with launches outside the recordable entry points — or the per-step index preparation with the
-            # calibration algebra on the HOST (torch CPU ops + uploads per step, which a replay would not repeat): keep
-            # issuing it call by call
-            self._one_call_ok = False
-            self.one_call_refused = rec.why or 'per-step calibration algebra on the host is issued call by call'
-            return out
-        compiled = rec.build()
-        # The recorder sees the library's calls only: a torch kernel issued inside the step (a ``zero_``, a ``copy_``, a
-        # hidden ``.contiguous()``) would be missing from the replay, silently (ADVICE round 5).  So the FIRST replay is held
-        # to the step that was just issued call by call, bit for bit, on the same inputs — one synchronisation, at record
-        # time only; a recording that does not reproduce itself is dropped and the step stays call by call.
-        flat = [t for t in self._flat_outputs(out)]
-        want = [t.clone() for t in flat]
-        compiled.run(*[st.cuda_stream for st in self._step_streams(cur)])
-        torch.cuda.synchronize(self.device)
-        if not all(torch.equal(a, b) for a, b in zip(flat, want)):
-            self._one_call_ok = False
-            self.one_call_refused = 'the first replay of the recorded step did not reproduce the step issued call by call'
-            return self._step_eager(depth, feat)
-        while len(self._compiled) >= 4:                    # (two phases x two input pairs, with room)
-            self._compiled.pop(next(iter(self._compiled)))
-        self._compiled[key] = (compiled, out, pool, _lib.workspace.generation(self.device))
-        return out
 
     @staticmethod
     def _flat_outputs(out):
@@ -811,10 +772,10 @@ class ShardedHotPath:
         from . import sharding
         self.cfg, self.device, self.rank, self.world = cfg, torch.device(device), rank, world
         # one_call: the rank's COMPUTE between the collectives — (poolings + renders) and (HOA-1/2) — is recorded once and
-        # replayed by one host call each (``_lib.StepRecorder``, as ``HotPath.step``): a rank of eight has ~ 0.1 ms of
+        # replayed by one host call each (``_lib.StepCache``, as ``HotPath.step``): a rank of eight has ~ 0.1 ms of
         # device work per step and would otherwise spend ~ 0.2 ms issuing its ~ 16 library calls through ctypes
-        self.one_call = bool(one_call) and self.device.type == 'cuda' and index_prep_mode == 'cached'
-        self._segments, self._segment_seen, self.one_call_refused = {}, {}, None
+        self._one_call = bool(one_call) and self.device.type == 'cuda' and index_prep_mode == 'cached'
+        self._segments = _lib.StepCache(self.device, size=16, seen_size=32)     # (four segments x two buffer sets, with room)
         X, Y, Z = cfg.bev_xyz
         C = cfg.channels
         self.n_frames = cfg.batch * cfg.n_frames
@@ -949,36 +910,22 @@ class ShardedHotPath:
             opacity_bev = full[:, self.planes_pool:self.planes_pool + 1]
         return full, rendered, gated, opacity_bev
 
+    @property
+    def one_call(self):
+        """The compute segments are replayed by one host call each (False once a recording was refused)."""
+        return self._one_call and self._segments.refused is None
+
+    @property
+    def one_call_refused(self):
+        return self._segments.refused
+
     def _segment(self, name, key, streams, fn):
         """``fn(rec)`` — library calls only, on ``streams`` (slot 0 = the caller's) — by ONE host call from the third time
-        ``key`` (the pointers it works on) is seen: first eagerly (plans and scratch are built), then recorded with its
-        allocations in a memory pool of its own, then replayed.  -> what ``fn`` returned (the same tensors every replay)."""
-        if not self.one_call or torch.cuda.is_current_stream_capturing():
+        ``key`` (the pointers it works on) is seen (``_lib.StepCache``; no first-replay check: the ``gate`` segment works
+        in place, so a second run is not comparable).  -> what ``fn`` returned (the same tensors every replay)."""
+        if not self._one_call:
             return fn(None)
-        hit = self._segments.get((name, key))
-        if hit is not None and hit[3] != _lib.workspace.generation(self.device):
-            del self._segments[(name, key)]          # a scratch buffer it baked in was replaced: record anew
-            hit = None
-        if hit is not None:
-            hit[0].run(*[st.cuda_stream for st in streams])
-            return hit[1]
-        if (name, key) not in self._segment_seen:
-            # (bounded: a caller that hands over NEW tensors every step never repeats a key — it runs call by call, and
-            # these tables must not grow with it)
-            if len(self._segment_seen) >= 32:
-                self._segment_seen.clear()
-            self._segment_seen[(name, key)] = True
-            return fn(None)
-        rec, pool = _lib.StepRecorder(streams), torch.cuda.MemPool()
-        with torch.cuda.use_mem_pool(pool, self.device), rec:
-            out = fn(rec)
-        if not rec.ok:
-            self.one_call, self.one_call_refused = False, rec.why
-            return out
-        while len(self._segments) >= 16:                    # (four segments x two buffer sets, with room)
-            self._segments.pop(next(iter(self._segments)))
-        self._segments[(name, key)] = (rec.build(), out, pool, _lib.workspace.generation(self.device))
-        return out
+        return self._segments((name, key), streams, fn)
 
     def _pool_and_render(self, inputs, target_of):
         cur = torch.cuda.current_stream(self.device) if self._side is not None else None

@@ -199,6 +199,39 @@ def test_step_recorder_encodes_arguments(monkeypatch):
     assert rec3.ok and rec3.items[0][3][fpos[0]] == struct.unpack('<I', struct.pack('<f', 1.5))[0]
 
 
+def test_a_recording_logs_exactly_the_entry_points_that_take_a_stream_last():
+    """While a step is recorded, ``lib()`` logs the calls of every entry point whose last parameter is an ocrf_stream_t
+    (it enqueues work) and passes every other one through — whatever its name says."""
+    text = _lib._header_text()
+    want = {name for name, params in re.findall(r'\b((?:ocrf_|bev_pool_v2)\w*)\s*\(([^()]*)\)\s*;', text)
+            if params.split(',')[-1].split()[:-1] == ['ocrf_stream_t']}
+    assert {'ocrf_hoa_height_gate_from_tiles', 'ocrf_diag_bev_pool_stamps', 'ocrf_rasterize_planned'} <= want
+    assert not {'ocrf_stream_create', 'ocrf_stream_destroy', 'ocrf_graph_node_census', 'ocrf_version'} & want
+
+    class Fn:
+        def __init__(self, argtypes):
+            self.argtypes, self.calls = argtypes, 0
+
+        def __call__(self, *args):
+            self.calls += 1
+            return 0
+    protos = _lib.prototypes()
+    fake = type('FakeLib', (), {})()
+    for name, (_, argtypes) in protos.items():
+        setattr(fake, name, Fn(argtypes))
+    _lib.lib()
+    rec = _lib.StepRecorder([])
+    recording = _lib._RecordingLib(fake, rec)
+    assert {name for name in protos if getattr(recording, name) is not getattr(fake, name)} == want
+
+    recording.ocrf_stream_create(None, 0, 0, None)               # passed through: not logged, the recording stays good
+    assert fake.ocrf_stream_create.calls == 1 and rec.names == [] and rec.ok
+    gate = fake.ocrf_hoa_height_gate_from_tiles
+    recording.ocrf_hoa_height_gate_from_tiles(*([0] * (len(gate.argtypes) - 1) + [None]))
+    assert gate.calls == 1 and rec.names == ['ocrf_hoa_height_gate_from_tiles']
+    assert not rec.ok and 'cannot be held' in rec.why
+
+
 def test_pooling_entry_points_refuse_operands_of_two_gib_at_the_c_boundary():
     """The tile / panel pooling kernels address features and output with 32-bit byte offsets (the reference indexes with
     int: bev_pool_cuda.cu:39-47).  ADVICE round 4 / VERDICT round 5: the refusal of 2 GiB operands lives in the C entry

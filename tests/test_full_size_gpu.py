@@ -260,7 +260,7 @@ def test_cfg2_step_options_give_the_same_outputs(cuda):
     one.step(d1, f1)                                   # issued call by call (builds plans and scratch)
     one.step(d1, f1)                                   # recorded (issued call by call once more, its library calls logged)
     one.step(d1, f1)                                   # replayed: one host call
-    assert one._compiled and next(iter(one._compiled.values()))[0].n_calls >= 7
+    assert one._compiled and next(iter(one._compiled.values())).step.n_calls >= 7
     # new values everywhere, same tensors: inputs of the poolings, of the renders, of HOA
     d2, f2 = ref_hp.make_inputs(seed=5)
     d1.copy_(d2), f1.copy_(f2)

@@ -31,7 +31,7 @@ for _ in range(30):
 for rep in range(3):
     for single in (0, 1):
         L.ocrf_tune_set(15, single)
-        hp._compiled.clear(), hp._warm_keys.clear()
+        hp._compiled.clear()
         for _ in range(10):
             hp.step(depth, feat)
         print('single pass' if single else 'two passes ', ' '.join('%.4f' % timed() for _ in range(5)), 'ms', flush=True)

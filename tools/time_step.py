@@ -52,7 +52,7 @@ t.disarm()
 in_step = float(np.median(t.read_ms())) * 1e3
 t.close()
 hp.overlap = False
-hp._compiled.clear(), hp._warm_keys.clear()
+hp._compiled.clear()
 for _ in range(6):
     step()
 t = _lib.KernelTimer(_lib.K_RASTER_BLEND_SORTED, 64)
