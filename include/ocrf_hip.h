@@ -498,7 +498,9 @@ int ocrf_render_losses_backward(int B, int K, int C, int H, int W, const float *
  *   cv_frustum's [0,0,:,0], [0,:,0,1], [:,0,0,2]); per camera the raw k2s_sensor (BN,4,4), intrins (BN,3,3),
  *   post_rots (BN,3,3) and post_trans (BN,3), contiguous.  The image size is (4 H, 4 W).  out (BN,D,H,W) NCHW:
  *   mode 0 the softmax over D of raw, mode 1 raw = -(cost + bias [warped channel 4 (C/4 - 1) == 0]).  The 3x3 inverses
- *   are taken in the kernel.  One launch, deterministic, no atomics.
+ *   are taken in the kernel.  One launch, deterministic, no atomics.  Limits: one camera's prev is addressed in unsigned
+ *   32-bit bytes, so C*H*W*sizeof(float) <= 2^32 - 1 (C = 256 allows H*W < 2^22), and D*H*W < 2^31; larger shapes
+ *   return hipErrorInvalidValue and launch nothing.
  */
 int ocrf_stereo_cost_volume(int BN, int C, int H, int W, int D, const float *prev, const float *curr,
                             const float *frustum_u, long long stride_u, const float *frustum_v, long long stride_v,

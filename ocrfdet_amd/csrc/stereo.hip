@@ -142,8 +142,8 @@ __device__ __forceinline__ void taps(float px, float py, int H, int W, unsigned*
   w[3] = (bx1 && by1) ? se : 0.0f;
 }
 
-__device__ __forceinline__ float ld(__amdgpu_buffer_rsrc_t rs, unsigned voff, int soff) {
-  return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (int)voff, soff, 0));
+__device__ __forceinline__ float ld(__amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned soff) {
+  return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (int)voff, (int)soff, 0));
 }
 
 __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3))) stereo_cost_volume_kernel(
@@ -162,13 +162,15 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3
   const int wc = live ? w : W - 1;
   const int HW = H * W;
   const int G = C >> 2, cb = 4 * (G - 1);
+  // one camera's prev is at most 2^32 - 1 bytes (host guard): its size and plane offsets in unsigned 32-bit bytes
+  const unsigned plane_bytes = (unsigned)HW * (unsigned)sizeof(float);
 
   Cam cm;
   load_cam(cam, k2s, intrins, post_rots, post_trans, &cm);
   const float wi1 = (float)(4 * W) - 1.0f, hi1 = (float)(4 * H) - 1.0f;
   const float u = fu[(long long)wc * su], v = fv[(long long)h * sv];
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(prev + (size_t)cam * C * HW), 0, C * HW * (int)sizeof(float), 0x00020000);
+      const_cast<float*>(prev + (size_t)cam * C * HW), 0, (int)((unsigned)C * plane_bytes), 0x00020000);
   const float* curr_px = curr + (size_t)cam * C * HW + (size_t)h * W + wc;
   float* out_px = out + (size_t)cam * D * HW + (size_t)h * W + wc;
 
@@ -195,7 +197,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3
       for (int cc = 0; cc < 4; ++cc) {
         const int c = 4 * g + cc;
         const float cur = curr_px[(size_t)c * HW];
-        const int plane = c * HW * (int)sizeof(float);
+        const unsigned plane = (unsigned)c * plane_bytes;
         float warp[kJ];
 #pragma unroll
         for (int j = 0; j < kJ; ++j) {
@@ -262,9 +264,11 @@ int ocrf_stereo_cost_volume(int BN, int C, int H, int W, int D, const float* pre
   if (!prev || !curr || !frustum_u || !frustum_v || !frustum_d || !k2s_sensor || !intrins || !post_rots ||
       !post_trans || !out)
     return (int)hipErrorInvalidValue;
-  // in-plane offsets are 32-bit; the per-camera and per-row block counts must fit the grid
+  // one camera's prev is addressed in unsigned 32-bit bytes (buffer size and plane offsets); out's planes and the
+  // per-row block counts must fit int
   const long long HW = (long long)H * W;
-  if ((long long)C * HW >= (1LL << 31) || (long long)D * HW >= (1LL << 31)) return (int)hipErrorInvalidValue;
+  if ((long long)C * HW * (long long)sizeof(float) > 0xFFFFFFFFLL || (long long)D * HW >= (1LL << 31))
+    return (int)hipErrorInvalidValue;
   const int per_row = (W + 63) / 64;
   const long long blocks = (long long)BN * H * per_row;
   if (blocks >= (1LL << 31)) return (int)hipErrorInvalidValue;

@@ -24,6 +24,7 @@ __all__ = ['BasicBlock', 'Mlp', 'SELayer', 'ASPP', '_ASPPModule', 'DepthNet', 's
            'stereo_cost_volume_torch', 'stereo_cost_volume_hip', 'stereo_grid_torch', 'supports']
 
 GROUP = 4                   # channels per group of the reference's loop (:580)
+PLANE_BYTES_MAX = 2 ** 32 - 1   # one camera's prev in bytes: the kernel addresses it in unsigned 32-bit
 
 
 # --------------------------------------------------------------------------------------------- building blocks
@@ -210,10 +211,13 @@ def stereo_cost_volume_hip(metas, bias, raw=False):
     frustum axes are passed as strided views of ``metas['frustum']``; the small calibration tensors are moved to the
     features' device if they are elsewhere."""
     prev, curr, D, H, W = _split(metas)
-    _lib.require_cuda(prev, curr)
     BN, C = curr.shape[:2]
     if C < GROUP or prev.shape[1] != C:
         raise ValueError(f'stereo features must have the same channel count >= {GROUP}: {prev.shape} vs {curr.shape}')
+    if C * H * W * 4 > PLANE_BYTES_MAX or D * H * W >= 2 ** 31:
+        raise ValueError(f'stereo cost volume: C * H * W * 4 = {C * H * W * 4} bytes per camera must be at most '
+                         f'2^32 - 1 (32-bit plane addressing) and D * H * W = {D * H * W} below 2^31')
+    _lib.require_cuda(prev, curr)
     dev = curr.device
     prev, curr = prev.detach().float().contiguous(), curr.detach().float().contiguous()
     cal = [metas[k].detach().to(dev, torch.float32).reshape(BN, -1).contiguous()

@@ -44,6 +44,16 @@ def metas(g, device='cpu'):
                 downsample=16, grid_config=None, cv_feat_list=[prev, curr])
 
 
+def near_lines(ix, iy, H, W, tol=AMBIGUOUS_PX):
+    """Bool, the shape of ``ix``: sample positions in feature pixels (any shape, float64) that reach the map and lie
+    within ``tol`` (a scalar or one value per sample) of a corner line, the map's border included."""
+    ix, iy = torch.as_tensor(ix, dtype=torch.float64), torch.as_tensor(iy, dtype=torch.float64)
+    tol = torch.as_tensor(tol, dtype=torch.float64)
+    near = lambda a: (a - a.round()).abs() < tol                   # noqa: E731
+    inside = (ix > -1 - tol) & (ix < W + tol) & (iy > -1 - tol) & (iy < H + tol)
+    return (near(ix) | near(iy)) & inside
+
+
 def ambiguity(grid, H, W, other=None, tol=AMBIGUOUS_PX):
     """(BN, D, H, W) bool: cells whose sample reaches the map and lies within ``tol`` feature pixels of a corner line
     (the map's border included), or whose behind-camera status differs between ``grid`` and ``other`` (same
@@ -52,9 +62,7 @@ def ambiguity(grid, H, W, other=None, tol=AMBIGUOUS_PX):
     BN = grid.shape[0]
     ix = (grid[..., 0] + 1) / 2 * (W - 1)
     iy = (grid[..., 1] + 1) / 2 * (H - 1)
-    near = lambda a: (a - a.round()).abs() < tol                   # noqa: E731
-    inside = (ix > -1 - tol) & (ix < W + tol) & (iy > -1 - tol) & (iy < H + tol)
-    amb = (near(ix) | near(iy)) & inside & (grid[..., 0] != -2)
+    amb = near_lines(ix, iy, H, W, tol) & (grid[..., 0] != -2)
     if other is not None:
         other = torch.as_tensor(other, dtype=torch.float64).reshape(grid.shape)
         amb |= (grid[..., 0] == -2) != (other[..., 0] == -2)
