@@ -591,6 +591,32 @@ int ocrf_center_decode(int B, int T, const int *ncls, int H, int W, const float 
                        int *labels, int *counts, void *workspace, size_t workspace_bytes, ocrf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Upsample + concatenate of the BEV encoder's neck (csrc/upsample_cat.hip): FPN_LSS.forward's
+ * x = cat([x2, up(x1)], 1) (mmdet3d/models/necks/lss_fpn.py:93-94) and up2[0] (:64-67): bilinear upsampling with
+ * align_corners=True and an integer factor, written into its channels of the concatenation.  Deterministic, no
+ * atomics, no workspace, no host reads.
+ *
+ * Sampling rule per axis, output index d of out = in * scale points: n = d (in - 1), i0 = n / (out - 1),
+ *   lambda = float(n % (out - 1)) / float(out - 1) (integer arithmetic, one rounding; in = 1: lambda = 0),
+ *   i1 = min(i0 + 1, in - 1); value (1 - ly) ((1 - lx) v00 + lx v01) + ly ((1 - lx) v10 + lx v11) in f32.  torch's
+ *   lambda comes from a float product and differs in its last bits.
+ *
+ * ocrf_upsample_cat_forward: x2 (B, C2, Hin*scale, Win*scale), x1 (B, C1, Hin, Win) f32 NCHW contiguous -> out
+ *   (B, C2 + C1, Hin*scale, Win*scale): channels [0, C2) a copy of x2, channels [C2, C2 + C1) the upsampled x1; every
+ *   element written once.  C2 = 0 with x2 = NULL: upsampling alone.  One launch; 16-byte accesses along the output
+ *   rows when the output plane is a multiple of 4 floats and out / x2 are 16-byte aligned, 4-byte accesses otherwise.
+ * ocrf_upsample_cat_backward: grad_out (B, C2 + C1, Hin*scale, Win*scale) -> grad_x1 (B, C1, Hin, Win), the transpose
+ *   of the upsampling as a gather per input pixel over the output pixels that read it (fixed order; every element
+ *   written).  One launch.  There is no grad_x2: it is grad_out[:, :C2].
+ * Limits: scale >= 1, (Hin + Win) * scale <= 8192, every operand below 2 GiB (the kernels index with int); anything
+ *   else returns hipErrorInvalidValue and launches nothing.
+ */
+int ocrf_upsample_cat_forward(int B, int C2, int C1, int Hin, int Win, int scale, const float *x2, const float *x1,
+                              float *out, ocrf_stream_t stream);
+int ocrf_upsample_cat_backward(int B, int C2, int C1, int Hin, int Win, int scale, const float *grad_out,
+                               float *grad_x1, ocrf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Index preparation of the two poolings on the device (csrc/index_prep.hip).
  *
  * ocrf_lss_prepare replaces get_lidar_coor + voxel_pooling_prepare_v2
@@ -986,7 +1012,9 @@ enum {
   OCRF_K_CD_SELECT = 98,         /* cd_select_kernel */
   OCRF_K_CD_MASK = 99,           /* cd_mask_kernel */
   OCRF_K_CD_SCAN = 100,          /* cd_scan_kernel */
-  OCRF_K_CD_WRITE = 101          /* cd_write_kernel */
+  OCRF_K_CD_WRITE = 101,         /* cd_write_kernel */
+  OCRF_K_UPSAMPLE_CAT = 102,     /* upsample_cat_kernel<V> */
+  OCRF_K_UPSAMPLE_CAT_BWD = 103  /* upsample_cat_backward_kernel */
 };
 const char *ocrf_kernel_name(int kernel_id);           /* symbol as rocprofv3 prints it */
 /* Diagnostic: a one-thread kernel that stores the device's constant-rate clock (wall_clock64, 100 MHz)

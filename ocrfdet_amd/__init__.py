@@ -12,6 +12,8 @@ Drop-in mirrors of the reference's Python surface for that path (and nothing els
   index preparation of view_transformer(_ocrf)    ocrfdet_amd.index_prep
   ...necks.view_transformer_ocrf                  ocrfdet_amd.view_transformer_ocrf (OcRFViewTransformerFull
                                                   and its sub-modules; kernels: ocrfdet_amd.neck_ops)
+  ...backbones.resnet.CustomResNet,               ocrfdet_amd.bev_encoder (CustomResNet, FPN_LSS, BEVEncoder,
+  ...necks.lss_fpn.FPN_LSS                        build_pre_process; kernel: upsample_cat)
   ==============================================  =================================================
 
 Every op calls the C ABI of ``csrc/libocrf_hip.so`` (``include/ocrf_hip.h``) through ctypes with

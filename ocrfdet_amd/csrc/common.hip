@@ -150,6 +150,8 @@ const char* ocrf_kernel_name(int kernel_id) {
     case OCRF_K_CD_MASK: return "cd_mask_kernel";
     case OCRF_K_CD_SCAN: return "cd_scan_kernel";
     case OCRF_K_CD_WRITE: return "cd_write_kernel";
+    case OCRF_K_UPSAMPLE_CAT: return "upsample_cat_kernel<*>";
+    case OCRF_K_UPSAMPLE_CAT_BWD: return "upsample_cat_backward_kernel";
     default: return "";
   }
 }
