@@ -617,6 +617,32 @@ int ocrf_upsample_cat_backward(int B, int C2, int C1, int Hin, int Win, int scal
                                float *grad_x1, ocrf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The memory-bound passes between the image encoder's convolutions (csrc/resnet_fuse.hip): the residual tail of a
+ * ResNet block and CustomFPN's top-down step (mmdet3d/models/necks/fpn.py:190-196), one launch each.  Deterministic, no
+ * atomics, no workspace, no host reads.  f32, contiguous; 16-byte accesses when every pointer is 16-byte aligned (and,
+ * for ocrf_upsample_add_forward, the destination plane a multiple of 4 floats), 4-byte accesses otherwise.
+ *
+ * ocrf_add_relu_forward: out[i] = relu(a[i] + b[i]), i in [0, n): one f32 addition rounded once, then
+ *   s < 0 ? 0 : s (torch's clamp_min: a NaN sum stays NaN).
+ * ocrf_add_relu_backward: grad[i] = out[i] <= 0 ? 0 : grad_out[i] (torch's threshold_backward: a NaN out passes the
+ *   gradient); the gradient of both addends.
+ * ocrf_upsample_add_forward: dst (B, C, Hout, Wout), src (B, C, Hin, Win) NCHW -> out = dst + nearest(src), every
+ *   element written once.  Index rule per axis, torch's mode='nearest' for destination index d:
+ *   i = min((int)floorf(d * ((float)in / (float)out)), in - 1).
+ * ocrf_upsample_add_backward: grad_out (B, C, Hout, Wout) -> grad_src (B, C, Hin, Win): per source pixel the sum of the
+ *   destination pixels that read it (one contiguous run per axis), rows ascending, columns ascending inside a row, into
+ *   one f32 accumulator; every element written.  There is no grad_dst: it is grad_out.
+ * Limits: n > 0; Hout >= Hin, Wout >= Win, Hout + Wout <= 8192; every operand below 2 GiB (the kernels index with int);
+ *   anything else returns hipErrorInvalidValue and launches nothing.
+ */
+int ocrf_add_relu_forward(long long n, const float *a, const float *b, float *out, ocrf_stream_t stream);
+int ocrf_add_relu_backward(long long n, const float *grad_out, const float *out, float *grad, ocrf_stream_t stream);
+int ocrf_upsample_add_forward(int B, int C, int Hin, int Win, int Hout, int Wout, const float *dst, const float *src,
+                              float *out, ocrf_stream_t stream);
+int ocrf_upsample_add_backward(int B, int C, int Hin, int Win, int Hout, int Wout, const float *grad_out,
+                               float *grad_src, ocrf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Index preparation of the two poolings on the device (csrc/index_prep.hip).
  *
  * ocrf_lss_prepare replaces get_lidar_coor + voxel_pooling_prepare_v2
@@ -1014,7 +1040,11 @@ enum {
   OCRF_K_CD_SCAN = 100,          /* cd_scan_kernel */
   OCRF_K_CD_WRITE = 101,         /* cd_write_kernel */
   OCRF_K_UPSAMPLE_CAT = 102,     /* upsample_cat_kernel<V> */
-  OCRF_K_UPSAMPLE_CAT_BWD = 103  /* upsample_cat_backward_kernel */
+  OCRF_K_UPSAMPLE_CAT_BWD = 103, /* upsample_cat_backward_kernel */
+  OCRF_K_ADD_RELU = 104,         /* binary_kernel<V, AddRelu> */
+  OCRF_K_ADD_RELU_BWD = 105,     /* binary_kernel<V, Threshold> */
+  OCRF_K_UPSAMPLE_ADD = 106,     /* upsample_add_kernel<V> */
+  OCRF_K_UPSAMPLE_ADD_BWD = 107  /* upsample_add_backward_kernel */
 };
 const char *ocrf_kernel_name(int kernel_id);           /* symbol as rocprofv3 prints it */
 /* Diagnostic: a one-thread kernel that stores the device's constant-rate clock (wall_clock64, 100 MHz)

@@ -14,6 +14,8 @@ Drop-in mirrors of the reference's Python surface for that path (and nothing els
                                                   and its sub-modules; kernels: ocrfdet_amd.neck_ops)
   ...backbones.resnet.CustomResNet,               ocrfdet_amd.bev_encoder (CustomResNet, FPN_LSS, BEVEncoder,
   ...necks.lss_fpn.FPN_LSS                        build_pre_process; kernel: upsample_cat)
+  mmdet ResNet, ...necks.fpn.CustomFPN,           ocrfdet_amd.image_encoder (ResNet, CustomFPN, ImageEncoder, also
+  BEVDet.image_encoder                            exported here; kernels: add_relu, upsample_add)
   ==============================================  =================================================
 
 Every op calls the C ABI of ``csrc/libocrf_hip.so`` (``include/ocrf_hip.h``) through ctypes with
@@ -22,3 +24,13 @@ raw device pointers; PyTorch is only the allocator / stream / ``torch.distribute
 from . import _lib  # noqa: F401
 
 __version__ = "0.1.0"
+_LAZY = ('ResNet', 'CustomFPN', 'ImageEncoder')
+
+
+def __getattr__(name):
+    """``ocrfdet_amd.ResNet`` / ``CustomFPN`` / ``ImageEncoder``: the classes of ``ocrfdet_amd.image_encoder``, imported
+    on first use.  There is no ``__all__``: ``from ocrfdet_amd import *`` yields what it yielded before."""
+    if name in _LAZY:
+        from . import image_encoder
+        return getattr(image_encoder, name)
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

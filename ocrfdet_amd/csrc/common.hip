@@ -152,6 +152,10 @@ const char* ocrf_kernel_name(int kernel_id) {
     case OCRF_K_CD_WRITE: return "cd_write_kernel";
     case OCRF_K_UPSAMPLE_CAT: return "upsample_cat_kernel<*>";
     case OCRF_K_UPSAMPLE_CAT_BWD: return "upsample_cat_backward_kernel";
+    case OCRF_K_ADD_RELU: return "binary_kernel<*, AddRelu>";
+    case OCRF_K_ADD_RELU_BWD: return "binary_kernel<*, Threshold>";
+    case OCRF_K_UPSAMPLE_ADD: return "upsample_add_kernel<*>";
+    case OCRF_K_UPSAMPLE_ADD_BWD: return "upsample_add_backward_kernel";
     default: return "";
   }
 }

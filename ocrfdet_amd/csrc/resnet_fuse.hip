@@ -1,0 +1,297 @@
+// The memory-bound passes between the image encoder's convolutions (ocrfdet_amd/image_encoder.py), each as ONE launch:
+//
+//   add_relu forward       out  = relu(a + b)                 the residual tail of every ResNet block
+//   add_relu backward      grad = out <= 0 ? 0 : grad_out     the gradient of both addends
+//   upsample_add forward   out  = dst + nearest(src)          CustomFPN's top-down step
+//                                                             (mmdet3d/models/necks/fpn.py:190-196)
+//   upsample_add backward  grad_src = the transpose of nearest() as a gather; the gradient of dst is grad_out itself
+//
+// No atomics, no workspace, no host synchronisation; repeated runs are bit-identical.  All four are HBM-bound: eager
+// torch makes two launches and five tensor passes of the tail (a + b -> t; t -> relu_ -> t), this file one launch and
+// three passes.
+//
+// Arithmetic.  a + b is one float32 addition, rounded once; the ReLU is `s < 0 ? 0 : s`, so that a NaN sum stays NaN
+// (torch's clamp_min) and -0 stays a zero.  The backward is torch's threshold_backward: `out <= 0 ? 0 : grad_out`, so
+// that a NaN `out` passes the gradient.  nearest() restates torch's mode='nearest', per axis, for destination index d of
+// `out` points over `in` source points:
+//   i = min((int)floorf(d * ((float)in / (float)out)), in - 1)
+// which is non-decreasing in d with steps of at most 1 for out >= in: the destinations of a source index form one
+// contiguous run, and every source index has one.
+//
+// Layout.  The element-wise kernels see their operands as flat runs of n floats cut into chunks of 256 threads x 4
+// groups x V floats: a workgroup takes chunks in a grid-stride loop (the grid is capped), a thread 4 groups of V
+// consecutive floats per chunk, 256 V floats apart, all loads of a chunk issued before its first store.  V = 4 when
+// every pointer is 16-byte aligned: a group is one 16-byte access, a wave touches 1 KiB contiguously, and the n % 4
+// floats behind the last whole group are handled by the first lanes of workgroup 0 with 4-byte accesses.  V = 1
+// otherwise (a view that starts off a 16-byte boundary): the same code with 4-byte accesses.
+// upsample_add forward cuts every (b, c) destination plane of Hout * Wout floats into such chunks, as
+// csrc/upsample_cat.hip does; V = 4 needs the plane size to be a multiple of 4 as well, and a group may straddle two
+// rows.  Both axes' source indices sit in LDS (Hout + Wout ints, built once per workgroup).  The source plane is
+// a quarter of the destination's or less and is read through L1 / L2: HBM sees it once.
+// upsample_add backward: one thread per source pixel, the lanes of a wave neighbouring pixels of a source row.  The
+// first destination of every source index sits in LDS (Hin + 1 + Win + 1 ints); a thread sums its run of rows, and
+// inside a row its run of columns, in ascending order into one float32 accumulator.  The lanes of a wave read
+// neighbouring runs of the same destination rows, so every fetched line is used in full.
+#include <hip/hip_runtime.h>
+
+#include "launch.h"
+#include "ocrf_hip.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kGroups = 4;                         // groups of V floats per thread and chunk
+constexpr int kMaxBlocks = 2048;                   // 8 workgroups per CU; the rest of the work is grid-strided
+constexpr int kMaxAxisSum = 8192;                  // Hout + Wout: the tables take 4 bytes per entry of LDS
+
+template <int V>
+struct Vec;
+template <>
+struct Vec<4> {
+  using type = float4;
+};
+template <>
+struct Vec<1> {
+  using type = float;
+};
+
+__device__ __forceinline__ float relu_of_sum(float a, float b) {
+  const float s = a + b;
+  return s < 0.0f ? 0.0f : s;                      // NaN < 0 is false: a NaN sum stays NaN
+}
+__device__ __forceinline__ float4 relu_of_sum(float4 a, float4 b) {
+  return make_float4(relu_of_sum(a.x, b.x), relu_of_sum(a.y, b.y), relu_of_sum(a.z, b.z), relu_of_sum(a.w, b.w));
+}
+__device__ __forceinline__ float threshold(float out, float g) {
+  return out <= 0.0f ? 0.0f : g;                   // NaN <= 0 is false: a NaN out passes the gradient
+}
+__device__ __forceinline__ float4 threshold(float4 o, float4 g) {
+  return make_float4(threshold(o.x, g.x), threshold(o.y, g.y), threshold(o.z, g.z), threshold(o.w, g.w));
+}
+
+struct AddRelu {
+  template <typename T>
+  __device__ __forceinline__ T operator()(T a, T b) const {
+    return relu_of_sum(a, b);
+  }
+};
+struct Threshold {                                 // (grad_out, out) -> grad
+  template <typename T>
+  __device__ __forceinline__ T operator()(T g, T o) const {
+    return threshold(o, g);
+  }
+};
+
+// out[i] = op(p[i], q[i]) for i in [0, n): groups = n / V whole groups, chunks of kThreads * kGroups of them
+template <int V, typename Op>
+__global__ void __launch_bounds__(kThreads) binary_kernel(int n, int groups, int chunks, const float* __restrict__ p,
+                                                           const float* __restrict__ q, float* __restrict__ out) {
+  using VT = typename Vec<V>::type;
+  const Op op;
+  const VT* pv = reinterpret_cast<const VT*>(p);
+  const VT* qv = reinterpret_cast<const VT*>(q);
+  VT* ov = reinterpret_cast<VT*>(out);
+  for (int c = blockIdx.x; c < chunks; c += gridDim.x) {
+    const int first = c * (kThreads * kGroups) + (int)threadIdx.x;
+    VT x[kGroups], y[kGroups];
+#pragma unroll
+    for (int g = 0; g < kGroups; ++g) {
+      const int idx = first + g * kThreads;
+      if (idx < groups) {
+        x[g] = pv[idx];
+        y[g] = qv[idx];
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < kGroups; ++g) {
+      const int idx = first + g * kThreads;
+      if (idx < groups) ov[idx] = op(x[g], y[g]);
+    }
+  }
+  if constexpr (V > 1) {                           // the n % V floats behind the last whole group
+    const int i = groups * V + (int)threadIdx.x;
+    if (blockIdx.x == 0 && i < n) out[i] = op(p[i], q[i]);
+  }
+}
+
+// torch's mode='nearest' source index of destination index d
+__device__ __forceinline__ int nearest_index(int d, int in, int out) {
+  const float scale = (float)in / (float)out;
+  return min((int)floorf((float)d * scale), in - 1);
+}
+
+template <int V>
+__global__ void __launch_bounds__(kThreads) upsample_add_kernel(int Hin, int Win, int Hout, int Wout, int chunks,
+                                                                 int units, const float* __restrict__ dst,
+                                                                 const float* __restrict__ src,
+                                                                 float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  int* tab_y = reinterpret_cast<int*>(lds_raw);    // [0, Hout): source row times Win; [Hout, Hout + Wout): source column
+  int* tab_x = tab_y + Hout;
+  for (int i = threadIdx.x; i < Hout + Wout; i += kThreads) {
+    tab_y[i] = i < Hout ? nearest_index(i, Hin, Hout) * Win : nearest_index(i - Hout, Win, Wout);
+  }
+  __syncthreads();
+  using VT = typename Vec<V>::type;
+  const int P = Hout * Wout, Pin = Hin * Win;
+  constexpr int kStep = kThreads * V;              // floats between a thread's groups
+  const int step_y = kStep / Wout, step_x = kStep - step_y * Wout;
+  for (int u = blockIdx.x; u < units; u += gridDim.x) {
+    const int plane = u / chunks, chunk = u - plane * chunks;
+    const int first = chunk * (kStep * kGroups) + (int)threadIdx.x * V;
+    const float* d = dst + (size_t)plane * P;
+    const float* s = src + (size_t)plane * Pin;
+    float* o = out + (size_t)plane * P;
+    int oy = first / Wout, ox = first - oy * Wout;
+#pragma unroll
+    for (int g = 0; g < kGroups; ++g) {
+      const int idx = first + g * kStep;
+      if (idx < P) {                               // P % V == 0: a group is inside the plane or outside it
+        const VT dv = *reinterpret_cast<const VT*>(d + idx);
+        float v[V];
+        int y = oy, x = ox;
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+          v[k] = s[tab_y[y] + tab_x[x]];
+          if (++x == Wout) {
+            x = 0;
+            ++y;                                   // past the last row only behind the group's last element
+          }
+        }
+        if constexpr (V == 4) {
+          *reinterpret_cast<float4*>(o + idx) = make_float4(dv.x + v[0], dv.y + v[1], dv.z + v[2], dv.w + v[3]);
+        } else {
+          o[idx] = dv + v[0];
+        }
+      }
+      oy += step_y;
+      ox += step_x;
+      if (ox >= Wout) {
+        ox -= Wout;
+        ++oy;
+      }
+    }
+  }
+}
+
+// start[i], i in [0, in]: the first destination index whose source index is >= i (start[in] = out), so that the
+// destinations of source index i are [start[i], start[i + 1])
+__device__ __forceinline__ void build_starts(int* start, int in, int out) {
+  for (int d = threadIdx.x; d <= out; d += kThreads) {
+    const int lo = d == 0 ? 0 : nearest_index(d - 1, in, out) + 1;
+    const int hi = d == out ? in : nearest_index(d, in, out);
+    for (int i = lo; i <= hi; ++i) start[i] = d;
+  }
+}
+
+__global__ void __launch_bounds__(kThreads) upsample_add_backward_kernel(int Hin, int Win, int Hout, int Wout,
+                                                                          int total,
+                                                                          const float* __restrict__ grad_out,
+                                                                          float* __restrict__ grad_src) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  int* start_y = reinterpret_cast<int*>(lds_raw);  // Hin + 1 entries
+  int* start_x = start_y + Hin + 1;                // Win + 1 entries
+  build_starts(start_y, Hin, Hout);
+  build_starts(start_x, Win, Wout);
+  __syncthreads();
+  const int P = Hout * Wout, Pin = Hin * Win;
+  for (int i = blockIdx.x * kThreads + (int)threadIdx.x; i < total; i += gridDim.x * kThreads) {
+    const int plane = i / Pin, pix = i - plane * Pin;
+    const int iy = pix / Win, ix = pix - iy * Win;
+    const float* g = grad_out + (size_t)plane * P;
+    const int y0 = start_y[iy], y1 = start_y[iy + 1], x0 = start_x[ix], x1 = start_x[ix + 1];
+    float acc = 0.0f;
+    for (int oy = y0; oy < y1; ++oy) {
+      const float* row = g + oy * Wout;
+      for (int ox = x0; ox < x1; ++ox) acc += row[ox];
+    }
+    grad_src[i] = acc;
+  }
+}
+
+constexpr long long kTwoGiB = 1LL << 31;
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+template <typename Op>
+int launch_binary(int kernel_id, long long n, const float* p, const float* q, float* out, ocrf_stream_t stream) {
+  // every operand below 2 GiB: the kernels index with int
+  if (n <= 0 || n * (long long)sizeof(float) >= kTwoGiB) return (int)hipErrorInvalidValue;
+  if (!p || !q || !out) return (int)hipErrorInvalidValue;
+  const bool vec = aligned16(p) && aligned16(q) && aligned16(out);
+  const int V = vec ? 4 : 1;
+  const int groups = (int)(n / V);
+  const int per_chunk = kThreads * kGroups;
+  const int chunks = (groups + per_chunk - 1) / per_chunk;         // 0 for n < 4 with V = 4: the tail lanes alone
+  const unsigned grid = (unsigned)(chunks < 1 ? 1 : chunks < kMaxBlocks ? chunks : kMaxBlocks);
+  if (vec) {
+    ocrf::launch(kernel_id, binary_kernel<4, Op>, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, (int)n, groups,
+                 chunks, p, q, out);
+  } else {
+    ocrf::launch(kernel_id, binary_kernel<1, Op>, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, (int)n, groups,
+                 chunks, p, q, out);
+  }
+  return (int)hipGetLastError();
+}
+
+// the shapes both upsample_add entry points accept; *P / *Pin: floats per destination / source plane
+bool shapes_ok(int B, int C, int Hin, int Win, int Hout, int Wout, long long* P, long long* Pin) {
+  if (B <= 0 || C <= 0 || Hin <= 0 || Win <= 0 || Hout < Hin || Wout < Win) return false;
+  if ((long long)Hout + Wout > kMaxAxisSum) return false;
+  *P = (long long)Hout * Wout;
+  *Pin = (long long)Hin * Win;
+  // every operand below 2 GiB (the kernels index with int): the destination-sized ones are the largest
+  const long long planes = (long long)B * C;
+  return planes < kTwoGiB && planes * *P * (long long)sizeof(float) < kTwoGiB;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ocrf_add_relu_forward(long long n, const float* a, const float* b, float* out, ocrf_stream_t stream) {
+  return launch_binary<AddRelu>(OCRF_K_ADD_RELU, n, a, b, out, stream);
+}
+
+int ocrf_add_relu_backward(long long n, const float* grad_out, const float* out, float* grad, ocrf_stream_t stream) {
+  return launch_binary<Threshold>(OCRF_K_ADD_RELU_BWD, n, grad_out, out, grad, stream);
+}
+
+int ocrf_upsample_add_forward(int B, int C, int Hin, int Win, int Hout, int Wout, const float* dst, const float* src,
+                              float* out, ocrf_stream_t stream) {
+  long long P, Pin;
+  if (!shapes_ok(B, C, Hin, Win, Hout, Wout, &P, &Pin)) return (int)hipErrorInvalidValue;
+  if (!dst || !src || !out) return (int)hipErrorInvalidValue;
+  const size_t lds = (size_t)(Hout + Wout) * sizeof(int);
+  const bool vec = P % 4 == 0 && aligned16(dst) && aligned16(out);
+  const int per_unit = kThreads * kGroups * (vec ? 4 : 1);
+  const int chunks = (int)((P + per_unit - 1) / per_unit);
+  const long long units = (long long)B * C * chunks;              // < 2^29 + B C
+  if (units >= kTwoGiB) return (int)hipErrorInvalidValue;
+  const unsigned grid = (unsigned)(units < kMaxBlocks ? units : kMaxBlocks);
+  if (vec) {
+    ocrf::launch(OCRF_K_UPSAMPLE_ADD, upsample_add_kernel<4>, dim3(grid), dim3(kThreads), lds, (hipStream_t)stream,
+                 Hin, Win, Hout, Wout, chunks, (int)units, dst, src, out);
+  } else {
+    ocrf::launch(OCRF_K_UPSAMPLE_ADD, upsample_add_kernel<1>, dim3(grid), dim3(kThreads), lds, (hipStream_t)stream,
+                 Hin, Win, Hout, Wout, chunks, (int)units, dst, src, out);
+  }
+  return (int)hipGetLastError();
+}
+
+int ocrf_upsample_add_backward(int B, int C, int Hin, int Win, int Hout, int Wout, const float* grad_out,
+                               float* grad_src, ocrf_stream_t stream) {
+  long long P, Pin;
+  if (!shapes_ok(B, C, Hin, Win, Hout, Wout, &P, &Pin)) return (int)hipErrorInvalidValue;
+  if (!grad_out || !grad_src) return (int)hipErrorInvalidValue;
+  // Hin <= Hout and Win <= Wout (shapes_ok), so this is at most (kMaxAxisSum + 2) ints: within the forward's LDS limit
+  const size_t lds = (size_t)(Hin + Win + 2) * sizeof(int);
+  const long long total = (long long)B * C * Pin;                 // <= B C P < 2^29
+  const long long blocks = (total + kThreads - 1) / kThreads;
+  const unsigned grid = (unsigned)(blocks < kMaxBlocks ? blocks : kMaxBlocks);
+  ocrf::launch(OCRF_K_UPSAMPLE_ADD_BWD, upsample_add_backward_kernel, dim3(grid), dim3(kThreads), lds,
+               (hipStream_t)stream, Hin, Win, Hout, Wout, (int)total, grad_out, grad_src);
+  return (int)hipGetLastError();
+}
+
+}  // extern "C"
