@@ -13,9 +13,13 @@ Drop-in mirrors of the reference's Python surface for that path (and nothing els
   ...necks.view_transformer_ocrf                  ocrfdet_amd.view_transformer_ocrf (OcRFViewTransformerFull
                                                   and its sub-modules; kernels: ocrfdet_amd.neck_ops)
   ...backbones.resnet.CustomResNet,               ocrfdet_amd.bev_encoder (CustomResNet, FPN_LSS, BEVEncoder,
-  ...necks.lss_fpn.FPN_LSS                        build_pre_process; kernel: upsample_cat)
+  ...necks.lss_fpn.FPN_LSS                        build_pre_process)
   mmdet ResNet, ...necks.fpn.CustomFPN,           ocrfdet_amd.image_encoder (ResNet, CustomFPN, ImageEncoder, also
-  BEVDet.image_encoder                            exported here; kernels: add_relu, upsample_add)
+  BEVDet.image_encoder                            exported here)
+  mmdet BasicBlock / Bottleneck, mmcv ConvModule, ocrfdet_amd.blocks (shared by the two encoders, depthnet and
+  build_norm_layer, kaiming_init                  center_head)
+  (the encoders' fused passes between             ocrfdet_amd.plane_ops (add_relu, upsample_add, upsample_cat;
+  convolutions)                                   re-exported by the encoder modules)
   ==============================================  =================================================
 
 Every op calls the C ABI of ``csrc/libocrf_hip.so`` (``include/ocrf_hip.h``) through ctypes with

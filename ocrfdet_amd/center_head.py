@@ -1,7 +1,7 @@
 """The detector's box head: the reference's ``CenterHead`` and ``SeparateHead`` (mmdet3d/models/dense_heads/
 centerpoint_head.py) with their constructor arguments, attribute names and ``state_dict`` keys, built without mmcv or
-mmdet.  ``ConvModule`` is restated as ``ConvBNReLU`` (mmcv's naming: ``conv`` / ``bn``, ``bias='auto'`` = no conv
-bias under BN).
+mmdet.  ``ConvBNReLU`` is ``blocks.ConvModule`` with a ReLU, for batch norms (mmcv's naming: ``conv`` / ``bn``,
+``bias='auto'`` = no conv bias under BN).
 
 The training path (``get_targets`` + ``loss``) has two formulations of the same arithmetic:
 
@@ -29,6 +29,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import center_decode as cd
+from .blocks import ConvModule, kaiming_init
 
 __all__ = ['ConvBNReLU', 'SeparateHead', 'DCNSeparateHead', 'CenterHead', 'HeatmapLoss', 'RegLoss', 'clip_sigmoid',
            'gaussian_focal_loss', 'targets_torch', 'heatmap_loss_torch', 'reg_loss_torch', 'pack_boxes', 'reduce_counts']
@@ -39,40 +40,17 @@ CLIP_INDEX = (0, 2, 3, 6, 8, 10)
 HEADS = ('reg', 'height', 'dim', 'rot', 'vel')
 
 
-class ConvBNReLU(nn.Module):
+class ConvBNReLU(ConvModule):
     """mmcv ``ConvModule(c_in, c_out, k, padding=..., norm_cfg=BN2d)``: conv (no bias under BN), ``bn``, ReLU."""
 
     def __init__(self, c_in, c_out, kernel_size, stride=1, padding=0, bias='auto', conv_cfg=None,
                  norm_cfg=dict(type='BN2d'), **kwargs):
-        super().__init__()
         if conv_cfg not in (None, dict(type='Conv2d')):
             raise NotImplementedError(f'conv_cfg {conv_cfg}: only Conv2d')
-        with_norm = norm_cfg is not None
-        if with_norm and norm_cfg.get('type') not in ('BN', 'BN2d'):
+        if norm_cfg is not None and norm_cfg.get('type') not in ('BN', 'BN2d'):
             raise NotImplementedError(f'norm_cfg {norm_cfg}: only BN2d')
-        self.conv = nn.Conv2d(c_in, c_out, kernel_size, stride=stride, padding=padding,
-                              bias=(not with_norm) if bias == 'auto' else bool(bias))
-        self.bn = nn.BatchNorm2d(c_out, eps=norm_cfg.get('eps', 1e-5), momentum=norm_cfg.get('momentum', 0.1)) \
-            if with_norm else None
-        self.activate = nn.ReLU(inplace=True)
-
-    def forward(self, x):
-        x = self.conv(x)
-        if self.bn is not None:
-            x = self.bn(x)
-        return self.activate(x)
-
-
-def _kaiming(module):
-    """mmcv's Kaiming init for Conv2d (fan_out, relu, normal, bias 0) and constant BN init (1, 0)."""
-    for m in module.modules():
-        if isinstance(m, nn.Conv2d):
-            nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
-            if m.bias is not None:
-                nn.init.zeros_(m.bias)
-        elif isinstance(m, nn.BatchNorm2d):
-            nn.init.ones_(m.weight)
-            nn.init.zeros_(m.bias)
+        super().__init__(c_in, c_out, kernel_size, stride=stride, padding=padding, bias=bias, conv_cfg=conv_cfg,
+                         norm_cfg=norm_cfg, act_cfg=dict(type='ReLU'), inplace=True)
 
 
 class SeparateHead(nn.Module):
@@ -95,7 +73,7 @@ class SeparateHead(nn.Module):
             self.__setattr__(head, nn.Sequential(*layers))
 
     def init_weights(self):
-        _kaiming(self)
+        kaiming_init(self)
         for head in self.heads:
             if head == 'heatmap':
                 self.__getattr__(head)[-1].bias.data.fill_(self.init_bias)
@@ -483,7 +461,7 @@ class CenterHead(nn.Module):
         self.register_buffer('_class_table', torch.tensor(table, dtype=torch.int32).view(-1, 2), persistent=False)
 
     def init_weights(self):
-        _kaiming(self.shared_conv)
+        kaiming_init(self.shared_conv)
         for h in self.task_heads:
             h.init_weights()
 

@@ -24,10 +24,9 @@
 // every pointer is 16-byte aligned: a group is one 16-byte access, a wave touches 1 KiB contiguously, and the n % 4
 // floats behind the last whole group are handled by the first lanes of workgroup 0 with 4-byte accesses.  V = 1
 // otherwise (a view that starts off a 16-byte boundary): the same code with 4-byte accesses.
-// upsample_add forward cuts every (b, c) destination plane of Hout * Wout floats into such chunks, as
-// csrc/upsample_cat.hip does; V = 4 needs the plane size to be a multiple of 4 as well, and a group may straddle two
-// rows.  Both axes' source indices sit in LDS (Hout + Wout ints, built once per workgroup).  The source plane is
-// a quarter of the destination's or less and is read through L1 / L2: HBM sees it once.
+// upsample_add forward walks every (b, c) destination plane of Hout * Wout floats as plane_walk.h describes.  Both
+// axes' source indices sit in LDS (Hout + Wout ints, built once per workgroup).  The source plane is a quarter of the
+// destination's or less and is read through L1 / L2: HBM sees it once.
 // upsample_add backward: one thread per source pixel, the lanes of a wave neighbouring pixels of a source row.  The
 // first destination of every source index sits in LDS (Hin + 1 + Win + 1 ints); a thread sums its run of rows, and
 // inside a row its run of columns, in ascending order into one float32 accumulator.  The lanes of a wave read
@@ -36,24 +35,15 @@
 
 #include "launch.h"
 #include "ocrf_hip.h"
+#include "plane_walk.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kGroups = 4;                         // groups of V floats per thread and chunk
-constexpr int kMaxBlocks = 2048;                   // 8 workgroups per CU; the rest of the work is grid-strided
-constexpr int kMaxAxisSum = 8192;                  // Hout + Wout: the tables take 4 bytes per entry of LDS
+using namespace plane;
 
-template <int V>
-struct Vec;
-template <>
-struct Vec<4> {
-  using type = float4;
-};
-template <>
-struct Vec<1> {
-  using type = float;
-};
+// The numbers of the layout comment above are plane_walk.h's, which the element-wise kernels use too:
+//   constexpr int kThreads = 256;  constexpr int kGroups = 4;  constexpr int kMaxBlocks = 2048;
+static_assert(kThreads == 256 && kGroups == 4 && kMaxBlocks == 2048, "the comments of this file state these values");
 
 __device__ __forceinline__ float relu_of_sum(float a, float b) {
   const float s = a + b;
@@ -134,43 +124,23 @@ __global__ void __launch_bounds__(kThreads) upsample_add_kernel(int Hin, int Win
   __syncthreads();
   using VT = typename Vec<V>::type;
   const int P = Hout * Wout, Pin = Hin * Win;
-  constexpr int kStep = kThreads * V;              // floats between a thread's groups
-  const int step_y = kStep / Wout, step_x = kStep - step_y * Wout;
+  const Walk<V> walk(Wout);
   for (int u = blockIdx.x; u < units; u += gridDim.x) {
     const int plane = u / chunks, chunk = u - plane * chunks;
-    const int first = chunk * (kStep * kGroups) + (int)threadIdx.x * V;
+    const int first = walk.first(chunk);
     const float* d = dst + (size_t)plane * P;
     const float* s = src + (size_t)plane * Pin;
     float* o = out + (size_t)plane * P;
-    int oy = first / Wout, ox = first - oy * Wout;
-#pragma unroll
-    for (int g = 0; g < kGroups; ++g) {
-      const int idx = first + g * kStep;
-      if (idx < P) {                               // P % V == 0: a group is inside the plane or outside it
-        const VT dv = *reinterpret_cast<const VT*>(d + idx);
-        float v[V];
-        int y = oy, x = ox;
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-          v[k] = s[tab_y[y] + tab_x[x]];
-          if (++x == Wout) {
-            x = 0;
-            ++y;                                   // past the last row only behind the group's last element
-          }
-        }
-        if constexpr (V == 4) {
-          *reinterpret_cast<float4*>(o + idx) = make_float4(dv.x + v[0], dv.y + v[1], dv.z + v[2], dv.w + v[3]);
-        } else {
-          o[idx] = dv + v[0];
-        }
+    walk.groups(first, P, [&](int idx, int y, int x) {
+      const VT dv = *reinterpret_cast<const VT*>(d + idx);
+      float v[V];
+      walk.values(v, y, x, [&](int yy, int xx) { return s[tab_y[yy] + tab_x[xx]]; });
+      if constexpr (V == 4) {
+        *reinterpret_cast<float4*>(o + idx) = make_float4(dv.x + v[0], dv.y + v[1], dv.z + v[2], dv.w + v[3]);
+      } else {
+        o[idx] = dv + v[0];
       }
-      oy += step_y;
-      ox += step_x;
-      if (ox >= Wout) {
-        ox -= Wout;
-        ++oy;
-      }
-    }
+    });
   }
 }
 
@@ -209,10 +179,6 @@ __global__ void __launch_bounds__(kThreads) upsample_add_backward_kernel(int Hin
   }
 }
 
-constexpr long long kTwoGiB = 1LL << 31;
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 template <typename Op>
 int launch_binary(int kernel_id, long long n, const float* p, const float* q, float* out, ocrf_stream_t stream) {
   // every operand below 2 GiB: the kernels index with int
@@ -223,7 +189,7 @@ int launch_binary(int kernel_id, long long n, const float* p, const float* q, fl
   const int groups = (int)(n / V);
   const int per_chunk = kThreads * kGroups;
   const int chunks = (groups + per_chunk - 1) / per_chunk;         // 0 for n < 4 with V = 4: the tail lanes alone
-  const unsigned grid = (unsigned)(chunks < 1 ? 1 : chunks < kMaxBlocks ? chunks : kMaxBlocks);
+  const unsigned grid = capped_grid(chunks < 1 ? 1 : chunks);
   if (vec) {
     ocrf::launch(kernel_id, binary_kernel<4, Op>, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, (int)n, groups,
                  chunks, p, q, out);
@@ -237,12 +203,10 @@ int launch_binary(int kernel_id, long long n, const float* p, const float* q, fl
 // the shapes both upsample_add entry points accept; *P / *Pin: floats per destination / source plane
 bool shapes_ok(int B, int C, int Hin, int Win, int Hout, int Wout, long long* P, long long* Pin) {
   if (B <= 0 || C <= 0 || Hin <= 0 || Win <= 0 || Hout < Hin || Wout < Win) return false;
-  if ((long long)Hout + Wout > kMaxAxisSum) return false;
+  if (!planes_ok((long long)B * C, Hout, Wout)) return false;
   *P = (long long)Hout * Wout;
   *Pin = (long long)Hin * Win;
-  // every operand below 2 GiB (the kernels index with int): the destination-sized ones are the largest
-  const long long planes = (long long)B * C;
-  return planes < kTwoGiB && planes * *P * (long long)sizeof(float) < kTwoGiB;
+  return true;
 }
 
 }  // namespace
@@ -264,17 +228,14 @@ int ocrf_upsample_add_forward(int B, int C, int Hin, int Win, int Hout, int Wout
   if (!dst || !src || !out) return (int)hipErrorInvalidValue;
   const size_t lds = (size_t)(Hout + Wout) * sizeof(int);
   const bool vec = P % 4 == 0 && aligned16(dst) && aligned16(out);
-  const int per_unit = kThreads * kGroups * (vec ? 4 : 1);
-  const int chunks = (int)((P + per_unit - 1) / per_unit);
-  const long long units = (long long)B * C * chunks;              // < 2^29 + B C
-  if (units >= kTwoGiB) return (int)hipErrorInvalidValue;
-  const unsigned grid = (unsigned)(units < kMaxBlocks ? units : kMaxBlocks);
+  const Units n = units_of((long long)B * C, P, vec);
+  if (n.units >= kTwoGiB) return (int)hipErrorInvalidValue;
   if (vec) {
-    ocrf::launch(OCRF_K_UPSAMPLE_ADD, upsample_add_kernel<4>, dim3(grid), dim3(kThreads), lds, (hipStream_t)stream,
-                 Hin, Win, Hout, Wout, chunks, (int)units, dst, src, out);
+    ocrf::launch(OCRF_K_UPSAMPLE_ADD, upsample_add_kernel<4>, dim3(n.grid), dim3(kThreads), lds, (hipStream_t)stream,
+                 Hin, Win, Hout, Wout, n.chunks, (int)n.units, dst, src, out);
   } else {
-    ocrf::launch(OCRF_K_UPSAMPLE_ADD, upsample_add_kernel<1>, dim3(grid), dim3(kThreads), lds, (hipStream_t)stream,
-                 Hin, Win, Hout, Wout, chunks, (int)units, dst, src, out);
+    ocrf::launch(OCRF_K_UPSAMPLE_ADD, upsample_add_kernel<1>, dim3(n.grid), dim3(kThreads), lds, (hipStream_t)stream,
+                 Hin, Win, Hout, Wout, n.chunks, (int)n.units, dst, src, out);
   }
   return (int)hipGetLastError();
 }
@@ -287,8 +248,7 @@ int ocrf_upsample_add_backward(int B, int C, int Hin, int Win, int Hout, int Wou
   // Hin <= Hout and Win <= Wout (shapes_ok), so this is at most (kMaxAxisSum + 2) ints: within the forward's LDS limit
   const size_t lds = (size_t)(Hin + Win + 2) * sizeof(int);
   const long long total = (long long)B * C * Pin;                 // <= B C P < 2^29
-  const long long blocks = (total + kThreads - 1) / kThreads;
-  const unsigned grid = (unsigned)(blocks < kMaxBlocks ? blocks : kMaxBlocks);
+  const unsigned grid = capped_grid((total + kThreads - 1) / kThreads);
   ocrf::launch(OCRF_K_UPSAMPLE_ADD_BWD, upsample_add_backward_kernel, dim3(grid), dim3(kThreads), lds,
                (hipStream_t)stream, Hin, Win, Hout, Wout, (int)total, grad_out, grad_src);
   return (int)hipGetLastError();

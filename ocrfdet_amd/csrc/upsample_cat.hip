@@ -12,13 +12,9 @@
 // in float32, each operation rounded once (the library is built with -ffp-contract=off).
 //
 // Layout.  Both kernels keep the (i0, lambda) pairs of the two axes in LDS (Hout + Wout entries of 8 bytes, built by
-// every workgroup at its start: two integer divisions per entry, once).  The forward sees each (b, c) output plane as a
-// flat run of Hout * Wout floats and cuts it into chunks of 4096: a workgroup of 256 threads takes (plane, chunk) units
-// in a grid-stride loop, a thread 4 groups of V consecutive floats per unit, 1024 floats apart.  V = 4 when the plane
-// size is a multiple of 4 and the pointers are 16-byte aligned (every even factor on torch's allocations): a group is
-// then one 16-byte store, a wave writes 1 KiB contiguously, and a group may straddle two output rows (the width need
-// not be a multiple of 4: the column wraps inside the group).  V = 1 otherwise: the same code with 4-byte accesses,
-// which is also what handles a plane whose size is no multiple of 4.  Copied channels are a 16-byte load and store.
+// every workgroup at its start: two integer divisions per entry, once).  The forward walks each (b, c) output plane as
+// plane_walk.h describes; V = 4 holds for every even factor on torch's allocations, and V = 1 is also what handles a
+// plane whose size is no multiple of 4.  Copied channels are a 16-byte load and store.
 // The x1 plane of a channel is Hin * Win floats (1 KiB at the reference's 16 x 16, 16 KiB at 64 x 64): the lanes of a
 // wave read neighbouring or equal addresses of two of its rows, served by L1 / L2; HBM sees every input once.
 // The backward's lanes are neighbouring input pixels of a row: at each step they read grad_out addresses `scale`
@@ -28,13 +24,11 @@
 
 #include "launch.h"
 #include "ocrf_hip.h"
+#include "plane_walk.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kGroups = 4;                         // groups of V floats per thread and unit
-constexpr int kMaxBlocks = 2048;                   // 8 workgroups per CU; the rest of the work is grid-strided
-constexpr int kMaxAxisSum = 8192;                  // Hout + Wout: the tables take 8 bytes per entry of 64 KiB LDS
+using namespace plane;
 
 struct Tap {
   int i0;
@@ -62,17 +56,6 @@ __device__ __forceinline__ void build_taps(Tap* tab, int Hin, int Win, int Hout,
 }
 
 template <int V>
-struct Vec;
-template <>
-struct Vec<4> {
-  using type = float4;
-};
-template <>
-struct Vec<1> {
-  using type = float;
-};
-
-template <int V>
 __global__ void __launch_bounds__(kThreads) upsample_cat_kernel(int C2, int C1, int Hin, int Win, int scale,
                                                                  int chunks, int units, const float* __restrict__ x2,
                                                                  const float* __restrict__ x1,
@@ -84,57 +67,39 @@ __global__ void __launch_bounds__(kThreads) upsample_cat_kernel(int C2, int C1, 
   build_taps(tab_y, Hin, Win, Hout, Wout);
   using VT = typename Vec<V>::type;
   const int P = Hout * Wout, Pin = Hin * Win, Ct = C2 + C1;
-  constexpr int kStep = kThreads * V;              // floats between a thread's groups
-  const int step_y = kStep / Wout, step_x = kStep - step_y * Wout;
+  const Walk<V> walk(Wout);
   for (int u = blockIdx.x; u < units; u += gridDim.x) {
     const int plane = u / chunks, chunk = u - plane * chunks;
     const int b = plane / Ct, c = plane - b * Ct;
-    const int first = chunk * (kStep * kGroups) + (int)threadIdx.x * V;
+    const int first = walk.first(chunk);
     float* o = out + (size_t)plane * P;
     if (c < C2) {                                  // uniform over the workgroup
       const float* s = x2 + ((size_t)b * C2 + c) * P;
 #pragma unroll
       for (int g = 0; g < kGroups; ++g) {
-        const int idx = first + g * kStep;
+        const int idx = first + g * walk.kStep;
         if (idx < P) *reinterpret_cast<VT*>(o + idx) = *reinterpret_cast<const VT*>(s + idx);
       }
       continue;
     }
     const float* s = x1 + ((size_t)b * C1 + (c - C2)) * Pin;
-    int oy = first / Wout, ox = first - oy * Wout;
-#pragma unroll
-    for (int g = 0; g < kGroups; ++g) {
-      const int idx = first + g * kStep;
-      if (idx < P) {                               // P % V == 0: a group is inside the plane or outside it
-        float v[V];
-        int y = oy, x = ox;
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-          const Tap ty = tab_y[y], tx = tab_x[x];
-          const int r0 = ty.i0 * Win, r1 = min(ty.i0 + 1, Hin - 1) * Win;
-          const int c0 = tx.i0, c1 = min(tx.i0 + 1, Win - 1);
-          const float v00 = s[r0 + c0], v01 = s[r0 + c1], v10 = s[r1 + c0], v11 = s[r1 + c1];
-          const float mx = 1.0f - tx.lam, my = 1.0f - ty.lam;
-          const float top = mx * v00 + tx.lam * v01, bot = mx * v10 + tx.lam * v11;
-          v[k] = my * top + ty.lam * bot;
-          if (++x == Wout) {
-            x = 0;
-            ++y;                                   // past the last row only behind the group's last element
-          }
-        }
-        if constexpr (V == 4) {
-          *reinterpret_cast<float4*>(o + idx) = make_float4(v[0], v[1], v[2], v[3]);
-        } else {
-          o[idx] = v[0];
-        }
+    walk.groups(first, P, [&](int idx, int y, int x) {
+      float v[V];
+      walk.values(v, y, x, [&](int yy, int xx) {
+        const Tap ty = tab_y[yy], tx = tab_x[xx];
+        const int r0 = ty.i0 * Win, r1 = min(ty.i0 + 1, Hin - 1) * Win;
+        const int c0 = tx.i0, c1 = min(tx.i0 + 1, Win - 1);
+        const float v00 = s[r0 + c0], v01 = s[r0 + c1], v10 = s[r1 + c0], v11 = s[r1 + c1];
+        const float mx = 1.0f - tx.lam, my = 1.0f - ty.lam;
+        const float top = mx * v00 + tx.lam * v01, bot = mx * v10 + tx.lam * v11;
+        return my * top + ty.lam * bot;
+      });
+      if constexpr (V == 4) {
+        *reinterpret_cast<float4*>(o + idx) = make_float4(v[0], v[1], v[2], v[3]);
+      } else {
+        o[idx] = v[0];
       }
-      oy += step_y;
-      ox += step_x;
-      if (ox >= Wout) {
-        ox -= Wout;
-        ++oy;
-      }
-    }
+    });
   }
 }
 
@@ -192,21 +157,15 @@ __global__ void __launch_bounds__(kThreads) upsample_cat_backward_kernel(int C2,
   }
 }
 
-constexpr long long kTwoGiB = 1LL << 31;
-
 // the shapes both entry points accept; *P / *Pin: floats per output / input plane
 bool shapes_ok(int B, int C2, int C1, int Hin, int Win, int scale, long long* P, long long* Pin) {
   if (B <= 0 || C2 < 0 || C1 <= 0 || Hin <= 0 || Win <= 0 || scale <= 0) return false;
   const long long Hout = (long long)Hin * scale, Wout = (long long)Win * scale;
-  if (Hout + Wout > kMaxAxisSum) return false;
+  if (!planes_ok((long long)B * (C2 + (long long)C1), Hout, Wout)) return false;   // out / grad_out are the largest
   *P = Hout * Wout;
   *Pin = (long long)Hin * Win;
-  // every operand below 2 GiB (the kernels index with int): out / grad_out are the largest of the five
-  const long long planes = (long long)B * (C2 + (long long)C1);
-  return planes < kTwoGiB && planes * *P * (long long)sizeof(float) < kTwoGiB;
+  return true;
 }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
 
@@ -219,17 +178,14 @@ int ocrf_upsample_cat_forward(int B, int C2, int C1, int Hin, int Win, int scale
   if (!x1 || !out || (C2 > 0 && !x2)) return (int)hipErrorInvalidValue;
   const size_t lds = (size_t)(Hin + Win) * scale * sizeof(Tap);
   const bool vec = P % 4 == 0 && aligned16(out) && (C2 == 0 || aligned16(x2));
-  const int per_unit = kThreads * kGroups * (vec ? 4 : 1);
-  const int chunks = (int)((P + per_unit - 1) / per_unit);
-  const long long units = (long long)B * (C2 + C1) * chunks;      // < 2^29 + B (C2 + C1)
-  if (units >= kTwoGiB) return (int)hipErrorInvalidValue;
-  const unsigned grid = (unsigned)(units < kMaxBlocks ? units : kMaxBlocks);
+  const Units n = units_of((long long)B * (C2 + C1), P, vec);
+  if (n.units >= kTwoGiB) return (int)hipErrorInvalidValue;
   if (vec) {
-    ocrf::launch(OCRF_K_UPSAMPLE_CAT, upsample_cat_kernel<4>, dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, C2,
-                 C1, Hin, Win, scale, chunks, (int)units, x2, x1, out);
+    ocrf::launch(OCRF_K_UPSAMPLE_CAT, upsample_cat_kernel<4>, dim3(n.grid), dim3(kThreads), lds, (hipStream_t)stream,
+                 C2, C1, Hin, Win, scale, n.chunks, (int)n.units, x2, x1, out);
   } else {
-    ocrf::launch(OCRF_K_UPSAMPLE_CAT, upsample_cat_kernel<1>, dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, C2,
-                 C1, Hin, Win, scale, chunks, (int)units, x2, x1, out);
+    ocrf::launch(OCRF_K_UPSAMPLE_CAT, upsample_cat_kernel<1>, dim3(n.grid), dim3(kThreads), lds, (hipStream_t)stream,
+                 C2, C1, Hin, Win, scale, n.chunks, (int)n.units, x2, x1, out);
   }
   return (int)hipGetLastError();
 }
@@ -241,8 +197,7 @@ int ocrf_upsample_cat_backward(int B, int C2, int C1, int Hin, int Win, int scal
   if (!grad_out || !grad_x1) return (int)hipErrorInvalidValue;
   const size_t lds = (size_t)(Hin + Win) * scale * sizeof(Tap);
   const long long total = (long long)B * C1 * Pin;                // < 2^29
-  const long long blocks = (total + kThreads - 1) / kThreads;
-  const unsigned grid = (unsigned)(blocks < kMaxBlocks ? blocks : kMaxBlocks);
+  const unsigned grid = capped_grid((total + kThreads - 1) / kThreads);
   ocrf::launch(OCRF_K_UPSAMPLE_CAT_BWD, upsample_cat_backward_kernel, dim3(grid), dim3(kThreads), lds,
                (hipStream_t)stream, C2, C1, Hin, Win, scale, (int)total, grad_out, grad_x1);
   return (int)hipGetLastError();

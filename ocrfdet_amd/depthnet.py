@@ -1,6 +1,6 @@
 """The stereo depth network of the neck: the reference's ``DepthNet`` (view_transformer.py:464-626) with its submodules
-``Mlp``, ``SELayer``, ``ASPP`` / ``_ASPPModule`` (:316-462) and mmdet 2.x's ``BasicBlock``, written from their structure
-with the same constructor arguments and the same ``state_dict`` keys and shapes.
+``Mlp``, ``SELayer``, ``ASPP`` / ``_ASPPModule`` (:316-462), written from their structure with the same constructor
+arguments and the same ``state_dict`` keys and shapes, and mmdet 2.x's ``BasicBlock`` from ``blocks.py``.
 
 The convolutions are stock PyTorch-ROCm layers (MIOpen).  The one operation that is not a convolution, the stereo cost
 volume (``gen_grid`` + ``calculate_cost_volumn``, :538-596), has two formulations of the same arithmetic:
@@ -19,6 +19,7 @@ from torch import nn
 from torch.utils.checkpoint import checkpoint
 
 from . import _lib
+from .blocks import BasicBlock, kaiming_init, unfuse_tails
 
 __all__ = ['BasicBlock', 'Mlp', 'SELayer', 'ASPP', '_ASPPModule', 'DepthNet', 'stereo_cost_volume',
            'stereo_cost_volume_torch', 'stereo_cost_volume_hip', 'stereo_grid_torch', 'supports']
@@ -28,34 +29,6 @@ PLANE_BYTES_MAX = 2 ** 32 - 1   # one camera's prev in bytes: the kernel address
 
 
 # --------------------------------------------------------------------------------------------- building blocks
-class BasicBlock(nn.Module):
-    """mmdet 2.x ``BasicBlock`` (expansion 1, pytorch style, BN): conv1 / bn1 / conv2 / bn2 / optional downsample."""
-    expansion = 1
-
-    def __init__(self, inplanes, planes, stride=1, dilation=1, downsample=None):
-        super().__init__()
-        self.conv1 = nn.Conv2d(inplanes, planes, 3, stride=stride, padding=dilation, dilation=dilation, bias=False)
-        self.bn1 = nn.BatchNorm2d(planes)
-        self.conv2 = nn.Conv2d(planes, planes, 3, padding=1, bias=False)
-        self.bn2 = nn.BatchNorm2d(planes)
-        self.relu = nn.ReLU(inplace=True)
-        self.downsample = downsample
-
-    def forward(self, x):
-        y = self.relu(self.bn1(self.conv1(x)))
-        y = self.bn2(self.conv2(y))
-        return self.relu(y + (x if self.downsample is None else self.downsample(x)))
-
-
-def _kaiming_init(module):
-    for m in module.modules():
-        if isinstance(m, nn.Conv2d):
-            nn.init.kaiming_normal_(m.weight)
-        elif isinstance(m, nn.BatchNorm2d):
-            nn.init.ones_(m.weight)
-            nn.init.zeros_(m.bias)
-
-
 class _ASPPModule(nn.Module):
     """Atrous conv (no bias) + BN + ReLU."""
 
@@ -65,7 +38,7 @@ class _ASPPModule(nn.Module):
                                      bias=False)
         self.bn = BatchNorm(planes)
         self.relu = nn.ReLU()
-        _kaiming_init(self)
+        kaiming_init(self, mode='fan_in')
 
     def forward(self, x):
         return self.relu(self.bn(self.atrous_conv(x)))
@@ -87,7 +60,7 @@ class ASPP(nn.Module):
         self.bn1 = BatchNorm(inplanes)
         self.relu = nn.ReLU()
         self.dropout = nn.Dropout(0.5)
-        _kaiming_init(self)
+        kaiming_init(self, mode='fan_in')
 
     def forward(self, x):
         branches = [self.aspp1(x), self.aspp2(x), self.aspp3(x), self.aspp4(x)]
@@ -277,6 +250,9 @@ class DepthNet(nn.Module):
             layers.append(ASPP(mid_channels, mid_channels if aspp_mid_channels < 0 else aspp_mid_channels))
         layers.append(nn.Conv2d(mid_channels, depth_channels, 1, stride=1, padding=0))
         self.depth_conv = nn.Sequential(*layers)
+        # off because the tail is unmeasured at these shapes; flipping it is a separate change with its own
+        # tools/time_bev_encoder.py row
+        unfuse_tails(self.depth_conv)
         self.with_cp = with_cp
         self.depth_channels = depth_channels
         # the stereo cost volume by ocrf_stereo_cost_volume for CUDA float32 features; False: its torch formulation

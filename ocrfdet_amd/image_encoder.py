@@ -5,249 +5,39 @@
 neck's 256-channel input and the stereo feature of ``DepthNet`` inside this package.
 
 ``ResNet`` restates mmdet 2.x for the arguments the reference passes and close neighbours: constructor keywords,
-attribute names and the torchvision ``state_dict`` layout (what ``pretrained='torchvision://resnet50'`` loads).  mmdet is
-not part of the reference tree, so the restatement could not be checked against it; ``tests/resnet_oracle.py`` is an
-independent float64 evaluation from the ``state_dict`` alone.  Deliberate deviations:
+attribute names and the torchvision ``state_dict`` layout (what ``pretrained='torchvision://resnet50'`` loads).  Its
+residual blocks and ``CustomFPN``'s ``ConvModule`` are those of ``blocks.py``.  Deliberate deviations:
 
 * no checkpoint is ever fetched: ``pretrained`` and ``init_cfg`` are stored and otherwise ignored; loading weights is the
   caller's ``load_state_dict``;
-* ``with_cp=True`` checkpoints the whole block (tail included) in the non-reentrant form, the rule ``CustomResNet`` and
-  ``DepthNet`` follow; the values are the same;
 * ``deep_stem``, ``avg_down``, ``dcn``, ``plugins``, a ``conv_cfg`` other than ``Conv2d`` and norms other than the batch
   norms raise ``NotImplementedError``;
 * ``CustomFPN``'s top-down step returns a new tensor instead of adding in place; ``ConvModule``'s activations are
   ``ReLU`` / ``LeakyReLU`` / ``Sigmoid`` / ``Tanh`` / ``GELU``; ``init_weights()`` is the reference's ``init_cfg``
   (Xavier-uniform on the ``Conv2d``s) and, as in mmcv, is the caller's to invoke.
 
-The convolutions stay with MIOpen.  What is fused are the memory-bound passes between them (``csrc/resnet_fuse.hip``):
-
-* ``add_relu(a, b)``: the residual tail ``relu(out + identity)`` of every block, one launch and three tensor passes
-  instead of two launches and five; the backward is one launch whose result is the gradient of both addends;
-* ``upsample_add(dst, src, size | scale_factor)``: ``CustomFPN``'s ``laterals[i - 1] += F.interpolate(laterals[i])`` in
-  mode ``nearest``, one launch instead of two; the backward is one gather launch, and the gradient of ``dst`` is
-  ``grad_out`` itself.
-
-Both are bit-equal to ``add_relu_torch`` / ``upsample_add_torch`` forward.  CUDA float32 contiguous tensors of equal
-shape (``add_relu``) or with matching B and C and a target no smaller than the source (``upsample_add``) take the
-kernels while ``ResNet.fused_tail`` / ``CustomFPN.fused_merge`` is True; everything else (the CPU, other dtypes,
-non-contiguous maps, other interpolation modes) takes the torch formulation.  The two functions themselves never fall
-back: they raise on an input the kernels do not take.
+The convolutions stay with MIOpen.  What is fused are the memory-bound passes between them, ``add_relu`` (the residual
+tail of every block) and ``upsample_add`` (``CustomFPN``'s top-down step), both of ``plane_ops.py`` and re-exported
+here.  CUDA float32 contiguous tensors of equal shape (``add_relu``) or with matching B and C and a target no smaller
+than the source (``upsample_add``) take the kernels while ``ResNet.fused_tail`` / ``CustomFPN.fused_merge`` is True;
+everything else (the CPU, other dtypes, non-contiguous maps, other interpolation modes) takes the torch formulation.
 """
-import torch
 import torch.nn.functional as F
 from torch import nn
 from torch.nn.modules.batchnorm import _BatchNorm
-from torch.utils.checkpoint import checkpoint
 
-from . import _lib
-from .bev_encoder import _build, _norm
-
-# Defaults of the two dispatch flags, from the measurement in profiles/image_encoder_time.txt (tools/time_image_encoder.py;
-# INTEGRATION 3f has the table): by device time each op is faster than its torch formulation at the reference shapes,
-# forward and forward + backward, at 12 and at 48 images (tail 1.07x to 1.65x, merge 2.0x to 2.4x), and the whole encoder
-# with both flags on is the fastest of the four flag pairs in eval and in training (1.02x to 1.09x of the unfused one).
-FUSED_TAIL_DEFAULT = True
-FUSED_MERGE_DEFAULT = True
-
-
-# ------------------------------------------------------------------------------------------------ add + relu
-def add_relu_torch(a, b):
-    """``relu(a + b)``: the residual tail as eager torch runs it."""
-    return torch.relu_(a + b)
-
-
-def _plain(t):
-    return t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
-
-
-def _add_relu_fusable(a, b):
-    return _plain(a) and _plain(b) and a.shape == b.shape and a.device == b.device and a.numel() > 0
-
-
-class _AddRelu(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, a, b):
-        out = torch.empty_like(a)
-        _lib.launch('ocrf_add_relu_forward', a.device, a.numel(), a, b, out)
-        ctx.save_for_backward(out)
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        out, = ctx.saved_tensors
-        grad_out = grad_out.contiguous()
-        grad = torch.empty_like(out)
-        _lib.launch('ocrf_add_relu_backward', out.device, out.numel(), grad_out, out, grad)
-        return grad, grad
-
-
-def add_relu(a, b):
-    """``add_relu_torch`` as one HIP launch (``ocrf_add_relu_forward`` / ``_backward``).  CUDA float32 contiguous
-    tensors of equal shape only: anything else raises (the blocks dispatch)."""
-    _lib.require_cuda(a, b)
-    if not _add_relu_fusable(a, b):
-        raise _lib.OcrfHipError('add_relu takes two non-empty contiguous float32 tensors of equal shape on one device')
-    return _AddRelu.apply(a, b)
-
-
-# ------------------------------------------------------------------------------------------------ upsample + add
-def upsample_add_torch(dst, src, size=None, scale_factor=None, mode='nearest', **kwargs):
-    """``dst + F.interpolate(src, size=size | scale_factor=scale_factor, mode=mode)``."""
-    if scale_factor is not None:
-        return dst + F.interpolate(src, scale_factor=scale_factor, mode=mode, **kwargs)
-    return dst + F.interpolate(src, size=size, mode=mode, **kwargs)
-
-
-def _target(src, size, scale_factor):
-    """(Hout, Wout) of ``F.interpolate(src, size | scale_factor)`` where the kernel's index rule is torch's: a ``size``,
-    or an integer ``scale_factor`` (torch then scales by 1 / factor, which is in / out rounded once).  Else None."""
-    if (size is None) == (scale_factor is None) or src.dim() != 4:
-        return None
-    if size is not None:
-        size = (size, size) if isinstance(size, int) else tuple(size)
-        return (int(size[0]), int(size[1])) if len(size) == 2 else None
-    if isinstance(scale_factor, (tuple, list)):
-        if len(scale_factor) != 2 or scale_factor[0] != scale_factor[1]:
-            return None
-        scale_factor = scale_factor[0]
-    if not isinstance(scale_factor, (int, float)) or scale_factor != int(scale_factor) or scale_factor < 1:
-        return None
-    return src.shape[2] * int(scale_factor), src.shape[3] * int(scale_factor)
-
-
-def _upsample_add_fusable(dst, src, size, scale_factor):
-    if not (_plain(dst) and _plain(src) and dst.dim() == 4 and src.dim() == 4 and dst.device == src.device):
-        return False
-    hw = _target(src, size, scale_factor)
-    return (hw is not None and dst.numel() > 0 and src.numel() > 0 and dst.shape[:2] == src.shape[:2]
-            and tuple(dst.shape[2:]) == hw and hw[0] >= src.shape[2] and hw[1] >= src.shape[3])
-
-
-class _UpsampleAdd(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, dst, src):
-        B, C, Hout, Wout = dst.shape
-        Hin, Win = src.shape[2:]
-        out = torch.empty_like(dst)
-        _lib.launch('ocrf_upsample_add_forward', dst.device, B, C, Hin, Win, Hout, Wout, dst, src, out)
-        ctx.shape = (B, C, Hin, Win, Hout, Wout)
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        B, C, Hin, Win, Hout, Wout = ctx.shape
-        grad_src = None
-        if ctx.needs_input_grad[1]:
-            g = grad_out.contiguous()
-            grad_src = torch.empty(B, C, Hin, Win, dtype=torch.float32, device=g.device)
-            _lib.launch('ocrf_upsample_add_backward', g.device, B, C, Hin, Win, Hout, Wout, g, grad_src)
-        return (grad_out if ctx.needs_input_grad[0] else None), grad_src
-
-
-def upsample_add(dst, src, size=None, scale_factor=None):
-    """``upsample_add_torch`` in mode ``nearest`` as one HIP launch (``ocrf_upsample_add_forward`` / ``_backward``):
-    ``src`` (B, C, Hin, Win) upsampled to the size of ``dst`` (B, C, Hout, Wout) and added to it; ``size`` must be that
-    of ``dst``, or ``scale_factor`` an integer with ``Hout = Hin * scale_factor``.  CUDA float32 contiguous tensors
-    only: anything else raises (``CustomFPN`` dispatches)."""
-    _lib.require_cuda(dst, src)
-    if not _upsample_add_fusable(dst, src, size, scale_factor):
-        raise _lib.OcrfHipError('upsample_add takes contiguous float32 NCHW tensors with the same B and C, dst of the '
-                                'target size and no smaller than src, and either size or an integer scale_factor')
-    return _UpsampleAdd.apply(dst, src)
+from .blocks import BasicBlock, Bottleneck, ConvModule, _Block, build, build_norm, kaiming_init
+from .plane_ops import (FUSED_MERGE_DEFAULT, FUSED_TAIL_DEFAULT, add_relu, add_relu_torch,  # noqa: F401 (re-exported)
+                        upsample_add, upsample_add_fusable, upsample_add_torch)
 
 
 # ------------------------------------------------------------------------------------------------ ResNet
-class _Block(nn.Module):
-    """What the two mmdet 2.x blocks share: the ``norm{i}`` properties, checkpointing and the residual tail."""
-    fused_tail = FUSED_TAIL_DEFAULT
-    with_cp = False
-
-    def _tail(self, out, identity):
-        if self.fused_tail and _add_relu_fusable(out, identity):
-            return add_relu(out, identity)
-        return add_relu_torch(out, identity)
-
-    def forward(self, x):
-        if self.with_cp and x.requires_grad:
-            return checkpoint(self._forward, x, use_reentrant=False)
-        return self._forward(x)
-
-    @property
-    def norm1(self):
-        return self.bn1
-
-    @property
-    def norm2(self):
-        return self.bn2
-
-
-class BasicBlock(_Block):
-    expansion = 1
-
-    def __init__(self, inplanes, planes, stride=1, dilation=1, downsample=None, style='pytorch', with_cp=False,
-                 norm_cfg=dict(type='BN')):
-        super().__init__()
-        self.conv1 = nn.Conv2d(inplanes, planes, 3, stride=stride, padding=dilation, dilation=dilation, bias=False)
-        self.bn1 = _norm(norm_cfg, planes)
-        self.conv2 = nn.Conv2d(planes, planes, 3, padding=1, bias=False)
-        self.bn2 = _norm(norm_cfg, planes)
-        self.relu = nn.ReLU(inplace=True)
-        self.downsample = downsample
-        self.stride, self.dilation, self.with_cp = stride, dilation, with_cp
-
-    @property
-    def last_norm(self):
-        return self.bn2
-
-    def _forward(self, x):
-        identity = x if self.downsample is None else self.downsample(x)
-        out = self.relu(self.bn1(self.conv1(x)))
-        out = self.bn2(self.conv2(out))
-        return self._tail(out, identity)
-
-
-class Bottleneck(_Block):
-    expansion = 4
-
-    def __init__(self, inplanes, planes, stride=1, dilation=1, downsample=None, style='pytorch', with_cp=False,
-                 norm_cfg=dict(type='BN')):
-        super().__init__()
-        assert style in ('pytorch', 'caffe')
-        # 'pytorch': the 3 x 3 convolution carries the stride; 'caffe': the first 1 x 1
-        self.conv1_stride, self.conv2_stride = (1, stride) if style == 'pytorch' else (stride, 1)
-        self.conv1 = nn.Conv2d(inplanes, planes, 1, stride=self.conv1_stride, bias=False)
-        self.bn1 = _norm(norm_cfg, planes)
-        self.conv2 = nn.Conv2d(planes, planes, 3, stride=self.conv2_stride, padding=dilation, dilation=dilation,
-                               bias=False)
-        self.bn2 = _norm(norm_cfg, planes)
-        self.conv3 = nn.Conv2d(planes, planes * self.expansion, 1, bias=False)
-        self.bn3 = _norm(norm_cfg, planes * self.expansion)
-        self.relu = nn.ReLU(inplace=True)
-        self.downsample = downsample
-        self.stride, self.dilation, self.style, self.with_cp = stride, dilation, style, with_cp
-
-    @property
-    def norm3(self):
-        return self.bn3
-
-    @property
-    def last_norm(self):
-        return self.bn3
-
-    def _forward(self, x):
-        identity = x if self.downsample is None else self.downsample(x)
-        out = self.relu(self.bn1(self.conv1(x)))
-        out = self.relu(self.bn2(self.conv2(out)))
-        out = self.bn3(self.conv3(out))
-        return self._tail(out, identity)
-
-
 def _res_layer(block, inplanes, planes, num_blocks, stride, dilation, style, with_cp, norm_cfg):
     """mmdet 2.x ``ResLayer`` without ``avg_down``: the first block carries the stride and the downsample."""
     downsample = None
     if stride != 1 or inplanes != planes * block.expansion:
         downsample = nn.Sequential(nn.Conv2d(inplanes, planes * block.expansion, 1, stride=stride, bias=False),
-                                   _norm(norm_cfg, planes * block.expansion))
+                                   build_norm(norm_cfg, planes * block.expansion))
     kw = dict(dilation=dilation, style=style, with_cp=with_cp, norm_cfg=norm_cfg)
     layers = [block(inplanes, planes, stride=stride, downsample=downsample, **kw)]
     layers += [block(planes * block.expansion, planes, stride=1, **kw) for _ in range(1, num_blocks)]
@@ -291,7 +81,7 @@ class ResNet(nn.Module):
 
         self.conv1 = nn.Conv2d(in_channels, stem_channels, 7, stride=2, padding=3, bias=False)
         self.norm1_name = 'bn1'
-        self.bn1 = _norm(norm_cfg, stem_channels)
+        self.bn1 = build_norm(norm_cfg, stem_channels)
         self.relu = nn.ReLU(inplace=True)
         self.maxpool = nn.MaxPool2d(kernel_size=3, stride=2, padding=1)
         self.res_layers, inplanes = [], stem_channels
@@ -335,14 +125,7 @@ class ResNet(nn.Module):
     def init_weights(self):
         """mmcv's ``kaiming_init`` (fan_out, relu, normal) on the convolutions, (1, 0) on the norms and, with
         ``zero_init_residual``, 0 on the last norm of every block.  Fetches nothing."""
-        for m in self.modules():
-            if isinstance(m, nn.Conv2d):
-                nn.init.kaiming_normal_(m.weight, a=0, mode='fan_out', nonlinearity='relu')
-                if m.bias is not None:
-                    nn.init.constant_(m.bias, 0)
-            elif isinstance(m, (_BatchNorm, nn.GroupNorm)):
-                nn.init.constant_(m.weight, 1)
-                nn.init.constant_(m.bias, 0)
+        kaiming_init(self, mode='fan_out')
         if self.zero_init_residual:
             for m in self.modules():
                 if isinstance(m, _Block):
@@ -368,41 +151,6 @@ class ResNet(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------ CustomFPN
-_ACTIVATIONS = dict(ReLU=nn.ReLU, LeakyReLU=nn.LeakyReLU, Sigmoid=nn.Sigmoid, Tanh=nn.Tanh, GELU=nn.GELU)
-
-
-class ConvModule(nn.Module):
-    """mmcv ``ConvModule`` in its default order conv -> norm -> act for what ``CustomFPN`` passes: ``conv`` has a bias
-    exactly when there is no norm (``bias='auto'``); the norm is ``bn``, the activation ``activate``."""
-
-    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, conv_cfg=None, norm_cfg=None,
-                 act_cfg=None, inplace=True):
-        super().__init__()
-        if conv_cfg is not None and conv_cfg.get('type', 'Conv2d') not in (None, 'Conv2d', 'Conv'):
-            raise NotImplementedError(f'conv_cfg {conv_cfg}: only Conv2d')
-        self.with_norm, self.with_activation = norm_cfg is not None, act_cfg is not None
-        self.conv = nn.Conv2d(in_channels, out_channels, kernel_size, stride=stride, padding=padding,
-                              bias=not self.with_norm)
-        if self.with_norm:
-            self.bn = _norm(norm_cfg, out_channels)
-        if self.with_activation:
-            cfg = dict(act_cfg)
-            kind = cfg.pop('type', None)
-            if kind not in _ACTIVATIONS:
-                raise NotImplementedError(f'act_cfg {act_cfg}: only {sorted(_ACTIVATIONS)}')
-            if kind in ('ReLU', 'LeakyReLU'):
-                cfg.setdefault('inplace', inplace)
-            self.activate = _ACTIVATIONS[kind](**cfg)
-
-    def forward(self, x):
-        x = self.conv(x)
-        if self.with_norm:
-            x = self.bn(x)
-        if self.with_activation:
-            x = self.activate(x)
-        return x
-
-
 class CustomFPN(nn.Module):
     def __init__(self, in_channels, out_channels, num_outs, start_level=0, end_level=-1, out_ids=[],
                  add_extra_convs=False, relu_before_extra_convs=False, no_norm_on_lateral=False, conv_cfg=None,
@@ -460,7 +208,7 @@ class CustomFPN(nn.Module):
             cfg['size'] = tuple(dst.shape[2:])
         if self.fused_merge and set(cfg) <= {'mode', 'size', 'scale_factor'} and cfg.get('mode', 'nearest') == 'nearest':
             size, scale = cfg.get('size'), cfg.get('scale_factor')
-            if _upsample_add_fusable(dst, src, size, scale):
+            if upsample_add_fusable(dst, src, size, scale):
                 return upsample_add(dst, src, size=size, scale_factor=scale)
         return upsample_add_torch(dst, src, **cfg)
 
@@ -496,9 +244,9 @@ class ImageEncoder(nn.Module):
 
     def __init__(self, img_backbone, img_neck=None):
         super().__init__()
-        self.img_backbone = _build(img_backbone, 'ResNet', ResNet)
+        self.img_backbone = build(img_backbone, 'ResNet', ResNet)
         if img_neck is not None:
-            self.img_neck = _build(img_neck, 'CustomFPN', CustomFPN)
+            self.img_neck = build(img_neck, 'CustomFPN', CustomFPN)
 
     @property
     def with_img_neck(self):

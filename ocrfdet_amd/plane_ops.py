@@ -1,0 +1,189 @@
+"""The three fused passes over (B, C, H, W) planes between the encoders' convolutions, each with its torch formulation:
+
+* ``add_relu(a, b)``: the residual tail ``relu(out + identity)`` of a block, one launch and three tensor passes
+  instead of two launches and five; the backward is one launch whose result is the gradient of both addends;
+* ``upsample_add(dst, src, size | scale_factor)``: ``CustomFPN``'s ``laterals[i - 1] += F.interpolate(laterals[i])`` in
+  mode ``nearest``, one launch instead of two; the backward is one gather launch, and the gradient of ``dst`` is
+  ``grad_out`` itself;
+* ``upsample_cat(x2, x1, scale)``: ``FPN_LSS``'s ``cat([x2, up(x1)], 1)`` and ``up2[0]``, bilinear upsampling with
+  ``align_corners=True`` by an integer factor written straight into its channels of the concatenation; the backward is
+  one gather launch without atomics.
+
+The first two (``csrc/resnet_fuse.hip``) are bit-equal to ``add_relu_torch`` / ``upsample_add_torch`` forward.  The
+third (``csrc/upsample_cat.hip``) takes its interpolation weights from integer arithmetic with one rounding, torch from
+a float product: the two differ in the last bits.
+
+The ops themselves never fall back: they raise on an input the kernels do not take.  The modules dispatch with the
+``*_fusable`` predicates: CUDA float32 contiguous tensors take the kernels, everything else (the CPU, other dtypes,
+non-contiguous maps) the ``*_torch`` formulation.
+"""
+import torch
+import torch.nn.functional as F
+
+from . import _lib
+
+# Defaults of the image encoder's two dispatch flags, from the measurement in profiles/image_encoder_time.txt
+# (tools/time_image_encoder.py; INTEGRATION 3f has the table): by device time each op is faster than its torch
+# formulation at the reference shapes, forward and forward + backward, at 12 and at 48 images (tail 1.07x to 1.65x, merge
+# 2.0x to 2.4x), and the whole encoder with both flags on is the fastest of the four flag pairs in eval and in training
+# (1.02x to 1.09x of the unfused one).
+FUSED_TAIL_DEFAULT = True
+FUSED_MERGE_DEFAULT = True
+
+
+def _plain(t):
+    return t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+
+
+# ------------------------------------------------------------------------------------------------ add + relu
+def add_relu_torch(a, b):
+    """``relu(a + b)``: the residual tail as eager torch runs it."""
+    return torch.relu_(a + b)
+
+
+def add_relu_fusable(a, b):
+    return _plain(a) and _plain(b) and a.shape == b.shape and a.device == b.device and a.numel() > 0
+
+
+class _AddRelu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b):
+        out = torch.empty_like(a)
+        _lib.launch('ocrf_add_relu_forward', a.device, a.numel(), a, b, out)
+        ctx.save_for_backward(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        out, = ctx.saved_tensors
+        grad_out = grad_out.contiguous()
+        grad = torch.empty_like(out)
+        _lib.launch('ocrf_add_relu_backward', out.device, out.numel(), grad_out, out, grad)
+        return grad, grad
+
+
+def add_relu(a, b):
+    """``add_relu_torch`` as one HIP launch (``ocrf_add_relu_forward`` / ``_backward``).  CUDA float32 contiguous
+    tensors of equal shape only: anything else raises (the blocks dispatch)."""
+    _lib.require_cuda(a, b)
+    if not add_relu_fusable(a, b):
+        raise _lib.OcrfHipError('add_relu takes two non-empty contiguous float32 tensors of equal shape on one device')
+    return _AddRelu.apply(a, b)
+
+
+# ------------------------------------------------------------------------------------------------ upsample + add
+def upsample_add_torch(dst, src, size=None, scale_factor=None, mode='nearest', **kwargs):
+    """``dst + F.interpolate(src, size=size | scale_factor=scale_factor, mode=mode)``."""
+    if scale_factor is not None:
+        return dst + F.interpolate(src, scale_factor=scale_factor, mode=mode, **kwargs)
+    return dst + F.interpolate(src, size=size, mode=mode, **kwargs)
+
+
+def _target(src, size, scale_factor):
+    """(Hout, Wout) of ``F.interpolate(src, size | scale_factor)`` where the kernel's index rule is torch's: a ``size``,
+    or an integer ``scale_factor`` (torch then scales by 1 / factor, which is in / out rounded once).  Else None."""
+    if (size is None) == (scale_factor is None) or src.dim() != 4:
+        return None
+    if size is not None:
+        size = (size, size) if isinstance(size, int) else tuple(size)
+        return (int(size[0]), int(size[1])) if len(size) == 2 else None
+    if isinstance(scale_factor, (tuple, list)):
+        if len(scale_factor) != 2 or scale_factor[0] != scale_factor[1]:
+            return None
+        scale_factor = scale_factor[0]
+    if not isinstance(scale_factor, (int, float)) or scale_factor != int(scale_factor) or scale_factor < 1:
+        return None
+    return src.shape[2] * int(scale_factor), src.shape[3] * int(scale_factor)
+
+
+def upsample_add_fusable(dst, src, size, scale_factor):
+    if not (_plain(dst) and _plain(src) and dst.dim() == 4 and src.dim() == 4 and dst.device == src.device):
+        return False
+    hw = _target(src, size, scale_factor)
+    return (hw is not None and dst.numel() > 0 and src.numel() > 0 and dst.shape[:2] == src.shape[:2]
+            and tuple(dst.shape[2:]) == hw and hw[0] >= src.shape[2] and hw[1] >= src.shape[3])
+
+
+class _UpsampleAdd(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, dst, src):
+        B, C, Hout, Wout = dst.shape
+        Hin, Win = src.shape[2:]
+        out = torch.empty_like(dst)
+        _lib.launch('ocrf_upsample_add_forward', dst.device, B, C, Hin, Win, Hout, Wout, dst, src, out)
+        ctx.shape = (B, C, Hin, Win, Hout, Wout)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        B, C, Hin, Win, Hout, Wout = ctx.shape
+        grad_src = None
+        if ctx.needs_input_grad[1]:
+            g = grad_out.contiguous()
+            grad_src = torch.empty(B, C, Hin, Win, dtype=torch.float32, device=g.device)
+            _lib.launch('ocrf_upsample_add_backward', g.device, B, C, Hin, Win, Hout, Wout, g, grad_src)
+        return (grad_out if ctx.needs_input_grad[0] else None), grad_src
+
+
+def upsample_add(dst, src, size=None, scale_factor=None):
+    """``upsample_add_torch`` in mode ``nearest`` as one HIP launch (``ocrf_upsample_add_forward`` / ``_backward``):
+    ``src`` (B, C, Hin, Win) upsampled to the size of ``dst`` (B, C, Hout, Wout) and added to it; ``size`` must be that
+    of ``dst``, or ``scale_factor`` an integer with ``Hout = Hin * scale_factor``.  CUDA float32 contiguous tensors
+    only: anything else raises (``CustomFPN`` dispatches)."""
+    _lib.require_cuda(dst, src)
+    if not upsample_add_fusable(dst, src, size, scale_factor):
+        raise _lib.OcrfHipError('upsample_add takes contiguous float32 NCHW tensors with the same B and C, dst of the '
+                                'target size and no smaller than src, and either size or an integer scale_factor')
+    return _UpsampleAdd.apply(dst, src)
+
+
+# ------------------------------------------------------------------------------------------------ upsample + cat
+def upsample_cat_torch(x2, x1, scale):
+    """``cat([x2, interpolate(x1, scale_factor=scale, mode='bilinear', align_corners=True)], 1)``; ``x2`` None: the
+    upsampling alone."""
+    up = F.interpolate(x1, scale_factor=scale, mode='bilinear', align_corners=True)
+    return up if x2 is None else torch.cat([x2, up], dim=1)
+
+
+def upsample_cat_fusable(x2, x1, scale):
+    if not isinstance(scale, (int, float)) or scale != int(scale) or scale < 1:
+        return False
+    for t in (x1, x2):
+        if t is not None and not (_plain(t) and t.dim() == 4):
+            return False
+    return x2 is None or (x2.shape[0] == x1.shape[0] and x2.shape[2] == x1.shape[2] * int(scale)
+                          and x2.shape[3] == x1.shape[3] * int(scale))
+
+
+class _UpsampleCat(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x2, x1, scale):
+        B, C1, Hin, Win = x1.shape
+        C2 = 0 if x2 is None else x2.shape[1]
+        out = torch.empty(B, C2 + C1, Hin * scale, Win * scale, dtype=torch.float32, device=x1.device)
+        _lib.launch('ocrf_upsample_cat_forward', x1.device, B, C2, C1, Hin, Win, scale, x2, x1, out)
+        ctx.shape = (B, C2, C1, Hin, Win, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        B, C2, C1, Hin, Win, scale = ctx.shape
+        grad_out = grad_out.contiguous()
+        grad_x2 = grad_x1 = None
+        if ctx.needs_input_grad[0] and C2:
+            grad_x2 = grad_out[:, :C2]
+        if ctx.needs_input_grad[1]:
+            grad_x1 = torch.empty(B, C1, Hin, Win, dtype=torch.float32, device=grad_out.device)
+            _lib.launch('ocrf_upsample_cat_backward', grad_out.device, B, C2, C1, Hin, Win, scale, grad_out, grad_x1)
+        return grad_x2, grad_x1, None
+
+
+def upsample_cat(x2, x1, scale):
+    """``upsample_cat_torch`` as one HIP launch (``ocrf_upsample_cat_forward`` / ``_backward``): ``x1`` (B, C1, H, W)
+    upsampled by the integer ``scale`` behind the channels of ``x2`` (B, C2, H*scale, W*scale), or alone with ``x2``
+    None.  CUDA float32 contiguous tensors only: anything else raises (``FPN_LSS`` dispatches)."""
+    _lib.require_cuda(x1, x2)
+    if not upsample_cat_fusable(x2, x1, scale):
+        raise _lib.OcrfHipError('upsample_cat takes contiguous float32 NCHW tensors, x2 scale times the size of x1, '
+                                'and an integer scale')
+    return _UpsampleCat.apply(x2, x1, int(scale))

@@ -15,6 +15,7 @@ import copy
 import pytest
 import torch
 
+from ocrfdet_amd import blocks
 from ocrfdet_amd import image_encoder as ie
 from tests import image_encoder_fixture as fx
 
@@ -41,7 +42,7 @@ def assert_close(got, want, what):
 def count_calls(monkeypatch):
     calls = []
     tail, merge = ie.add_relu, ie.upsample_add
-    monkeypatch.setattr(ie, 'add_relu', lambda *a: calls.append('tail') or tail(*a))
+    monkeypatch.setattr(blocks, 'add_relu', lambda *a: calls.append('tail') or tail(*a))
     monkeypatch.setattr(ie, 'upsample_add', lambda *a, **k: calls.append('merge') or merge(*a, **k))
     return calls
 

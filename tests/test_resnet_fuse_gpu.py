@@ -11,7 +11,7 @@
 
 Sizes: the smallest at which a vector kernel can go wrong (below, at and above one 16-byte group, one wave row of 256
 groups, one chunk of the kernel's ``kThreads * kGroups`` groups for both access widths) and one beyond ``kMaxBlocks``
-chunks, where the grid-stride loop takes a second turn; the constants are read from the kernel's source.
+chunks, where the grid-stride loop takes a second turn; the constants are read from the kernels' shared header.
 """
 import copy
 import functools
@@ -23,12 +23,12 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from ocrfdet_amd import _lib
+from ocrfdet_amd import _lib, blocks
 from ocrfdet_amd import image_encoder as ie
 
 pytestmark = pytest.mark.gpu
 
-_SRC = os.path.join(os.path.dirname(os.path.abspath(ie.__file__)), 'csrc', 'resnet_fuse.hip')
+_SRC = os.path.join(os.path.dirname(os.path.abspath(ie.__file__)), 'csrc', 'plane_walk.h')
 with open(_SRC) as _f:
     _K = {k: int(v) for k, v in re.findall(r'constexpr int (k\w+) = (\d+);', _f.read())}
 GROUPS_PER_CHUNK = _K['kThreads'] * _K['kGroups']                 # 16-byte groups (or floats, unaligned) per chunk
@@ -230,7 +230,7 @@ def test_other_inputs_raise_and_the_modules_take_the_torch_path(cuda, monkeypatc
 
     calls = []
     real_tail, real_merge = ie.add_relu, ie.upsample_add
-    monkeypatch.setattr(ie, 'add_relu', lambda *x: calls.append('tail') or real_tail(*x))
+    monkeypatch.setattr(blocks, 'add_relu', lambda *x: calls.append('tail') or real_tail(*x))
     monkeypatch.setattr(ie, 'upsample_add', lambda *x, **k: calls.append('merge') or real_merge(*x, **k))
     block = ie.BasicBlock(4, 4).to(cuda).eval()
     fpn = ie.CustomFPN([4, 4], 4, num_outs=1, out_ids=[0]).to(cuda)

@@ -11,7 +11,7 @@ around synchronised blocks — at 12 and at 48 images of 3 x 256 x 704 (B = 2 an
   forward in ``eval()`` and forward + backward in ``train()``, with each pair of ``fused_tail`` / ``fused_merge``;
 
 with the kernels' algorithmic bytes against the MI355X's measured HBM copy rate.  The defaults of the two flags in
-``ocrfdet_amd/image_encoder.py`` follow from this file's output.
+``ocrfdet_amd/plane_ops.py`` follow from this file's output.
 
     python tools/time_image_encoder.py [--iters N] [--enc-iters N] [--images 12 48] [--out profiles/image_encoder_time.txt]
 """
