@@ -387,6 +387,18 @@ int ocrf_bev_pool_v2_nchw_panel(int c, int n_units, const int *units, const int 
                                 const unsigned short *cell_code, const float *cw, const float *feat, float *out, int B,
                                 int Z, int Y, int X, int layout, int *arrive, void *slabs, size_t feat_bytes,
                                 ocrf_stream_t stream); /* feat_bytes: as for ocrf_bev_pool_v2_nchw_planned */
+/*
+ * ocrf_bev_pool_v2_nchw_panel + the channel statistics of its output in the same launch: the workgroup that writes a
+ * finished tile also writes stats[b][0][y][x] = mean_c out, stats[b][1][y][x] = max_c out for the tile's pixels — what
+ * ocrf_hoa_channel_stats computes from the pooled BEV, bit for bit, without reading it again (the height-sampling BEV is
+ * what HOA-3 gates: hand stats to ocrf_hoa_opacity_mask_gate).  Every pixel of stats (B, 2, Y, X) is written, empty
+ * tiles as zeros.  Z == 1 and layout 0 or 1 only; everything else as ocrf_bev_pool_v2_nchw_panel.
+ */
+int ocrf_bev_pool_v2_nchw_panel_stats(int c, int n_units, const int *units, const int *unit_slab, const int *panel_rows,
+                                      const int *panel_nrows, const int *panel_cell_off, const int *panel_voff,
+                                      const unsigned short *cell_code, const float *cw, const float *feat, float *out,
+                                      int B, int Z, int Y, int X, int layout, int *arrive, void *slabs, size_t feat_bytes,
+                                      float *stats, ocrf_stream_t stream);
 
 /*
  * Backward of the colour output of ocrf_rasterize_forward (the w-depth fork has no depth backward,
@@ -1077,7 +1089,7 @@ int ocrf_stream_create(const uint32_t *cu_mask, int n_words, int priority, void 
  * streams: the same entry points with the same arguments, launched eagerly (no hipGraph).  Pointer arguments are used as
  * recorded: the caller keeps inputs, outputs and scratch alive and in place, as for a captured graph.
  *   ocrf_step_fn_id(name)    id of an entry point a step can hold (-1: not supported — issue the step call by call):
- *                            ocrf_bev_pool_v2_nchw_planned / _mfma / _panel, ocrf_bev_pool_cell_weights,
+ *                            ocrf_bev_pool_v2_nchw_planned / _mfma / _panel / _panel_stats, ocrf_bev_pool_cell_weights,
  *                            ocrf_rasterize_planned, ocrf_raster_plan_build, ocrf_hoa1_forward, ocrf_hoa_v2b_forward,
  *                            ocrf_hoa_channel_stats, ocrf_hoa_opacity_mask_gate, ocrf_stream_write_value32
  *   ocrf_step_add_call       args: the entry point's arguments WITHOUT its trailing stream, one 64-bit word each —

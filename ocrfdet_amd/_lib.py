@@ -225,7 +225,7 @@ class StepRecorder:
     def build(self):
         if not self.ok:
             raise StepNotRecordable(self.why)
-        return CompiledStep(self.items)
+        return CompiledStep(self.items, self.names)
 
 
 class _RecordingLib:
@@ -251,8 +251,9 @@ class CompiledStep:
     """The calls of one step inside the library (``ocrf_step``): ``run(main, side, ...)`` issues all of them with one
     host call."""
 
-    def __init__(self, items):
+    def __init__(self, items, names=()):
         L = lib()
+        self.names = tuple(names)        # the entry points it holds, in call order
         self._h = ctypes.c_void_p()
         check(L.ocrf_step_create(ctypes.byref(self._h)), 'ocrf_step_create')
         self.n_calls = 0

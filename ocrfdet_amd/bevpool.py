@@ -521,10 +521,13 @@ def bev_pool_cell_weights(depth, plan, plan2=None):
 
 
 @torch.no_grad()
-def bev_pool_v2_panel(depth, feat, plan, layout=1, out=None, weights_ready=False):
+def bev_pool_v2_panel(depth, feat, plan, layout=1, out=None, weights_ready=False, stats=None):
     """The pooling of ``plan``'s rank vectors cell by cell out of LDS (csrc/bev_pool_panel.hip): same plan and same
     result as ``bev_pool_v2_mfma`` (bit for bit on finite inputs).  ``weights_ready``: ``bev_pool_cell_weights`` has
-    already run for this ``depth`` on this stream (one launch for both poolings of a step)."""
+    already run for this ``depth`` on this stream (one launch for both poolings of a step).  ``stats``: contiguous fp32
+    (B, 2, Y, X) tensor (Z == 1, layout 0 or 1) that the same launch fills with the output's channel mean and max, every
+    pixel of it — the bits of ``hoa.channel_stats(out)`` without its pass over the BEV
+    (``ocrf_bev_pool_v2_nchw_panel_stats``)."""
     B, Z, Y, X, C = plan.shape
     f32 = feat.float().contiguous()
     _check_32bit_offsets(f32)
@@ -539,9 +542,17 @@ def bev_pool_v2_panel(depth, feat, plan, layout=1, out=None, weights_ready=False
         out = torch.empty(shape, dtype=torch.float32, device=dev)
     elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * C * Z * Y * X or out.device != dev:
         raise _lib.OcrfHipError('out must be a contiguous fp32 tensor of B*C*Z*Y*X elements on the inputs\' device')
-    _lib.launch('ocrf_bev_pool_v2_nchw_panel', dev, C, plan.n_units, plan.units, plan.unit_slab, plan.panel_rows,
-                plan.panel_nrows, plan.panel_cell_off, plan.panel_voff, plan.cell_code, plan.cw, f32, out, B, Z, Y, X,
-                int(layout), plan.arrive, plan.slabs, f32.numel() * 4)
+    args = (C, plan.n_units, plan.units, plan.unit_slab, plan.panel_rows, plan.panel_nrows, plan.panel_cell_off,
+            plan.panel_voff, plan.cell_code, plan.cw, f32, out, B, Z, Y, X, int(layout), plan.arrive, plan.slabs, f32.numel() * 4)
+    if stats is None:
+        _lib.launch('ocrf_bev_pool_v2_nchw_panel', dev, *args)
+        return out
+    if Z != 1 or int(layout) not in (0, 1):
+        raise _lib.OcrfHipError('channel statistics come with a pooling of Z == 1 in layout 0 or 1')
+    if (not torch.is_tensor(stats) or stats.dtype != torch.float32 or not stats.is_contiguous()
+            or tuple(stats.shape) != (B, 2, Y, X) or stats.device != dev):
+        raise _lib.OcrfHipError('stats must be a contiguous fp32 (B, 2, Y, X) tensor on the inputs\' device')
+    _lib.launch('ocrf_bev_pool_v2_nchw_panel_stats', dev, *args, stats)
     return out
 
 

@@ -19,7 +19,9 @@
 //     instructions of index work per cell and were bound by exactly that;
 //   * the rows sit in LDS at an odd float4 pitch (lanes read different rows: 16 distinct bank offsets);
 //   * the 64 x C tile leaves through LDS in the caller's layout (bev_pool_tile_out.h; tiles of several units reduce
-//     through write-through slabs and a ticket in slice order).
+//     through write-through slabs and a ticket in slice order);
+//   * STATS: the finished tile's channel mean / max per pixel leave with it (ocrf_bev_pool_v2_nchw_panel_stats: HOA-3's
+//     statistics of the height-sampling BEV without a second pass over it).
 // No float atomics anywhere: results are bitwise reproducible.
 #include <hip/hip_runtime.h>
 
@@ -113,8 +115,9 @@ __global__ __launch_bounds__(kBlock) void bev_pool_cell_weights_kernel(
 #else
 #define OCRF_PANEL_BOUNDS(C4) __launch_bounds__(kBlock, (C4) == 20 ? 5 : ((C4) <= 24 ? 4 : 3))
 #endif
-template <int C4, bool STAMP = false>
-__global__ OCRF_PANEL_BOUNDS(C4) void bev_pool_panel_kernel(PanelArgs a, unsigned long long* __restrict__ stamps) {
+template <int C4, bool STAMP = false, bool STATS = false>
+__global__ OCRF_PANEL_BOUNDS(C4) void bev_pool_panel_kernel(PanelArgs a, unsigned long long* __restrict__ stamps,
+                                                            float* __restrict__ stats) {
   OCRF_POOL_PRIO();
   unsigned long long t_prev = 0, t_acc[5] = {0, 0, 0, 0, 0};        // diagnostic build only
   auto stamp = [&](int slot) {
@@ -254,7 +257,8 @@ __global__ OCRF_PANEL_BOUNDS(C4) void bev_pool_panel_kernel(PanelArgs a, unsigne
   for (int k = 0; k < K; ++k) tile[lane * ldq + wave * K + k] = acc[k];
   __syncthreads();
   stamp(3);
-  pool_out::leave<C4>(tile, s_flag, a.d, tileid, plane, y0, x0, n_slices, slice, n_slices > 1 ? a.unit_slab[blockIdx.x] : 0);
+  pool_out::leave<C4, STATS>(tile, s_flag, a.d, tileid, plane, y0, x0, n_slices, slice,
+                             n_slices > 1 ? a.unit_slab[blockIdx.x] : 0, stats);
   stamp(4);
   if constexpr (STAMP) {
     if (tid == 0) {
@@ -297,11 +301,11 @@ int ocrf_bev_pool_cell_weights(int n_cells0, const int* cells0, const int* rd_so
   return (int)hipGetLastError();
 }
 
-int ocrf_bev_pool_v2_nchw_panel(int c, int n_units, const int* units, const int* unit_slab, const int* panel_rows,
-                                const int* panel_nrows, const int* panel_cell_off, const int* panel_voff,
-                                const unsigned short* cell_code, const float* cw, const float* feat, float* out, int B, int Z,
-                                int Y, int X, int layout, int* arrive, void* slabs, size_t feat_bytes, ocrf_stream_t stream_) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
+// Both entry points: stats == nullptr is the plain pooling.
+static int panel_pool(int c, int n_units, const int* units, const int* unit_slab, const int* panel_rows, const int* panel_nrows,
+                      const int* panel_cell_off, const int* panel_voff, const unsigned short* cell_code, const float* cw,
+                      const float* feat, float* out, int B, int Z, int Y, int X, int layout, int* arrive, void* slabs,
+                      size_t feat_bytes, float* stats, hipStream_t stream) {
   if (c != 80 && c != 64 && c != 96 && c != 128) return (int)hipErrorInvalidValue;
   // 32-bit byte offsets into feat and the output (bev_pool_cuda.cu:39-47 indexes with int): refused at the C boundary
   if (feat_bytes >= (1ull << 31) || (size_t)B * Z * Y * X * c * 4 >= (1ull << 31)) return (int)hipErrorInvalidValue;
@@ -321,17 +325,45 @@ int ocrf_bev_pool_v2_nchw_panel(int c, int n_units, const int* units, const int*
   a.d.out = out; a.d.slabs = static_cast<float4*>(slabs); a.d.arrive = arrive;
   const dim3 grid((unsigned)n_units), block(kBlock);
   unsigned long long* none = nullptr;
+  if (stats) {      // (the stamped build has no statistics form: a diagnostic of the plain pooling)
+    switch (c) {
+      case 64: ocrf::launch(OCRF_K_BEV_POOL_PANEL, bev_pool_panel_kernel<16, false, true>, grid, block, panel_lds_bytes<16>(), stream, a, none, stats); break;
+      case 80: ocrf::launch(OCRF_K_BEV_POOL_PANEL, bev_pool_panel_kernel<20, false, true>, grid, block, panel_lds_bytes<20>(), stream, a, none, stats); break;
+      case 96: ocrf::launch(OCRF_K_BEV_POOL_PANEL, bev_pool_panel_kernel<24, false, true>, grid, block, panel_lds_bytes<24>(), stream, a, none, stats); break;
+      default: ocrf::launch(OCRF_K_BEV_POOL_PANEL, bev_pool_panel_kernel<32, false, true>, grid, block, panel_lds_bytes<32>(), stream, a, none, stats); break;
+    }
+    return (int)hipGetLastError();
+  }
   if (g_panel_stamps && c == 80) {      // diagnostic build, never used by the product path
-    hipLaunchKernelGGL((bev_pool_panel_kernel<20, true>), grid, block, panel_lds_bytes<20>(), stream, a, g_panel_stamps);
+    hipLaunchKernelGGL((bev_pool_panel_kernel<20, true>), grid, block, panel_lds_bytes<20>(), stream, a, g_panel_stamps, stats);
     return (int)hipGetLastError();
   }
   switch (c) {
-    case 64: ocrf::launch(OCRF_K_BEV_POOL_PANEL, bev_pool_panel_kernel<16>, grid, block, panel_lds_bytes<16>(), stream, a, none); break;
-    case 80: ocrf::launch(OCRF_K_BEV_POOL_PANEL, bev_pool_panel_kernel<20>, grid, block, panel_lds_bytes<20>(), stream, a, none); break;
-    case 96: ocrf::launch(OCRF_K_BEV_POOL_PANEL, bev_pool_panel_kernel<24>, grid, block, panel_lds_bytes<24>(), stream, a, none); break;
-    default: ocrf::launch(OCRF_K_BEV_POOL_PANEL, bev_pool_panel_kernel<32>, grid, block, panel_lds_bytes<32>(), stream, a, none); break;
+    case 64: ocrf::launch(OCRF_K_BEV_POOL_PANEL, bev_pool_panel_kernel<16>, grid, block, panel_lds_bytes<16>(), stream, a, none, stats); break;
+    case 80: ocrf::launch(OCRF_K_BEV_POOL_PANEL, bev_pool_panel_kernel<20>, grid, block, panel_lds_bytes<20>(), stream, a, none, stats); break;
+    case 96: ocrf::launch(OCRF_K_BEV_POOL_PANEL, bev_pool_panel_kernel<24>, grid, block, panel_lds_bytes<24>(), stream, a, none, stats); break;
+    default: ocrf::launch(OCRF_K_BEV_POOL_PANEL, bev_pool_panel_kernel<32>, grid, block, panel_lds_bytes<32>(), stream, a, none, stats); break;
   }
   return (int)hipGetLastError();
+}
+
+int ocrf_bev_pool_v2_nchw_panel(int c, int n_units, const int* units, const int* unit_slab, const int* panel_rows,
+                                const int* panel_nrows, const int* panel_cell_off, const int* panel_voff,
+                                const unsigned short* cell_code, const float* cw, const float* feat, float* out, int B, int Z,
+                                int Y, int X, int layout, int* arrive, void* slabs, size_t feat_bytes, ocrf_stream_t stream_) {
+  return panel_pool(c, n_units, units, unit_slab, panel_rows, panel_nrows, panel_cell_off, panel_voff, cell_code, cw, feat, out,
+                    B, Z, Y, X, layout, arrive, slabs, feat_bytes, nullptr, static_cast<hipStream_t>(stream_));
+}
+
+// ... and the channel mean / max of every pixel to stats (B, 2, Y, X): one plane per batch entry, NCHW layouts only
+int ocrf_bev_pool_v2_nchw_panel_stats(int c, int n_units, const int* units, const int* unit_slab, const int* panel_rows,
+                                      const int* panel_nrows, const int* panel_cell_off, const int* panel_voff,
+                                      const unsigned short* cell_code, const float* cw, const float* feat, float* out, int B,
+                                      int Z, int Y, int X, int layout, int* arrive, void* slabs, size_t feat_bytes, float* stats,
+                                      ocrf_stream_t stream_) {
+  if (Z != 1 || layout == 2 || !stats) return (int)hipErrorInvalidValue;
+  return panel_pool(c, n_units, units, unit_slab, panel_rows, panel_nrows, panel_cell_off, panel_voff, cell_code, cw, feat, out,
+                    B, Z, Y, X, layout, arrive, slabs, feat_bytes, stats, static_cast<hipStream_t>(stream_));
 }
 
 }  // extern "C"

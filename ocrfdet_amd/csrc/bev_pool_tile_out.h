@@ -6,6 +6,10 @@
 // adds the slabs in slice order (fixed order whoever arrives last: no float atomics, bitwise reproducible) and writes
 // the tile in the caller's layout.  Returns after the tile (or the slab) is on its way; every thread of the workgroup
 // calls it.
+//
+// STATS (layouts 0 / 1 with Z = 1): whoever writes the finished tile also writes its pixels' channel mean and channel max
+// to `stats` (B, 2, Y, X) — what hoa_channel_stats_kernel (hoa.hip) would re-read the whole BEV for, in its arithmetic
+// (sum over c = 0 .. C-1 from 0.f with plain adds, / (float)C; fmaxf from -INFINITY): same bits.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,9 +28,9 @@ struct Dest {
 };
 
 // tile: LDS [64][ldq]; s_flag: one LDS int; slab_first: first slab of the tile (n_slices > 1)
-template <int C4>
+template <int C4, bool STATS = false>
 __device__ __forceinline__ void leave(float4* tile, int* s_flag, const Dest& d, int tileid, int plane, int y0, int x0,
-                                      int n_slices, int slice, int slab_first) {
+                                      int n_slices, int slice, int slab_first, float* stats = nullptr) {
   constexpr int ldq = C4 | 1;
   constexpr int C = 4 * C4;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -105,6 +109,46 @@ __device__ __forceinline__ void leave(float4* tile, int* s_flag, const Dest& d, 
         oc[cstride] = t.y;
         oc[2 * cstride] = t.z;
         oc[3 * cstride] = t.w;
+      }
+      if constexpr (STATS) {
+        // lane = voxel slot, as above: wave 0 walks the C channels of its LDS row in channel order (one lane, one
+        // pixel: no combine across lanes, so the sum is the stats kernel's chain of adds)
+        if (wave == 0) {
+          // the row in four groups of C4 / 4 float4, the next group's reads issued before this group's adds (the scheduling
+          // barriers keep them there): the chain of C dependent adds runs under the reads instead of waiting once per read
+          static_assert(C4 % 4 == 0, "four groups");
+          constexpr int kG = C4 / 4;
+          const float4* row = tile + lane * ldq;
+          float sum = 0.f, mx = -INFINITY;
+          float4 ta[kG], tb[kG];
+          auto eat = [&](const float4 (&t)[kG]) __attribute__((always_inline)) {
+#pragma unroll
+            for (int k = 0; k < kG; ++k) {
+              sum += t[k].x; mx = fmaxf(mx, t[k].x);
+              sum += t[k].y; mx = fmaxf(mx, t[k].y);
+              sum += t[k].z; mx = fmaxf(mx, t[k].z);
+              sum += t[k].w; mx = fmaxf(mx, t[k].w);
+            }
+          };
+#pragma unroll
+          for (int k = 0; k < kG; ++k) ta[k] = row[k];
+#pragma unroll
+          for (int k = 0; k < kG; ++k) tb[k] = row[kG + k];
+          __builtin_amdgcn_sched_barrier(0);
+          eat(ta);
+#pragma unroll
+          for (int k = 0; k < kG; ++k) ta[k] = row[2 * kG + k];
+          __builtin_amdgcn_sched_barrier(0);
+          eat(tb);
+#pragma unroll
+          for (int k = 0; k < kG; ++k) tb[k] = row[3 * kG + k];
+          __builtin_amdgcn_sched_barrier(0);
+          eat(ta);
+          eat(tb);
+          float* sp = stats + (long)plane * 2 * YX + (long)y * d.X + x;      // Z = 1: plane = batch entry
+          sp[0] = sum / (float)C;
+          sp[YX] = mx;
+        }
       }
     }
   }

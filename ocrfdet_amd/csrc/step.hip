@@ -91,7 +91,7 @@ const FnInfo kFns[] = {
     OCRF_STEP_FN(ocrf_raster_plan_build),        OCRF_STEP_FN(ocrf_rasterize_forward),
     OCRF_STEP_FN(ocrf_bev_pool_v2_nchw_dyn),     OCRF_STEP_FN(ocrf_lss_prepare),
     OCRF_STEP_FN(ocrf_ht_prepare),               OCRF_STEP_FN(ocrf_geometry_blocks),
-    OCRF_STEP_FN(ocrf_rasterize_forward_sets),
+    OCRF_STEP_FN(ocrf_rasterize_forward_sets),   OCRF_STEP_FN(ocrf_bev_pool_v2_nchw_panel_stats),
 };
 #undef OCRF_STEP_FN
 constexpr int kFnCount = int(sizeof(kFns) / sizeof(kFns[0]));

@@ -61,7 +61,7 @@ class HotPath:
                  render_mode='planned', render_guard='host', frame_motion=True, frame_offset=0, plan_margin=1.25,
                  ht_pool_backend=None, fuse_frames='auto', render_streams=1, blend_workgroups='auto',
                  lss_pool_backend=None, lss_mfma_group=2, plan_rebuild='never', hoa_first=None, one_call=True,
-                 gaussians='init', alternate=None):
+                 gaussians='init', alternate=None, fuse_hoa_stats=True):
         """``cams``: optional list of camera indices this instance owns (camera sharding).
         ``index_prep_mode``: 'cached' — rank vectors computed once per calibration, the reference's
         ``accelerate=True`` intent; 'per_step' — recomputed inside every ``step()`` by the HIP index
@@ -89,8 +89,12 @@ class HotPath:
         of the step replayed from C, ``_lib.StepCache``) instead of ~14 ctypes calls + torch stream / event calls
         (225 -> ~60 us of host work at cfg2).  The step's outputs are then the SAME tensors every step (overwritten by
         the next one, like a replayed graph's), and ``depth`` / ``feat`` have to be the tensors of the recorded call
-        (another pair is recorded anew)."""
+        (another pair is recorded anew).
+        ``fuse_hoa_stats``: HOA-3's channel statistics of the HT BEV leave the HT pooling with its tiles
+        (``bevpool.bev_pool_v2_panel(..., stats=...)``) instead of being read back from the BEV by a launch of their own
+        (``_fused_stats``: cached rank vectors and the panel backend; False: always that launch)."""
         self.cfg, self.device = cfg, torch.device(device)
+        self.fuse_hoa_stats = bool(fuse_hoa_stats)
         assert render_mode in ('planned', 'per_call') and render_guard in ('host', 'device')
         assert plan_rebuild in ('never', 'per_step')
         self.plan_rebuild = plan_rebuild
@@ -182,7 +186,7 @@ class HotPath:
                                                 cfg.input_size, cfg.grid['depth'])
         self.voxel_xyz = voxel
 
-        if cfg.render:
+        if cfg.render or cfg.hoa:      # (HOA-1 reads the Gaussian opacities: the parameter sets exist without the render too)
             self._prepare_render(r)
         if cfg.hoa:
             self._prepare_hoa()
@@ -203,6 +207,9 @@ class HotPath:
         self.alpha_lidar = torch.rand(self.batch, cfg.num_height, Y, X, generator=g).to(dev)
         self._opac_flat = None
         self.bev_pos1 = (torch.randn(self.batch, 4, Y, X, generator=g) * 0.1).to(dev)
+        # channel mean / max of the HT BEV, written by the HT pooling and read by HOA-3's gate (``fuse_hoa_stats``): one
+        # buffer for every step, like the step's other persistent scratch (a recorded step replays its address)
+        self._hoa_stats = torch.empty(self.batch, 2, Y, X, dtype=torch.float32, device=dev) if dev.type == 'cuda' else None
 
     @torch.no_grad()
     def hoa_opacity_bev(self):
@@ -221,12 +228,22 @@ class HotPath:
         return m['v2b'](oa, self.bev_pos1)
 
     @torch.no_grad()
-    def hoa_step(self, geom_feat, opacity_bev=None):
-        """HOA-1/2/3 (view_transformer_ocrf.py:1159-1161, 1196-1199): -> (gated BEV, opacity BEV)."""
+    def hoa_step(self, geom_feat, opacity_bev=None, stats=None):
+        """HOA-1/2/3 (view_transformer_ocrf.py:1159-1161, 1196-1199): -> (gated BEV, opacity BEV).  ``stats``:
+        ``hoa.channel_stats(geom_feat)`` if the caller has it already (``_fused_stats``)."""
         if opacity_bev is None:
             opacity_bev = self.hoa_opacity_bev()
-        _, gated = self.hoa_mods['mask'].gate(geom_feat, opacity_bev)
+        _, gated = self.hoa_mods['mask'].gate(geom_feat, opacity_bev, stats=stats)
         return gated, opacity_bev
+
+    def _fused_stats(self):
+        """The buffer the HT pooling fills with HOA-3's channel statistics, or None where they are a launch of their own:
+        without HOA, with the per-step index preparation (``bev_pool_v2_nchw_dyn``) and with the tile / MFMA backends."""
+        C = self.ht.bev_shape[-1]
+        if (self.fuse_hoa_stats and self.cfg.hoa and self.index_prep_mode == 'cached' and self.ht_pool_backend == 'panel'
+                and C in (64, 80, 96, 128) and self.ht.n_points and self._hoa_stats is not None):
+            return self._hoa_stats
+        return None
 
     def _prepare_render(self, r, convention='corrected', seed=0):
         """Cameras + synthetic Gaussian parameters of the OcRF render, per frame.
@@ -478,10 +495,15 @@ class HotPath:
             plan.mfma_plan = bevpool.MfmaPoolPlan(plan.ranks_depth, plan.ranks_feat, plan.ranks_bev, plan.bev_shape, **kw)
         return plan.mfma_plan
 
-    def pool(self, plan, depth, feat, out=None, weights_ready=False):
+    def pool(self, plan, depth, feat, out=None, weights_ready=False, stats=None):
         """-> (B, Z*C, Y, X): pooled BEV with Z collapsed into channels (view_transformer.py:194).  The
         rank vectors are cached, so the rank-only half of the pooling is too (bevpool.DevicePoolPlan).
-        ``out``: contiguous fp32 tensor to write into (a slice of a fused buffer)."""
+        ``out``: contiguous fp32 tensor to write into (a slice of a fused buffer).  ``stats``: panel backend only, see
+        ``bevpool.bev_pool_v2_panel``."""
+        if stats is not None and not (plan.n_points and plan.bev_shape[-1] in (64, 80, 96, 128) and
+                                      (self.ht_pool_backend if plan is self.ht else
+                                       self.lss_pool_backend if plan is self.lss else 'tile') == 'panel'):
+            raise _lib.OcrfHipError('only the panel pooling writes channel statistics')
         if plan.n_points == 0:
             res = bevpool.bev_pool_v2_collapsed(depth, feat, plan.ranks_depth, plan.ranks_feat,
                                                 plan.ranks_bev, plan.bev_shape, plan.starts, plan.lengths)
@@ -498,7 +520,7 @@ class HotPath:
             self._panel_plan(plan)
             if backend == 'mfma':
                 return bevpool.bev_pool_v2_mfma(depth, feat, plan.mfma_plan, out=out)
-            return bevpool.bev_pool_v2_panel(depth, feat, plan.mfma_plan, out=out, weights_ready=weights_ready)
+            return bevpool.bev_pool_v2_panel(depth, feat, plan.mfma_plan, out=out, weights_ready=weights_ready, stats=stats)
         if plan.device_plan is None:
             plan.device_plan = bevpool.DevicePoolPlan(plan.ranks_depth, plan.ranks_feat, plan.ranks_bev, plan.bev_shape,
                                                       plan.starts, plan.lengths)
@@ -544,10 +566,10 @@ class HotPath:
         return (PoolPlan(*self._or_empty(index_prep._trim(lss[0], counts[0])), (self.batch, Z, Y, X, cfg.channels)),
                 PoolPlan(*self._or_empty(index_prep._trim(ht[0], counts[1])), (self.batch, 1, Y, X, cfg.channels)))
 
-    def pool_step(self, depth, feat, prepared=None):
+    def pool_step(self, depth, feat, prepared=None, ht_stats=None):
         """Both poolings (index preparation first in 'per_step' mode): LSS BEV (B, Z*C, Y, X) and
         HT BEV (B, C, Y, X) (view_transformer.py:194, view_transformer_ocrf.py:781).  ``prepared``: what
-        ``prepare_indices_hip(sync=False)`` returned, if the caller already issued it."""
+        ``prepare_indices_hip(sync=False)`` returned, if the caller already issued it.  ``ht_stats``: ``_fused_stats()``."""
         if self.index_prep_mode == 'per_step':
             # ranks stay on the device, their lengths too: no host read anywhere in the step
             (lv, lc), (hv, hc) = prepared if prepared is not None else self.prepare_indices_hip(sync=False)
@@ -559,8 +581,9 @@ class HotPath:
                 and self.lss.n_points and self.ht.n_points):
             # both poolings read the same depth tensor: ONE launch sums the cell weights of both plans
             bevpool.bev_pool_cell_weights(depth, self._panel_plan(self.lss), self._panel_plan(self.ht))
-            return self.pool(self.lss, depth, feat, weights_ready=True), self.pool(self.ht, depth, feat, weights_ready=True)
-        return self.pool(self.lss, depth, feat), self.pool(self.ht, depth, feat)
+            return (self.pool(self.lss, depth, feat, weights_ready=True),
+                    self.pool(self.ht, depth, feat, weights_ready=True, stats=ht_stats))
+        return self.pool(self.lss, depth, feat), self.pool(self.ht, depth, feat, stats=ht_stats)
 
     def step(self, depth, feat):
         """One pass of the hot path: pools (+ render + HOA where the configuration has them).
@@ -594,7 +617,7 @@ class HotPath:
         return (depth.data_ptr(), feat.data_ptr(), tuple(depth.shape), tuple(feat.shape), depth.dtype, feat.dtype, self.phase,
                 self.index_prep_mode, self.plan_rebuild, self.overlap, bw if isinstance(bw, (int, str)) else tuple(bw),
                 self.render_mode, self.render_guard, self.hoa_first, self.lss_pool_backend, self.ht_pool_backend,
-                self.render_streams, self.fuse_frames, self.device_geometry)
+                self.render_streams, self.fuse_frames, self.device_geometry, self.fuse_hoa_stats)
 
     def _forks(self):
         return self.overlap and self.cfg.render
@@ -672,7 +695,7 @@ class HotPath:
     def _main_chain(self, depth, feat):
         """Pools + HOA on the current stream -> (lss, ht[, gated, opacity_bev])."""
         # HOA-1/2 do not read the pooled BEV and are latency chains of small kernels
-        prepared = None
+        prepared = stats = None
         if self._prep_forks():
             # the index preparation (~ 20 launches, 0.17 ms) needs nothing HOA-1/2 produce: on streams of its own
             # beside them; the poolings wait for it.  Only with the calibration algebra on the device: with the host
@@ -734,14 +757,16 @@ class HotPath:
             lss.record_stream(main)
             ht.record_stream(main)
         else:
-            lss, ht = self.pool_step(depth, feat, prepared)
+            # the HT BEV is what HOA-3 gates below: its channel statistics leave the pooling with its tiles
+            stats = self._fused_stats()
+            lss, ht = self.pool_step(depth, feat, prepared, ht_stats=stats)
         if self.cfg.hoa and not hoa_first:
             ob = self.hoa_opacity_bev()
         out = [lss, ht]
         if self.cfg.hoa:
             # stand-in for geom_feat: the HT BEV has its shape (B,C,Y,X); the fusion convs between
             # the pools and HOA-3 are MIOpen territory, not part of this path
-            out.extend(self.hoa_step(ht, ob))
+            out.extend(self.hoa_step(ht, ob, stats=stats))
         return out
 
     @property

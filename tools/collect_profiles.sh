@@ -8,6 +8,8 @@
 #        the SQ instruction / cycle counters of the blend roofline, LDS counters, GRBM_GUI_ACTIVE (clock);
 #     3. tools/pmc_reduce.py -> gpurun_out/prof_<tag>/{kernel_stats*.csv, pmc_raw.csv, pmc_mean.csv}
 # Copy the three reduced files into profiles/ (named per round) to have them judged.
+# Every run has a time limit of its own (STEP_TIMEOUT seconds) and the first one that fails ends the collection: nothing
+# more is started on a device that a run has just faulted or hung.
 set -eo pipefail
 TAG=${1:?tag}
 shift || true
@@ -17,12 +19,13 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 STEPS=${STEPS:-20}
+LIMIT="timeout -k 10 ${STEP_TIMEOUT:-300}"
 B="$ROOT/bench.py --steps $STEPS --warmup 3 --no-cpu-baseline --no-pool-backends $EXTRA"
 
 echo "[collect] kernel trace, serial" && date
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_serial" -o x -- python3 $B --no-overlap > "$OUT/trace_serial.log" 2>&1
+$LIMIT rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_serial" -o x -- python3 $B --no-overlap > "$OUT/trace_serial.log" 2>&1
 echo "[collect] kernel trace, overlapped" && date
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_overlap" -o x -- python3 $B > "$OUT/trace_overlap.log" 2>&1
+$LIMIT rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_overlap" -o x -- python3 $B > "$OUT/trace_overlap.log" 2>&1
 
 i=0
 for GROUP in "FETCH_SIZE" "WRITE_SIZE" \
@@ -33,8 +36,8 @@ for GROUP in "FETCH_SIZE" "WRITE_SIZE" \
              "GRBM_GUI_ACTIVE TCC_HIT_sum TCC_MISS_sum"; do
   i=$((i + 1))
   echo "[collect] pmc pass $i: $GROUP" && date
-  rocprofv3 --pmc $GROUP --output-format csv -d "$OUT/pmc_$i" -o x -- python3 $B --no-overlap > "$OUT/pmc_$i.log" 2>&1 \
-    || echo "[collect] pmc pass $i FAILED (see pmc_$i.log)"
+  $LIMIT rocprofv3 --pmc $GROUP --output-format csv -d "$OUT/pmc_$i" -o x -- python3 $B --no-overlap > "$OUT/pmc_$i.log" 2>&1 \
+    || { echo "[collect] pmc pass $i FAILED (see pmc_$i.log): stopping"; tail -20 "$OUT/pmc_$i.log"; exit 1; }
 done
 python3 "$ROOT/tools/pmc_reduce.py" "$OUT"
 # what these passes ran: bench.py uses the counters only for the same config / render mode / library sources
