@@ -629,6 +629,42 @@ int ocrf_upsample_cat_backward(int B, int C2, int C1, int Hin, int Win, int scal
                                float *grad_x1, ocrf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Temporal BEV alignment (csrc/bev_align.hip, csrc/bev_align_index.h): BEVDet4D.shift_feature
+ * (mmdet3d/models/detectors/bevdet.py:305-376), the warp of an adjacent frame's BEV feature into the key ego frame,
+ * written into its channels of the concatenation in front of the BEV encoder (bevdet.py:529-536, ocrfdet.py:267-274).
+ * Deterministic, no atomics, no workspace, no host reads.  f32.
+ *
+ * Sampling rule.  tf (n, 3, 3) f32 row-major, gen_grid's tf rounded to f32; rows 0 and 1 are read.  Output pixel
+ *   (row i, column j) of sample b samples the source plane at
+ *     sx = fmaf(t00, j, fmaf(t01, i, t02)),  sy = fmaf(t10, j, fmaf(t11, i, t12)),
+ *   x0 = floorf(sx), lx = sx - x0 (y alike), value (1 - ly) ((1 - lx) v00 + lx v01) + ly ((1 - lx) v10 + lx v11), each
+ *   operation rounded once, a tap outside [0, w) x [0, h) read as 0: grid_sample(bilinear, zeros, align_corners=True) on
+ *   the reference's normalised grid without the normalise / unnormalise round trip.
+ *
+ * ocrf_bev_align_forward: x (n, c, h, w) contiguous -> element [b][ch][i][j] at out + b * out_batch_stride +
+ *   (ch * h + i) * w + j (floats), so that out may be a channel slice of a wider concatenation; out_batch_stride >=
+ *   c * h * w.  One launch, every destination element written once; 16-byte stores when h * w and out_batch_stride are
+ *   multiples of 4 and out is 16-byte aligned, 4-byte stores otherwise.
+ * ocrf_bev_align_backward: grad_out addressed like out (grad_batch_stride) -> grad_x (n, c, h, w) contiguous, the
+ *   transpose of the forward as a gather: per source pixel the output pixels inside its box (below) are walked rows
+ *   ascending, columns ascending, the forward's expressions re-evaluated, and weight * grad_out added where a tap is
+ *   that pixel.  One launch, every element written.  There is no gradient of tf.
+ * ocrf_bev_align_source_box: host only, touches no GPU.  box[0..3] = first and last column, first and last row
+ *   (inclusive) of a box that holds every output pixel of an h x w plane one of whose taps is source pixel (qx, qy)
+ *   under the 6 floats tf[0..5] (rows 0 and 1 of one transform).  For ANY float input (NaN, infinities, det = 0) the
+ *   box lies inside the plane or is the empty box (0, -1, 0, -1); a singular or strongly shrinking transform gives the
+ *   whole plane.  The backward kernel uses this very function.
+ * Limits: n, c, h, w > 0; the contiguous operand and the strided one ((n - 1) * stride + c * h * w floats) below 2 GiB
+ *   (the kernels index with int); anything else returns hipErrorInvalidValue and launches nothing.  With non-finite tf
+ *   the results are unspecified, but no address outside the operands is formed.
+ */
+int ocrf_bev_align_forward(int n, int c, int h, int w, const float *x, const float *tf, float *out,
+                           long long out_batch_stride, ocrf_stream_t stream);
+int ocrf_bev_align_backward(int n, int c, int h, int w, const float *grad_out, long long grad_batch_stride,
+                            const float *tf, float *grad_x, ocrf_stream_t stream);
+int ocrf_bev_align_source_box(const float *tf, int h, int w, int qx, int qy, int *box);
+
+/* ------------------------------------------------------------------------------------------
  * The memory-bound passes between the image encoder's convolutions (csrc/resnet_fuse.hip): the residual tail of a
  * ResNet block and CustomFPN's top-down step (mmdet3d/models/necks/fpn.py:190-196), one launch each.  Deterministic, no
  * atomics, no workspace, no host reads.  f32, contiguous; 16-byte accesses when every pointer is 16-byte aligned (and,
@@ -1056,7 +1092,9 @@ enum {
   OCRF_K_ADD_RELU = 104,         /* binary_kernel<V, AddRelu> */
   OCRF_K_ADD_RELU_BWD = 105,     /* binary_kernel<V, Threshold> */
   OCRF_K_UPSAMPLE_ADD = 106,     /* upsample_add_kernel<V> */
-  OCRF_K_UPSAMPLE_ADD_BWD = 107  /* upsample_add_backward_kernel */
+  OCRF_K_UPSAMPLE_ADD_BWD = 107, /* upsample_add_backward_kernel */
+  OCRF_K_BEV_ALIGN = 108,        /* bev_align_kernel<V> */
+  OCRF_K_BEV_ALIGN_BWD = 109     /* bev_align_backward_kernel */
 };
 const char *ocrf_kernel_name(int kernel_id);           /* symbol as rocprofv3 prints it */
 /* Diagnostic: a one-thread kernel that stores the device's constant-rate clock (wall_clock64, 100 MHz)

@@ -20,6 +20,9 @@ Drop-in mirrors of the reference's Python surface for that path (and nothing els
   build_norm_layer, kaiming_init                  center_head)
   (the encoders' fused passes between             ocrfdet_amd.plane_ops (add_relu, upsample_add, upsample_cat;
   convolutions)                                   re-exported by the encoder modules)
+  BEVDet4D.gen_grid / shift_feature and the       ocrfdet_amd.temporal (feature_transform, shift_feature,
+  cat of the aligned frames                       align_and_cat, gen_grid, shift_feature_method, also
+                                                  exported here)
   ==============================================  =================================================
 
 Every op calls the C ABI of ``csrc/libocrf_hip.so`` (``include/ocrf_hip.h``) through ctypes with
@@ -29,12 +32,18 @@ from . import _lib  # noqa: F401
 
 __version__ = "0.1.0"
 _LAZY = ('ResNet', 'CustomFPN', 'ImageEncoder')
+_LAZY_TEMPORAL = ('feature_transform', 'shift_feature', 'shift_feature_torch', 'align_and_cat', 'gen_grid',
+                  'shift_feature_method')
 
 
 def __getattr__(name):
     """``ocrfdet_amd.ResNet`` / ``CustomFPN`` / ``ImageEncoder``: the classes of ``ocrfdet_amd.image_encoder``, imported
-    on first use.  There is no ``__all__``: ``from ocrfdet_amd import *`` yields what it yielded before."""
+    on first use, and the functions of ``ocrfdet_amd.temporal`` likewise.  There is no ``__all__``:
+    ``from ocrfdet_amd import *`` yields what it yielded before."""
     if name in _LAZY:
         from . import image_encoder
         return getattr(image_encoder, name)
+    if name in _LAZY_TEMPORAL:
+        from . import temporal
+        return getattr(temporal, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -1,0 +1,209 @@
+// Temporal BEV alignment: BEVDet4D.shift_feature (mmdet3d/models/detectors/bevdet.py:305-376), the warp of an adjacent
+// frame's BEV feature into the key ego frame, written straight into its channels of the concatenation that feeds the BEV
+// encoder (bevdet.py:529-536, ocrfdet.py:267-274).  The transform is affine in pixel coordinates (gen_grid's tf), so
+// the forward is grid_sample(bilinear, zeros, align_corners=True) without the grid tensor and without the normalise /
+// unnormalise round trip, and the backward is a gather: no atomics, no workspace, no host synchronisation; repeated runs
+// are bit-identical.  The sampling rule and the box of candidates are in bev_align_index.h.
+//
+// Forward.  A unit is (batch, block of kChannels channels, chunk of the plane); a thread walks its groups of V output
+// pixels as plane_walk.h describes, computes the four tap addresses, the validity of the taps and the two fractions of
+// each pixel once, and then loops over the channels of the block: 4 V loads and one V-wide store per channel.  V = 4
+// when the plane is a multiple of 4 floats and the destination (pointer and batch stride) is 16-byte aligned.  The
+// source is read with 4-byte loads: for the motions this is made for (a few pixels of shift, a few degrees) the lanes of
+// a wave read neighbouring addresses of two source rows, served by L1 / L2; HBM sees every source element once.
+//
+// Backward.  A thread owns one source pixel and kBwdChannels channels (their sums stay in registers).  It walks the
+// box of output pixels that may read its pixel, rows ascending, columns ascending, re-evaluates the forward's own
+// expressions for each candidate and adds weight * grad_out where one of the candidate's taps is its pixel.  For a
+// realistic motion that is at most 25 candidates and at most 4 hits.  The lanes of a wave are neighbouring source
+// pixels, so their candidates are neighbouring output pixels.  A singular or strongly shrinking transform makes the box
+// the whole plane: slow, but correct and bounded.
+#include <hip/hip_runtime.h>
+
+#include "bev_align_index.h"
+#include "launch.h"
+#include "ocrf_hip.h"
+#include "plane_walk.h"
+
+namespace {
+
+using namespace plane;
+using namespace bev_align;
+
+constexpr int kChannels = 2;                       // channels per forward unit: coordinates are computed once for them
+constexpr int kBwdChannels = 4;                    // channels per backward thread
+
+struct Taps {
+  int r0, r1, c0, c1;                              // row offsets (row * w) and columns of the taps, clamped to the plane
+  float lx, ly;
+  bool v00, v01, v10, v11;                         // the tap lies inside the plane
+};
+
+__device__ __forceinline__ Taps taps_at(const float* t, int i, int j, int h, int w) {
+  const Sample s = sample_at(t, i, j);
+  const bool x0_in = s.x0 >= 0.0f && s.x0 <= (float)(w - 1), x1_in = s.x0 >= -1.0f && s.x0 <= (float)(w - 2);
+  const bool y0_in = s.y0 >= 0.0f && s.y0 <= (float)(h - 1), y1_in = s.y0 >= -1.0f && s.y0 <= (float)(h - 2);
+  const int x0 = clamped_floor(s.x0, w), y0 = clamped_floor(s.y0, h);
+  Taps p;
+  p.c0 = max(x0, 0);
+  p.c1 = min(x0 + 1, w - 1);
+  p.r0 = max(y0, 0) * w;
+  p.r1 = min(y0 + 1, h - 1) * w;
+  p.lx = s.lx;
+  p.ly = s.ly;
+  p.v00 = x0_in && y0_in;
+  p.v01 = x1_in && y0_in;
+  p.v10 = x0_in && y1_in;
+  p.v11 = x1_in && y1_in;
+  return p;
+}
+
+__device__ __forceinline__ float sample_value(const float* __restrict__ s, const Taps& p) {
+  const float v00 = p.v00 ? s[p.r0 + p.c0] : 0.0f, v01 = p.v01 ? s[p.r0 + p.c1] : 0.0f;
+  const float v10 = p.v10 ? s[p.r1 + p.c0] : 0.0f, v11 = p.v11 ? s[p.r1 + p.c1] : 0.0f;
+  const float mx = 1.0f - p.lx, my = 1.0f - p.ly;
+  const float top = mx * v00 + p.lx * v01, bot = mx * v10 + p.lx * v11;
+  return my * top + p.ly * bot;
+}
+
+template <int V>
+__global__ void __launch_bounds__(kThreads) bev_align_kernel(int c, int h, int w, int cblocks, int chunks, int units,
+                                                             const float* __restrict__ x, const float* __restrict__ tf,
+                                                             float* __restrict__ out, long long out_batch_stride) {
+  const int P = h * w;
+  const Walk<V> walk(w);
+  for (int u = blockIdx.x; u < units; u += gridDim.x) {
+    const int rest = u / chunks, chunk = u - rest * chunks;
+    const int b = rest / cblocks, c0 = (rest - b * cblocks) * kChannels;
+    const int nc = min(kChannels, c - c0);
+    float t[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) t[k] = tf[b * 9 + k];
+    const float* s = x + ((size_t)b * c + c0) * P;
+    float* o = out + (size_t)b * out_batch_stride + (size_t)c0 * P;
+    walk.groups(walk.first(chunk), P, [&](int idx, int y, int xx) {
+      Taps p[V];
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        p[k] = taps_at(t, y, xx, h, w);
+        if (++xx == w) {
+          xx = 0;
+          ++y;                                     // past the last row only behind the group's last pixel
+        }
+      }
+#pragma unroll
+      for (int ch = 0; ch < kChannels; ++ch) {
+        if (ch < nc) {
+          const float* sc = s + ch * P;
+          float v[V];
+#pragma unroll
+          for (int k = 0; k < V; ++k) v[k] = sample_value(sc, p[k]);
+          if constexpr (V == 4) {
+            *reinterpret_cast<float4*>(o + ch * P + idx) = make_float4(v[0], v[1], v[2], v[3]);
+          } else {
+            o[ch * P + idx] = v[0];
+          }
+        }
+      }
+    });
+  }
+}
+
+// grad_x[b][ch][qy][qx] = sum over the output pixels (i, j) one of whose taps is (qx, qy) of weight * grad_out[b][ch][i][j]
+__global__ void __launch_bounds__(kThreads) bev_align_backward_kernel(int c, int h, int w, int cblocks, int total,
+                                                                      const float* __restrict__ grad_out,
+                                                                      long long grad_batch_stride,
+                                                                      const float* __restrict__ tf,
+                                                                      float* __restrict__ grad_x) {
+  const int P = h * w;
+  for (int n = blockIdx.x * kThreads + (int)threadIdx.x; n < total; n += gridDim.x * kThreads) {
+    const int rest = n / P, pix = n - rest * P;
+    const int b = rest / cblocks, c0 = (rest - b * cblocks) * kBwdChannels;
+    const int nc = min(kBwdChannels, c - c0);
+    const int qy = pix / w, qx = pix - qy * w;
+    float t[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) t[k] = tf[b * 9 + k];
+    const Box box = source_box(t, h, w, qx, qy);
+    const float fqx = (float)qx, fqy = (float)qy;
+    const float* g = grad_out + (size_t)b * grad_batch_stride + (size_t)c0 * P;
+    float acc[kBwdChannels];
+#pragma unroll
+    for (int ch = 0; ch < kBwdChannels; ++ch) acc[ch] = 0.0f;
+    for (int i = box.y0; i <= box.y1; ++i) {
+      for (int j = box.x0; j <= box.x1; ++j) {
+        const Sample s = sample_at(t, i, j);
+        const bool hit = (s.x0 == fqx || s.x0 + 1.0f == fqx) && (s.y0 == fqy || s.y0 + 1.0f == fqy);
+        if (hit) {
+          const float wgt = axis_weight(s.y0, s.ly, fqy) * axis_weight(s.x0, s.lx, fqx);
+          const float* gp = g + i * w + j;
+#pragma unroll
+          for (int ch = 0; ch < kBwdChannels; ++ch) {
+            if (ch < nc) acc[ch] += wgt * gp[ch * P];
+          }
+        }
+      }
+    }
+    float* d = grad_x + ((size_t)b * c + c0) * P + pix;
+#pragma unroll
+    for (int ch = 0; ch < kBwdChannels; ++ch) {
+      if (ch < nc) d[ch * P] = acc[ch];
+    }
+  }
+}
+
+// The shapes both entry points accept: positive sizes, the contiguous (n, c, h, w) operand and the strided one (n rows
+// of c * h * w floats, `stride` floats apart) both below 2 GiB.  *P: floats per plane
+bool shapes_ok(int n, int c, int h, int w, long long stride, long long* P) {
+  if (n <= 0 || c <= 0 || h <= 0 || w <= 0) return false;
+  const long long planes = (long long)n * c, plane = (long long)h * w;           // each below 2^62
+  const long long limit = kTwoGiB / (long long)sizeof(float);
+  if (planes >= limit || plane >= limit || planes * plane >= limit) return false;
+  const long long row = (long long)c * plane;
+  if (stride < row || stride >= limit || (n - 1) * stride + row >= limit) return false;
+  *P = plane;
+  return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ocrf_bev_align_forward(int n, int c, int h, int w, const float* x, const float* tf, float* out,
+                           long long out_batch_stride, ocrf_stream_t stream) {
+  long long P;
+  if (!shapes_ok(n, c, h, w, out_batch_stride, &P) || !x || !tf || !out) return (int)hipErrorInvalidValue;
+  const int cblocks = (c + kChannels - 1) / kChannels;
+  const bool vec = P % 4 == 0 && out_batch_stride % 4 == 0 && aligned16(out);
+  const Units u = units_of((long long)n * cblocks, P, vec);
+  if (u.units >= kTwoGiB) return (int)hipErrorInvalidValue;
+  if (vec) {
+    ocrf::launch(OCRF_K_BEV_ALIGN, bev_align_kernel<4>, dim3(u.grid), dim3(kThreads), 0, (hipStream_t)stream, c, h, w,
+                 cblocks, u.chunks, (int)u.units, x, tf, out, out_batch_stride);
+  } else {
+    ocrf::launch(OCRF_K_BEV_ALIGN, bev_align_kernel<1>, dim3(u.grid), dim3(kThreads), 0, (hipStream_t)stream, c, h, w,
+                 cblocks, u.chunks, (int)u.units, x, tf, out, out_batch_stride);
+  }
+  return (int)hipGetLastError();
+}
+
+int ocrf_bev_align_backward(int n, int c, int h, int w, const float* grad_out, long long grad_batch_stride,
+                            const float* tf, float* grad_x, ocrf_stream_t stream) {
+  long long P;
+  if (!shapes_ok(n, c, h, w, grad_batch_stride, &P) || !grad_out || !tf || !grad_x) return (int)hipErrorInvalidValue;
+  const int cblocks = (c + kBwdChannels - 1) / kBwdChannels;
+  const long long total = (long long)n * cblocks * P;                            // <= n c h w < 2^29
+  const unsigned grid = capped_grid((total + kThreads - 1) / kThreads);
+  ocrf::launch(OCRF_K_BEV_ALIGN_BWD, bev_align_backward_kernel, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, c,
+               h, w, cblocks, (int)total, grad_out, grad_batch_stride, tf, grad_x);
+  return (int)hipGetLastError();
+}
+
+int ocrf_bev_align_source_box(const float* tf, int h, int w, int qx, int qy, int* box) {
+  if (!tf || !box || h <= 0 || w <= 0) return (int)hipErrorInvalidValue;
+  const Box b = source_box(tf, h, w, qx, qy);
+  box[0] = b.x0, box[1] = b.x1, box[2] = b.y0, box[3] = b.y1;
+  return 0;
+}
+
+}  // extern "C"

@@ -156,6 +156,8 @@ const char* ocrf_kernel_name(int kernel_id) {
     case OCRF_K_ADD_RELU_BWD: return "binary_kernel<*, Threshold>";
     case OCRF_K_UPSAMPLE_ADD: return "upsample_add_kernel<*>";
     case OCRF_K_UPSAMPLE_ADD_BWD: return "upsample_add_backward_kernel";
+    case OCRF_K_BEV_ALIGN: return "bev_align_kernel<*>";
+    case OCRF_K_BEV_ALIGN_BWD: return "bev_align_backward_kernel";
     default: return "";
   }
 }

@@ -1,0 +1,294 @@
+"""Temporal BEV alignment: ``BEVDet4D.gen_grid`` / ``shift_feature`` (mmdet3d/models/detectors/bevdet.py:305-376) and the
+``torch.cat`` of the aligned frames in front of the BEV encoder (bevdet.py:529-536, ocrfdet.py:267-274), the step between
+``pre_process`` and ``BEVEncoder`` of ``BEVDet4D`` / ``BEVStereo4D`` / ``OcRFDet4D``.
+
+* ``feature_transform``: ``gen_grid``'s ``tf``, the (n, 3, 3) map from a pixel of the key frame's BEV plane to the pixel
+  of the adjacent frame's plane that shows the same place, in float64 and in closed form (torch only, no kernel);
+* ``shift_feature_torch(input, tf)``: the reference's formulation, a grid and ``F.grid_sample``;
+* ``shift_feature(input, tf, out=None)``: the same warp as one HIP launch (``csrc/bev_align.hip``), its backward a
+  gather launch without atomics: deterministic;
+* ``align_and_cat``: every frame warped (the key frame copied) straight into its channels of one concatenation;
+* ``gen_grid`` / ``shift_feature_method``: the reference's method signatures, adopted by assignment.
+
+Sampling rule of the kernels (include/ocrf_hip.h): with ``t`` the float32 rounding of rows 0 and 1 of ``tf``, output
+pixel (row i, column j) samples its source plane at ``sx = fmaf(t00, j, fmaf(t01, i, t02))``,
+``sy = fmaf(t10, j, fmaf(t11, i, t12))``, bilinearly, a tap outside the plane read as 0.  That is
+``grid_sample(bilinear, zeros, align_corners=True)`` on the reference's normalised grid without the normalise /
+unnormalise round trip; ``shift_feature_torch`` makes that round trip and differs by its rounding.
+
+Precondition: the 4 x 4 matrices of ``sensor2keyegos`` have the last row (0, 0, 0, 1), as the dataset's always have.  It
+is not checked: a check would synchronise.
+
+The ops never fall back: ``shift_feature`` raises on an input the kernels do not take.  ``align_and_cat`` and
+``shift_feature_method`` dispatch: CUDA float32 contiguous maps take the kernels (float16 maps after the cast to
+float32 that the reference's ``@force_fp32`` makes), everything else (the CPU, other dtypes, non-contiguous maps, poses
+that require a gradient) the torch formulation.
+"""
+import torch
+import torch.nn.functional as F
+
+from . import _lib
+
+# Default of the dispatch flag of align_and_cat / shift_feature_method, from the measurement in
+# profiles/bev_align_time.txt (tools/time_bev_align.py; INTEGRATION 3g has the table): on (8, 80, 128, 128) maps with 1
+# and with 8 warped frames, forward and forward + backward, the kernels are faster than the torch formulation in all four
+# cases (1.7x to 2.8x by device time, 1.06x to 1.47x by wall time, the transforms included in both).
+FUSED_ALIGN_DEFAULT = True
+
+
+# ------------------------------------------------------------------------------------------------ the transform
+def _affine(bda, pose):
+    """``bda4 . pose`` for (n, 3, 3) ``bda`` and (n, 4, 4) ``pose`` with last row (0, 0, 0, 1): its 3 x 3 block and its
+    translation."""
+    return (torch.einsum('nij,njk->nik', bda, pose[:, :3, :3]), torch.einsum('nij,nj->ni', bda, pose[:, :3, 3]))
+
+
+def _inverse3(m):
+    """Inverse of (n, 3, 3) matrices as adjugate / determinant, elementwise: cofactor (i, j) is
+    m[i+1][j+1] m[i+2][j+2] - m[i+1][j+2] m[i+2][j+1] with the indices taken modulo 3."""
+    def shifted(di, dj):
+        return torch.roll(m, shifts=(-di, -dj), dims=(1, 2))
+    cof = shifted(1, 1) * shifted(2, 2) - shifted(1, 2) * shifted(2, 1)
+    det = (m[:, 0] * cof[:, 0]).sum(-1)
+    return cof.transpose(1, 2) / det[:, None, None]
+
+
+def _pair(values, like):
+    """The first two entries of ``grid_interval`` / ``grid_lower_bound`` as float64: Python floats from a sequence or
+    a CPU tensor (the view transformer's attributes), 0-dim tensors of a device tensor (no host read)."""
+    if isinstance(values, torch.Tensor) and values.device.type != 'cpu':
+        v = values.detach().to(device=like.device, dtype=torch.float64)
+        return v[0], v[1]
+    return float(values[0]), float(values[1])
+
+
+def feature_transform(sensor2keyegos, bda, grid_interval, grid_lower_bound, bda_adj=None):
+    """``gen_grid``'s ``tf`` (bevdet.py:322-361) for ``sensor2keyegos = [curr (n, v, 4, 4), adj (n, v, 4, 4)]`` (camera 0
+    of each is read), ``bda`` (n, 3, 3) and the view transformer's ``grid_interval`` / ``grid_lower_bound``:
+
+        inv(feat2bev) . ((bda4 . curr) . inv(bda_adj4 . adj))[rows, cols (0, 1, 3)] . feat2bev        -> (n, 3, 3) float64
+
+    in float64 and in closed form: the inverse of an affine map from the adjugate of its 3 x 3 block, the conjugation
+    with ``feat2bev`` written out.  Elementwise and einsum ops on the device of the poses, no host read, differentiable.
+    Precondition: the 4 x 4 matrices have the last row (0, 0, 0, 1).  The reference computes the same in float32 with
+    two ``torch.inverse`` calls."""
+    curr, adj = sensor2keyegos[0][:, 0].double(), sensor2keyegos[1][:, 0].double()
+    bda = bda.to(device=curr.device, dtype=torch.float64)
+    bda_adj = bda if bda_adj is None else bda_adj.to(device=curr.device, dtype=torch.float64)
+    rc, tc = _affine(bda, curr)
+    ra, ta = _affine(bda_adj, adj)
+    rm = torch.einsum('nij,njk->nik', rc, _inverse3(ra))          # key ego <- adjacent ego: 3 x 3 block ...
+    tm = tc - torch.einsum('nij,nj->ni', rm, ta)                  # ... and translation
+    ix, iy = _pair(grid_interval, curr)
+    lx, ly = _pair(grid_lower_bound, curr)
+    zero, one = torch.zeros_like(tm[:, 0]), torch.ones_like(tm[:, 0])
+    # inv(feat2bev) . L . feat2bev, row by row
+    off0 = (rm[:, 0, 0] * lx + rm[:, 0, 1] * ly + tm[:, 0] - lx) / ix
+    off1 = (rm[:, 1, 0] * lx + rm[:, 1, 1] * ly + tm[:, 1] - ly) / iy
+    row0 = torch.stack([rm[:, 0, 0], rm[:, 0, 1] * iy / ix, off0], -1)
+    row1 = torch.stack([rm[:, 1, 0] * ix / iy, rm[:, 1, 1], off1], -1)
+    return torch.stack([row0, row1, torch.stack([zero, zero, one], -1)], -2)
+
+
+# ------------------------------------------------------------------------------------------------ torch formulation
+def _normalised_grid(tf, h, w, dtype):
+    """``gen_grid``'s result from ``tf``: (n, h, w, 2) sample positions normalised to [-1, 1] over (w - 1, h - 1),
+    computed in float64 and rounded once to ``dtype``."""
+    t = tf.to(torch.float64)
+    xs = torch.arange(w, dtype=torch.float64, device=t.device).view(1, 1, w)
+    ys = torch.arange(h, dtype=torch.float64, device=t.device).view(1, h, 1)
+    sx = t[:, 0, 0, None, None] * xs + t[:, 0, 1, None, None] * ys + t[:, 0, 2, None, None]
+    sy = t[:, 1, 0, None, None] * xs + t[:, 1, 1, None, None] * ys + t[:, 1, 2, None, None]
+    grid = torch.stack([sx / max(w - 1, 1) * 2.0 - 1.0, sy / max(h - 1, 1) * 2.0 - 1.0], -1)
+    return grid.to(dtype)
+
+
+def shift_feature_torch(input, tf):
+    """``shift_feature`` as the reference runs it: the normalised grid of ``tf`` (n, 3, 3), then
+    ``F.grid_sample(input, grid, align_corners=True)``.  Any device, any floating dtype, differentiable in both."""
+    n, c, h, w = input.shape
+    grid = _normalised_grid(tf.to(input.device), h, w, input.dtype)
+    return F.grid_sample(input, grid, mode='bilinear', padding_mode='zeros', align_corners=True)
+
+
+# ------------------------------------------------------------------------------------------------ the kernels
+def _plain(t):
+    """A map the kernels take, after the cast of a float16 one."""
+    return (t.is_cuda and t.dtype in (torch.float32, torch.float16) and t.is_contiguous() and t.dim() == 4
+            and t.numel() > 0)
+
+
+def _cast(t):
+    """The reference's ``@force_fp32``: a float16 map is computed in float32."""
+    return t.float() if t.dtype == torch.float16 else t
+
+
+def _tf32(tf, like):
+    """(n, 3, 3) float32 contiguous on the device of ``like``, without a gradient: what the kernels read."""
+    if tf.dim() != 3 or tuple(tf.shape) != (like.shape[0], 3, 3) or tf.device != like.device:
+        raise _lib.OcrfHipError(f'tf must be (n, 3, 3) = ({like.shape[0]}, 3, 3) on {like.device}, got '
+                                f'{tuple(tf.shape)} on {tf.device}')
+    return tf.detach().to(torch.float32).contiguous()
+
+
+def _batch_stride(t):
+    """Floats between the samples of an (n, c, h, w) view with contiguous (c, h, w) blocks (n = 1: torch's stride of a
+    dimension of size 1 means nothing)."""
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1] * t.shape[2] * t.shape[3]
+
+
+def _warp_into(x, tf32, dst):
+    """One forward launch: ``x`` (n, c, h, w) warped into ``dst``, an (n, c, h, w) view whose planes are contiguous and
+    whose samples are ``dst.stride(0)`` floats apart."""
+    n, c, h, w = x.shape
+    _lib.launch('ocrf_bev_align_forward', x.device, n, c, h, w, x, tf32, dst, _batch_stride(dst))
+
+
+def _gather_from(grad, tf32, shape):
+    """One backward launch: the gradient of the source of ``_warp_into`` from ``grad``, addressed like ``dst``."""
+    n, c, h, w = shape
+    grad_x = torch.empty(n, c, h, w, dtype=torch.float32, device=grad.device)
+    _lib.launch('ocrf_bev_align_backward', grad.device, n, c, h, w, grad, _batch_stride(grad), tf32, grad_x)
+    return grad_x
+
+
+def _sliceable(dst, like):
+    """``dst`` can take the warp of ``like``: same shape, float32, same device, contiguous (c, h, w) blocks."""
+    n, c, h, w = like.shape
+    return (dst.shape == like.shape and dst.dtype == torch.float32 and dst.device == like.device
+            and dst.stride()[1:] == (h * w, w, 1) and (n == 1 or dst.stride(0) >= c * h * w))
+
+
+class _ShiftFeature(torch.autograd.Function):
+    @staticmethod
+    @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
+    def forward(ctx, input, tf32):
+        out = torch.empty_like(input)
+        _warp_into(input, tf32, out)
+        ctx.save_for_backward(tf32)
+        ctx.shape = tuple(input.shape)
+        return out
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type='cuda')
+    def backward(ctx, grad_out):
+        tf32, = ctx.saved_tensors
+        return _gather_from(grad_out.contiguous(), tf32, ctx.shape), None
+
+
+def shift_feature(input, tf, out=None):
+    """``shift_feature_torch`` as one HIP launch (``ocrf_bev_align_forward``; backward ``ocrf_bev_align_backward``, a
+    gather): ``input`` (n, c, h, w) sampled at ``tf`` (n, 3, 3, any floating dtype, on the device of ``input``; rounded
+    to float32).  CUDA float32 contiguous input only, a float16 input is cast to float32 first (``@force_fp32``);
+    anything else raises.  ``tf`` gets no gradient.
+
+    ``out``: an (n, c, h, w) float32 view with contiguous (c, h, w) blocks, such as a channel slice of a wider
+    concatenation, to write into; it is returned.  This form records no gradient, so ``input`` must not require one."""
+    _lib.require_cuda(input, tf)
+    if not _plain(input):
+        raise _lib.OcrfHipError('shift_feature takes a non-empty contiguous float32 (or float16) NCHW map on the GPU')
+    input = _cast(input)
+    tf32 = _tf32(tf, input)
+    if out is None:
+        return _ShiftFeature.apply(input, tf32)
+    if torch.is_grad_enabled() and input.requires_grad:
+        raise _lib.OcrfHipError('shift_feature(out=...) records no gradient: detach the input, or use align_and_cat')
+    if not _sliceable(out, input):
+        raise _lib.OcrfHipError('out must be a float32 (n, c, h, w) view with contiguous (c, h, w) blocks on the '
+                                'device of the input')
+    _warp_into(input, tf32, out)
+    return out
+
+
+class _AlignCat(torch.autograd.Function):
+    """``tfs[k]`` None: ``feats[k]`` is copied; else warped with it.  One launch per warped frame, each into its channels
+    of the result."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
+    def forward(ctx, tfs, *feats):
+        B, C, H, W = feats[0].shape
+        out = torch.empty(B, len(feats) * C, H, W, dtype=torch.float32, device=feats[0].device)
+        for k, (x, tf32) in enumerate(zip(feats, tfs)):
+            dst = out[:, k * C:(k + 1) * C]
+            if tf32 is None:
+                dst.copy_(x)
+            else:
+                _warp_into(x, tf32, dst)
+        ctx.tfs = tfs                                # float32 tensors without a gradient, none of them an input
+        ctx.shape = (B, C, H, W)
+        return out
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type='cuda')
+    def backward(ctx, grad_out):
+        B, C, H, W = ctx.shape
+        grad_out = grad_out.contiguous()
+        grads = []
+        for k, tf32 in enumerate(ctx.tfs):
+            if not ctx.needs_input_grad[1 + k]:
+                grads.append(None)                   # the reference computes adjacent frames under no_grad
+            elif tf32 is None:
+                grads.append(grad_out[:, k * C:(k + 1) * C])
+            else:
+                grads.append(_gather_from(grad_out[:, k * C:(k + 1) * C], tf32, ctx.shape))
+        return (None, *grads)
+
+
+def align_fusable(feats, tfs):
+    """The kernels take these maps: CUDA float32 (or float16) contiguous, of one shape on one device, and no transform
+    that requires a gradient."""
+    first = feats[0]
+    for x in feats:
+        if not (_plain(x) and x.shape == first.shape and x.device == first.device):
+            return False
+    return not any(tf is not None and tf.requires_grad and torch.is_grad_enabled() for tf in tfs)
+
+
+def align_and_cat(feats, frame_ids, sensor2keyegos, bda, grid_interval, grid_lower_bound, bda_adj=None, fused=None):
+    """The aligned concatenation in front of the BEV encoder: ``feats`` a list of (B, C, H, W) maps, ``frame_ids[k]`` the
+    index into the per-frame list ``sensor2keyegos`` of the frame ``feats[k]`` came from.  Frame 0 is the key frame and
+    is copied; every other map is warped with ``feature_transform([sensor2keyegos[0], sensor2keyegos[frame_ids[k]]],
+    bda, ...)``.  Returns (B, len(feats) * C, H, W).
+
+    ``BEVDet4D`` (bevdet.py:529-536): ``align_and_cat(bev_feat_list, range(num_frame), ...)``; ``OcRFDet4D``
+    (ocrfdet.py:267-274), whose list runs from the oldest frame to the key frame:
+    ``align_and_cat(bev_feat_list, [num_frame - 2 - k for k in range(num_frame - 2)] + [0], ...)``.
+
+    ``fused`` (default ``FUSED_ALIGN_DEFAULT``): maps that ``align_fusable`` accepts are written by one HIP launch per
+    warped frame straight into their channels of the result, without ``torch.cat``; the backward hands a copied frame a
+    view of the incoming gradient, runs one gather launch per warped frame that requires a gradient and nothing for one
+    that does not.  Everything else takes ``shift_feature_torch`` and ``torch.cat``."""
+    frame_ids = [int(f) for f in frame_ids]
+    if len(frame_ids) != len(feats) or not feats:
+        raise ValueError('align_and_cat takes one frame id per feature map')
+    tfs = [None if fid == 0 else feature_transform([sensor2keyegos[0], sensor2keyegos[fid]], bda, grid_interval,
+                                                   grid_lower_bound, bda_adj=bda_adj) for fid in frame_ids]
+    if (FUSED_ALIGN_DEFAULT if fused is None else fused) and align_fusable(feats, tfs):
+        feats = [_cast(x) for x in feats]
+        return _AlignCat.apply(tuple(None if tf is None else _tf32(tf, feats[0]) for tf in tfs), *feats)
+    return torch.cat([x if tf is None else shift_feature_torch(_cast(x), tf) for x, tf in zip(feats, tfs)], dim=1)
+
+
+# ------------------------------------------------------------------------------------------------ drop-in methods
+def _method_transform(self, sensor2keyegos, bda, bda_adj):
+    vt = self.img_view_transformer
+    return feature_transform(sensor2keyegos, bda, vt.grid_interval, vt.grid_lower_bound, bda_adj=bda_adj)
+
+
+def gen_grid(self, input, sensor2keyegos, bda, bda_adj=None):
+    """``BEVDet4D.gen_grid`` (bevdet.py:305-370): the normalised sampling grid (n, h, w, 2) of ``input`` (n, c, h, w),
+    from ``feature_transform`` (float64, rounded once to the dtype of ``input``).  Reads
+    ``self.img_view_transformer.grid_interval`` / ``grid_lower_bound``."""
+    n, c, h, w = input.shape
+    return _normalised_grid(_method_transform(self, sensor2keyegos, bda, bda_adj).to(input.device), h, w, input.dtype)
+
+
+def shift_feature_method(self, input, sensor2keyegos, bda, bda_adj=None):
+    """``BEVDet4D.shift_feature`` (bevdet.py:372-376), adopted with ``Detector.shift_feature = shift_feature_method``.
+    With ``input`` (num_frame - 1, C, H, W) and poses repeated per frame it is the sequential test's alignment
+    (bevdet.py:401-406).  ``self.fused_align`` (default ``FUSED_ALIGN_DEFAULT``) and ``align_fusable`` dispatch."""
+    tf = _method_transform(self, sensor2keyegos, bda, bda_adj)
+    if getattr(self, 'fused_align', FUSED_ALIGN_DEFAULT) and align_fusable([input], [tf]):
+        return shift_feature(input, tf.to(input.device))
+    return shift_feature_torch(_cast(input), tf)
