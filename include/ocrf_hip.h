@@ -665,6 +665,75 @@ int ocrf_bev_align_backward(int n, int c, int h, int w, const float *grad_out, l
 int ocrf_bev_align_source_box(const float *tf, int h, int w, int qx, int qy, int *box);
 
 /* ------------------------------------------------------------------------------------------
+ * The tail of a training iteration (csrc/optim.hip): clip_grad_norm_(max_norm, norm_type=2), torch.optim.AdamW and the
+ * weight EMA of mmdet3d/core/hook/ema.py:48-60 (v *= d; v += (1 - d) * msd[k]) over ALL tensors of a model in three
+ * launches, whatever their count (configs/ocrfdet/ocrfdet.py:259-274, 329-330).  f32, contiguous tensors.
+ * Deterministic: no float atomics, the norm is summed in a fixed order, reruns give the same bits.  No host reads.
+ *
+ * The kernels read two device tables, passed as const void * and laid out as the structs below (ocrf_optim_layout
+ * reports their sizes and field offsets, so that a host packing them without this header can check itself).
+ *
+ * Static table, built once per set of tensors:
+ *   tensors   n_tensors x ocrf_optim_tensor: the device addresses of p, exp_avg, exp_avg_sq and ema, the element count n
+ *             and the mode: OCRF_OPTIM_ADAM_EMA (AdamW, then the EMA of the new p), OCRF_OPTIM_ADAM (no EMA; ema is
+ *             not read) or OCRF_OPTIM_EMA_ONLY (p is the SOURCE buffer and is only read; exp_avg / exp_avg_sq and
+ *             the tensor's gradient are not read).
+ *   chunks    n_chunks x ocrf_optim_chunk: tensor index and first element.  A chunk is the at most OCRF_OPTIM_CHUNK
+ *             elements of ONE tensor from `offset` on; offset is a multiple of OCRF_OPTIM_CHUNK.  Every element of
+ *             every tensor belongs to exactly one chunk; a tensor of 0 elements has none.  A chunk whose tensor index
+ *             or offset lies outside the tables is skipped (nothing outside the named tensors is addressed).
+ * Per-step record, step_recs: n_tensors x ocrf_optim_step_rec, entry i for tensor i: the gradient's address (0: no
+ *   gradient this step) and the scalars of that tensor's param group and step count, computed by the host in double and
+ *   rounded once to f32: decay = 1 - lr * weight_decay, one_minus_beta1, beta2, one_minus_beta2, bc2_sqrt =
+ *   sqrt(1 - beta2^step) (the DIVISOR, as torch's bias_correction2_sqrt), eps, step_size = lr / (1 - beta1^step).
+ *
+ * ocrf_optim_layout: host only.  out[0..OCRF_OPTIM_LAYOUT_INTS): sizeof and the field offsets, in declaration order,
+ *   of ocrf_optim_tensor, then ocrf_optim_chunk, then ocrf_optim_step_rec.
+ * ocrf_optim_grad_sqnorm: two launches.  partials[c] (n_chunks doubles, scratch) = sum of g * g over chunk c, each
+ *   square and sum in double, 0 for a chunk whose tensor has no gradient or is EMA_ONLY; then *total_norm (f32, device)
+ *   = sqrt(sum of the partials), the partials added in a fixed order in double.
+ * ocrf_optim_step: one launch.  Per element, in f32, every operation rounded once:
+ *     coef = min(1, max_norm / (*total_norm + 1e-6))     total_norm == NULL: no clipping, coef = 1
+ *     g    = g * coef                                     (g itself is NOT written back; clip_grad_norm_ does write it)
+ *     p    = p * decay
+ *     m    = m + one_minus_beta1 * (g - m)
+ *     v    = v * beta2 + one_minus_beta2 * g * g
+ *     p    = p - step_size * (m / (sqrt(v) / bc2_sqrt + eps))
+ *     ema  = ema * ema_decay + ema_one_minus_decay * p    EMA_ONLY: just this line
+ *   A tensor without a gradient skips the AdamW lines and still takes the EMA line.  A NaN or infinite norm propagates
+ *   as in torch: there is no check.  16-byte accesses for a chunk all of whose addresses are 16-byte aligned, 4-byte
+ *   accesses otherwise, the same arithmetic either way.
+ * Limits: NULL tables (or partials / total_norm of ocrf_optim_grad_sqnorm), n_tensors, n_chunks or max_elements <= 0,
+ *   or max_elements (the largest element count in `tensors`, stated by the caller: the kernels index a tensor with
+ *   int) of 2 GiB / 4 or more return hipErrorInvalidValue and launch nothing.
+ * The per-step record changes every step, so these entry points are not held by a step object (csrc/step.hip).
+ */
+#define OCRF_OPTIM_CHUNK 8192
+#define OCRF_OPTIM_ADAM_EMA 0
+#define OCRF_OPTIM_ADAM 1
+#define OCRF_OPTIM_EMA_ONLY 2
+#define OCRF_OPTIM_LAYOUT_INTS 19
+typedef struct ocrf_optim_tensor {
+  unsigned long long p, exp_avg, exp_avg_sq, ema; /* device addresses; 0 where the mode does not use one */
+  long long n;                                    /* elements */
+  int mode, reserved;
+} ocrf_optim_tensor;
+typedef struct ocrf_optim_chunk {
+  int tensor, offset;
+} ocrf_optim_chunk;
+typedef struct ocrf_optim_step_rec {
+  unsigned long long grad;
+  float decay, one_minus_beta1, beta2, one_minus_beta2, bc2_sqrt, eps, step_size;
+  int reserved;
+} ocrf_optim_step_rec;
+int ocrf_optim_layout(int *out);
+int ocrf_optim_grad_sqnorm(const void *tensors, int n_tensors, const void *chunks, int n_chunks, const void *step_recs,
+                           long long max_elements, double *partials, float *total_norm, ocrf_stream_t stream);
+int ocrf_optim_step(const void *tensors, int n_tensors, const void *chunks, int n_chunks, const void *step_recs,
+                    long long max_elements, const float *total_norm, float max_norm, float ema_decay,
+                    float ema_one_minus_decay, ocrf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * The memory-bound passes between the image encoder's convolutions (csrc/resnet_fuse.hip): the residual tail of a
  * ResNet block and CustomFPN's top-down step (mmdet3d/models/necks/fpn.py:190-196), one launch each.  Deterministic, no
  * atomics, no workspace, no host reads.  f32, contiguous; 16-byte accesses when every pointer is 16-byte aligned (and,
@@ -1094,7 +1163,10 @@ enum {
   OCRF_K_UPSAMPLE_ADD = 106,     /* upsample_add_kernel<V> */
   OCRF_K_UPSAMPLE_ADD_BWD = 107, /* upsample_add_backward_kernel */
   OCRF_K_BEV_ALIGN = 108,        /* bev_align_kernel<V> */
-  OCRF_K_BEV_ALIGN_BWD = 109     /* bev_align_backward_kernel */
+  OCRF_K_BEV_ALIGN_BWD = 109,    /* bev_align_backward_kernel */
+  OCRF_K_OPTIM_SQNORM = 110,     /* optim_grad_sqnorm_kernel */
+  OCRF_K_OPTIM_NORM_FINAL = 111, /* optim_norm_final_kernel */
+  OCRF_K_OPTIM_STEP = 112        /* optim_step_kernel */
 };
 const char *ocrf_kernel_name(int kernel_id);           /* symbol as rocprofv3 prints it */
 /* Diagnostic: a one-thread kernel that stores the device's constant-rate clock (wall_clock64, 100 MHz)

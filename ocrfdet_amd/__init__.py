@@ -23,6 +23,9 @@ Drop-in mirrors of the reference's Python surface for that path (and nothing els
   BEVDet4D.gen_grid / shift_feature and the       ocrfdet_amd.temporal (feature_transform, shift_feature,
   cat of the aligned frames                       align_and_cat, gen_grid, shift_feature_method, also
                                                   exported here)
+  torch.optim.AdamW + clip_grad_norm_ (mmcv's     ocrfdet_amd.optim (FusedAdamW, ModelEMA, paramwise_groups, also
+  grad_clip), ...core.hook.ema.ModelEMA, mmcv's   exported here)
+  DefaultOptimizerConstructor custom_keys
   ==============================================  =================================================
 
 Every op calls the C ABI of ``csrc/libocrf_hip.so`` (``include/ocrf_hip.h``) through ctypes with
@@ -34,16 +37,20 @@ __version__ = "0.1.0"
 _LAZY = ('ResNet', 'CustomFPN', 'ImageEncoder')
 _LAZY_TEMPORAL = ('feature_transform', 'shift_feature', 'shift_feature_torch', 'align_and_cat', 'gen_grid',
                   'shift_feature_method')
+_LAZY_OPTIM = ('FusedAdamW', 'ModelEMA', 'paramwise_groups')
 
 
 def __getattr__(name):
     """``ocrfdet_amd.ResNet`` / ``CustomFPN`` / ``ImageEncoder``: the classes of ``ocrfdet_amd.image_encoder``, imported
-    on first use, and the functions of ``ocrfdet_amd.temporal`` likewise.  There is no ``__all__``:
-    ``from ocrfdet_amd import *`` yields what it yielded before."""
+    on first use, and the functions of ``ocrfdet_amd.temporal`` and the names of ``ocrfdet_amd.optim`` likewise.  There
+    is no ``__all__``: ``from ocrfdet_amd import *`` yields what it yielded before."""
     if name in _LAZY:
         from . import image_encoder
         return getattr(image_encoder, name)
     if name in _LAZY_TEMPORAL:
         from . import temporal
         return getattr(temporal, name)
+    if name in _LAZY_OPTIM:
+        from . import optim
+        return getattr(optim, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -158,6 +158,9 @@ const char* ocrf_kernel_name(int kernel_id) {
     case OCRF_K_UPSAMPLE_ADD_BWD: return "upsample_add_backward_kernel";
     case OCRF_K_BEV_ALIGN: return "bev_align_kernel<*>";
     case OCRF_K_BEV_ALIGN_BWD: return "bev_align_backward_kernel";
+    case OCRF_K_OPTIM_SQNORM: return "optim_grad_sqnorm_kernel";
+    case OCRF_K_OPTIM_NORM_FINAL: return "optim_norm_final_kernel";
+    case OCRF_K_OPTIM_STEP: return "optim_step_kernel";
     default: return "";
   }
 }
