@@ -533,6 +533,9 @@ int ocrf_stereo_cost_volume(int BN, int C, int H, int W, int D, const float *pre
  *   (device): heatmap = the tasks' (B, ncls[t], H, W) blocks back to back, anno_box (T, B, max_objs, 10 | 8), ind
  *   (T, B, max_objs) int64, mask (T, B, max_objs) uint8, counts[2T] f32 = per task the heatmap pixels equal to 1 and
  *   the mask sum.  A memset of counts and two launches; workspace from ocrf_center_head_targets_workspace_bytes.
+ *   A label outside [0, n_labels) is in no task.  radius = max(min_radius, (int)r) of the float32 gaussian_radius r,
+ *   with two rules of this library's: a NaN r (an infinite box dimension; the reference raises there) counts as 0, so
+ *   the radius falls to min_radius, and r is capped at 65536.
  * ocrf_center_head_heatmap_loss: logits[T] (host table of device (B, ncls[t], HW) f32) against the targets' heatmap ->
  *   clipped[T] (clip_sigmoid, same shapes), out[T] = loss_weight * gaussian focal sum / (float)(max(counts[t], 1) +
  *   FLT_EPSILON) and dens[T] for the backward.  Two launches; workspace from ..._heatmap_loss_workspace_bytes.
@@ -545,6 +548,8 @@ int ocrf_stereo_cost_volume(int BN, int C, int H, int W, int D, const float *pre
  *   launches; workspace from ocrf_center_head_reg_loss_workspace_bytes.
  * ocrf_center_head_reg_loss_backward: grad_out (T, 6) (device) -> grad_heads[5T] (host table, zero-filled by the
  *   caller): only the pixels at ind are written, duplicate indices summed in slot order.  One launch, max_objs <= 16384.
+ *   The sign of pred - target is 0 where it is NaN, as autograd's abs has it: a NaN target code (weight 0) makes its
+ *   loss NaN and its gradient 0, and leaves every other gradient finite.
  */
 #define OCRF_CH_MAX_TASKS 8
 #define OCRF_CH_MAX_PLANES 64

@@ -105,7 +105,8 @@ __global__ void __launch_bounds__(kThreads) ch_assign_kernel(TargetArgs a) {
       const float width = __fdiv_rn(__fdiv_rn(bx[3], a.vs0), a.osf);
       const float length = __fdiv_rn(__fdiv_rn(bx[4], a.vs1), a.osf);
       if (k < a.M && width > 0.0f && length > 0.0f) {
-        const int radius = max(a.min_radius, (int)fminf(gaussian_radius_f32(a, length, width), 65536.0f));
+        const float rf = gaussian_radius_f32(a, length, width);   // NaN (an infinite dimension) counts as 0
+        const int radius = max(a.min_radius, rf == rf ? (int)fminf(rf, 65536.0f) : 0);
         const float cx = __fdiv_rn(__fdiv_rn(bx[0] - a.pc0, a.vs0), a.osf);
         const float cy = __fdiv_rn(__fdiv_rn(bx[1] - a.pc1, a.vs1), a.osf);
         const int ix = (int)cx, iy = (int)cy;  // .to(torch.int32): toward zero
@@ -367,7 +368,7 @@ __global__ void __launch_bounds__(kThreads) ch_reg_loss_backward_kernel(RegArgs 
         const float tgt = a.anno[(row0 + j) * a.C + c];
         const float wt = reg_weight(a, a.mask[row0 + j], tgt, c);
         const float d = p - tgt;
-        const float sg = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : (d == d ? 0.0f : d));
+        const float sg = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);   // sgn(NaN) = 0, as autograd's abs
         acc += (base_g[kCodeGroup[c]] * wt) * sg + (base_all * wt) * sg;
       }
       const int h = kCodeHead[c];
