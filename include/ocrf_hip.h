@@ -763,6 +763,32 @@ int ocrf_upsample_add_forward(int B, int C, int Hin, int Win, int Hout, int Wout
                               float *out, ocrf_stream_t stream);
 int ocrf_upsample_add_backward(int B, int C, int Hin, int Win, int Hout, int Wout, const float *grad_out,
                                float *grad_src, ocrf_stream_t stream);
+/*
+ * The same four passes on bfloat16 data, for the encoder under bf16 autocast: every operand and result is bf16, passed
+ * as unsigned short (the upper half of the f32 with the same value), contiguous.  16-byte accesses (8 elements) when
+ * every pointer accessed by groups is 16-byte aligned (and, for ocrf_upsample_add_forward_bf16, the destination plane a
+ * multiple of 8 elements); 2-byte accesses otherwise.  Deterministic, no atomics, no workspace, no host reads.
+ *
+ * Arithmetic, that of torch's bf16 element-wise ops: both operands widened to f32 (exact), ONE f32 addition, ONE
+ * rounding to bf16, to nearest even.  A NaN stays a NaN; which NaN is not specified.
+ * ocrf_add_relu_forward_bf16: out[i] = relu(bf16(a[i] + b[i])), the ReLU on the rounded sum s as `s < 0 ? 0 : s` (a NaN
+ *   sum stays NaN).
+ * ocrf_add_relu_backward_bf16: grad[i] = out[i] <= 0 ? 0 : grad_out[i], a select: grad_out's bits pass unchanged, a
+ *   NaN out passes the gradient.
+ * ocrf_upsample_add_forward_bf16: out = bf16(dst + nearest(src)) with the index rule of ocrf_upsample_add_forward.
+ * ocrf_upsample_add_backward_bf16: per source pixel the sum of its run in the order of ocrf_upsample_add_backward (rows
+ *   ascending, columns ascending inside a row) into one f32 accumulator, rounded once to bf16.
+ * Limits: those of the f32 entry points, every operand below 2 GiB included (n < 2^30 elements); anything else returns
+ *   hipErrorInvalidValue and launches nothing.
+ */
+int ocrf_add_relu_forward_bf16(long long n, const unsigned short *a, const unsigned short *b, unsigned short *out,
+                               ocrf_stream_t stream);
+int ocrf_add_relu_backward_bf16(long long n, const unsigned short *grad_out, const unsigned short *out,
+                                unsigned short *grad, ocrf_stream_t stream);
+int ocrf_upsample_add_forward_bf16(int B, int C, int Hin, int Win, int Hout, int Wout, const unsigned short *dst,
+                                   const unsigned short *src, unsigned short *out, ocrf_stream_t stream);
+int ocrf_upsample_add_backward_bf16(int B, int C, int Hin, int Win, int Hout, int Wout, const unsigned short *grad_out,
+                                    unsigned short *grad_src, ocrf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Index preparation of the two poolings on the device (csrc/index_prep.hip).
@@ -1171,7 +1197,11 @@ enum {
   OCRF_K_BEV_ALIGN_BWD = 109,    /* bev_align_backward_kernel */
   OCRF_K_OPTIM_SQNORM = 110,     /* optim_grad_sqnorm_kernel */
   OCRF_K_OPTIM_NORM_FINAL = 111, /* optim_norm_final_kernel */
-  OCRF_K_OPTIM_STEP = 112        /* optim_step_kernel */
+  OCRF_K_OPTIM_STEP = 112,       /* optim_step_kernel */
+  OCRF_K_ADD_RELU_BF16 = 113,     /* binary_bf16_kernel<V, AddRelu> */
+  OCRF_K_ADD_RELU_BWD_BF16 = 114, /* binary_bf16_kernel<V, Threshold> */
+  OCRF_K_UPSAMPLE_ADD_BF16 = 115, /* upsample_add_bf16_kernel<V> */
+  OCRF_K_UPSAMPLE_ADD_BWD_BF16 = 116 /* upsample_add_backward_bf16_kernel */
 };
 const char *ocrf_kernel_name(int kernel_id);           /* symbol as rocprofv3 prints it */
 /* Diagnostic: a one-thread kernel that stores the device's constant-rate clock (wall_clock64, 100 MHz)

@@ -5,14 +5,16 @@
 them; ``tests/resnet_oracle.py`` is an independent float64 evaluation of the blocks from the ``state_dict`` alone.
 
 The residual tail ``relu(out + identity)`` of a block is ``plane_ops.add_relu`` (one HIP launch) for CUDA float32
-contiguous maps while the block's ``fused_tail`` is True, else ``add_relu_torch``.  ``with_cp=True`` checkpoints the
-whole block (tail included) in the non-reentrant form.
+contiguous maps while the block's ``fused_tail`` is True, else ``add_relu_torch``.  Under bf16 autocast ``out`` and
+``identity`` are both bfloat16 and take the op's bf16 kernels while ``fused_tail_bf16`` is True as well; a mixed pair
+stays on torch, which promotes.  ``with_cp=True`` checkpoints the whole block (tail included) in the non-reentrant form.
 """
+import torch
 from torch import nn
 from torch.nn.modules.batchnorm import _BatchNorm
 from torch.utils.checkpoint import checkpoint
 
-from .plane_ops import FUSED_TAIL_DEFAULT, add_relu, add_relu_fusable, add_relu_torch
+from .plane_ops import FUSED_TAIL_BF16_DEFAULT, FUSED_TAIL_DEFAULT, add_relu, add_relu_fusable, add_relu_torch
 
 
 def build_norm(norm_cfg, channels):
@@ -57,10 +59,12 @@ def kaiming_init(module, mode='fan_out'):
 class _Block(nn.Module):
     """What the two mmdet 2.x blocks share: the ``norm{i}`` properties, checkpointing and the residual tail."""
     fused_tail = FUSED_TAIL_DEFAULT
+    fused_tail_bf16 = FUSED_TAIL_BF16_DEFAULT      # bfloat16 operands take the op too (only while fused_tail is on)
     with_cp = False
 
     def _tail(self, out, identity):
-        if self.fused_tail and add_relu_fusable(out, identity):
+        if (self.fused_tail and (self.fused_tail_bf16 or out.dtype != torch.bfloat16)
+                and add_relu_fusable(out, identity)):
             return add_relu(out, identity)
         return add_relu_torch(out, identity)
 
@@ -137,6 +141,13 @@ class Bottleneck(_Block):
         out = self.relu(self.bn2(self.conv2(out)))
         out = self.bn3(self.conv3(out))
         return self._tail(out, identity)
+
+
+def fuse_bf16_tails(module, flag=True):
+    """Set ``fused_tail_bf16`` on every block inside ``module``."""
+    for m in module.modules():
+        if isinstance(m, _Block):
+            m.fused_tail_bf16 = bool(flag)
 
 
 def unfuse_tails(module):

@@ -13,6 +13,9 @@ post_max_size:
   ``head.fused_decode = False``.  Vectorised over samples, tasks and boxes; its greedy scan loops over candidate rank
   for every (sample, task) at once and reads nothing back.
 
+bfloat16 head outputs (bf16 autocast) are cast to float32 first (``bf16_as_float32``), so they decode in float32 on
+either path; float16 ones take the torch formulation as they are.
+
 Rules both keep:
 
 * ties: equal scores go in ascending (class, cell) order and every later sort is stable;
@@ -382,6 +385,15 @@ def decode_torch(preds_dicts, cfg, norm_bbox=True):
 
 
 # --------------------------------------------------------------------------------------------- fused
+def bf16_as_float32(preds_dicts):
+    """``preds_dicts`` with every bfloat16 head output (a head that ran under bf16 autocast) cast to float32, in new
+    dicts; the same object when there is none.  float16 outputs stay as they are."""
+    if not any(v.dtype == torch.bfloat16 for p in preds_dicts for k, v in p[0].items() if k in HEAD_KEYS):
+        return preds_dicts
+    return [[{k: v.float() if k in HEAD_KEYS and v.dtype == torch.bfloat16 else v for k, v in p[0].items()}]
+            for p in preds_dicts]
+
+
 def fused_ok(preds_dicts):
     ts = [v for p in preds_dicts for k, v in p[0].items() if k in HEAD_KEYS]
     return all(t.is_cuda and t.dtype == torch.float32 for t in ts) and all('reg' in p[0] for p in preds_dicts)

@@ -12,6 +12,10 @@ The training path (``get_targets`` + ``loss``) has two formulations of the same 
 * the torch one (``*_torch``) -- the CPU path, and the fallback when ``fused_loss`` is False or an input is not float32.
   It is vectorised over boxes (no per-object Python loop) and reads nothing back to the host.
 
+bfloat16 head outputs (``forward`` under bf16 autocast) are cast to float32 in ``loss`` and ``get_bboxes``: they take
+the fused kernels, losses and boxes are float32, and autograd's cast hands a bf16 prediction a bf16 gradient.  The
+reference runs the head's loss in whatever dtype arrives; float16 outputs keep the torch formulation.
+
 Both keep the reference's integer outcomes (slot, radius, centre cell) and heatmap values bit for bit: the radius in
 float32 in the reference's operation order, the Gaussian in float64 as numpy computes it.
 
@@ -507,11 +511,12 @@ class CenterHead(nn.Module):
     def loss(self, gt_bboxes_3d, gt_labels_3d, preds_dicts, **kwargs):
         """The reference's loss dict: task{i}.loss_{xy,z,whl,yaw,vel,heatmap}, or 'loss' without task_specific."""
         B = len(gt_labels_3d)
-        logits = [p[0]['heatmap'] for p in preds_dicts]
+        cast = cd.bf16_as_float32(preds_dicts)      # read from these; the caller's dicts get 'heatmap' and 'anno_box'
+        logits = [p[0]['heatmap'] for p in cast]
         heat, anno, ind, mask, counts = self._targets(gt_bboxes_3d, gt_labels_3d, device=logits[0].device)
         counts = reduce_counts(counts)
         T = len(self.num_classes)
-        heads = [[p[0].get(k) for k in HEADS] for p in preds_dicts]
+        heads = [[p[0].get(k) for k in HEADS] for p in cast]
         w_cls = float(self.loss_cls_cfg.get('loss_weight', 1.0))
         w_box = float(self.loss_bbox_cfg.get('loss_weight', 1.0))
         cw = list(self.train_cfg['code_weights'])
@@ -533,7 +538,7 @@ class CenterHead(nn.Module):
         else:
             clipped, hm = heatmap_loss_torch(logits, self._split_heat(heat, B), counts, w_cls)
             regs = [reg_loss_torch(p[0], anno[t], ind[t], mask[t], counts[T + t], cw, w_box, self.task_specific, red)
-                    for t, p in enumerate(preds_dicts)]
+                    for t, p in enumerate(cast)]
         loss_dict = dict()
         if not self.task_specific:
             loss_dict['loss'] = 0
@@ -562,6 +567,7 @@ class CenterHead(nn.Module):
         bottom-centre z, scores (B, M) f32, labels (B, M) int32 and counts (B,) int32, M = T * post_max_size; rows past
         a sample's count are zero."""
         cfg = self._decode_cfg()
+        preds_dicts = cd.bf16_as_float32(preds_dicts)
         if self.fused_decode and cd.fused_ok(preds_dicts):
             return cd.decode_fused(preds_dicts, cfg, self.norm_bbox)
         return cd.decode_torch(preds_dicts, cfg, self.norm_bbox)

@@ -175,7 +175,7 @@ int ocrf_bev_align_forward(int n, int c, int h, int w, const float* x, const flo
   if (!shapes_ok(n, c, h, w, out_batch_stride, &P) || !x || !tf || !out) return (int)hipErrorInvalidValue;
   const int cblocks = (c + kChannels - 1) / kChannels;
   const bool vec = P % 4 == 0 && out_batch_stride % 4 == 0 && aligned16(out);
-  const Units u = units_of((long long)n * cblocks, P, vec);
+  const Units u = units_of((long long)n * cblocks, P, vec ? 4 : 1);
   if (u.units >= kTwoGiB) return (int)hipErrorInvalidValue;
   if (vec) {
     ocrf::launch(OCRF_K_BEV_ALIGN, bev_align_kernel<4>, dim3(u.grid), dim3(kThreads), 0, (hipStream_t)stream, c, h, w,

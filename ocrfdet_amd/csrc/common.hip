@@ -161,6 +161,10 @@ const char* ocrf_kernel_name(int kernel_id) {
     case OCRF_K_OPTIM_SQNORM: return "optim_grad_sqnorm_kernel";
     case OCRF_K_OPTIM_NORM_FINAL: return "optim_norm_final_kernel";
     case OCRF_K_OPTIM_STEP: return "optim_step_kernel";
+    case OCRF_K_ADD_RELU_BF16: return "binary_bf16_kernel<*, AddRelu>";
+    case OCRF_K_ADD_RELU_BWD_BF16: return "binary_bf16_kernel<*, Threshold>";
+    case OCRF_K_UPSAMPLE_ADD_BF16: return "upsample_add_bf16_kernel<*>";
+    case OCRF_K_UPSAMPLE_ADD_BWD_BF16: return "upsample_add_backward_bf16_kernel";
     default: return "";
   }
 }

@@ -9,6 +9,10 @@
 // multiple of 4: the column wraps inside the group).  V = 1 otherwise: the same code with 4-byte accesses.  The kernels
 // index with int, so every operand stays below 2 GiB, and they keep one table entry per row and per column in LDS, so
 // Hout + Wout stays within kMaxAxisSum.
+//
+// The width of an access is counted in bytes: with 16-bit elements (bf16, passed as unsigned short) a 16-byte group is
+// V = 8 elements, P has to be a multiple of 8 for it, and the narrow form is a 2-byte access.  Walk<V> counts in
+// elements and does not care what they are.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -33,26 +37,38 @@ struct Vec<1> {
   using type = float;
 };
 
+// the same for 16-bit elements: 8 of them in one 16-byte access, or one
+template <int V>
+struct Vec16;
+template <>
+struct Vec16<8> {
+  using type = uint4;
+};
+template <>
+struct Vec16<1> {
+  using type = unsigned short;
+};
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-// `planes` destination planes of Hout x Wout floats: the tables fit, and the destination-sized operands (the largest)
-// stay below 2 GiB
-inline bool planes_ok(long long planes, long long Hout, long long Wout) {
+// `planes` destination planes of Hout x Wout elements of `elem_bytes` each: the tables fit, and the destination-sized
+// operands (the largest) stay below 2 GiB
+inline bool planes_ok(long long planes, long long Hout, long long Wout, long long elem_bytes = sizeof(float)) {
   if (Hout + Wout > kMaxAxisSum) return false;
-  return planes < kTwoGiB && planes * Hout * Wout * (long long)sizeof(float) < kTwoGiB;
+  return planes < kTwoGiB && planes * Hout * Wout * elem_bytes < kTwoGiB;
 }
 
 inline unsigned capped_grid(long long blocks) { return (unsigned)(blocks < kMaxBlocks ? blocks : kMaxBlocks); }
 
-// launch geometry of a forward walk over `planes` planes of P floats
+// launch geometry of a forward walk over `planes` planes of P elements in groups of V
 struct Units {
   int chunks;                                      // per plane
   long long units;                                 // planes * chunks, < 2^29 + planes
   unsigned grid;
 };
 
-inline Units units_of(long long planes, long long P, bool vec) {
-  const int per_unit = kThreads * kGroups * (vec ? 4 : 1);
+inline Units units_of(long long planes, long long P, int V) {
+  const int per_unit = kThreads * kGroups * V;
   Units n;
   n.chunks = (int)((P + per_unit - 1) / per_unit);
   n.units = planes * n.chunks;

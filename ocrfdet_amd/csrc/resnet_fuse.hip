@@ -31,6 +31,15 @@
 // first destination of every source index sits in LDS (Hin + 1 + Win + 1 ints); a thread sums its run of rows, and
 // inside a row its run of columns, in ascending order into one float32 accumulator.  The lanes of a wave read
 // neighbouring runs of the same destination rows, so every fetched line is used in full.
+//
+// bfloat16 (the *_bf16 entry points, for the encoder under bf16 autocast).  The same four passes on bf16 data, passed as
+// unsigned short.  Arithmetic as torch's bf16 element-wise ops: widen both operands to float32 (a shift: exact), one
+// float32 addition, one rounding to bf16 to nearest even (the compiler's float -> __bf16 conversion: v_cvt_pk_bf16_f32
+// on gfx950, two values per instruction); the ReLU tests the rounded sum, the threshold is a select on grad_out's bits.
+// The layout is the same with the access width counted in bytes: a 16-byte group is V = 8 elements, the tail is n % 8
+// elements, the narrow form a 2-byte access; upsample_add's wide path needs P % 8 == 0.  A thread of the wide path
+// works on four 32-bit words of two bf16 each.  The backward keeps one thread per source pixel and one float32
+// accumulator, and rounds once.
 #include <hip/hip_runtime.h>
 
 #include "launch.h"
@@ -72,11 +81,10 @@ struct Threshold {                                 // (grad_out, out) -> grad
   }
 };
 
-// out[i] = op(p[i], q[i]) for i in [0, n): groups = n / V whole groups, chunks of kThreads * kGroups of them
-template <int V, typename Op>
-__global__ void __launch_bounds__(kThreads) binary_kernel(int n, int groups, int chunks, const float* __restrict__ p,
-                                                           const float* __restrict__ q, float* __restrict__ out) {
-  using VT = typename Vec<V>::type;
+// out[i] = op(p[i], q[i]) for i in [0, n): groups = n / V whole groups of type VT, chunks of kThreads * kGroups of them
+template <int V, typename VT, typename Op, typename T>
+__device__ __forceinline__ void binary_body(int n, int groups, int chunks, const T* __restrict__ p,
+                                            const T* __restrict__ q, T* __restrict__ out) {
   const Op op;
   const VT* pv = reinterpret_cast<const VT*>(p);
   const VT* qv = reinterpret_cast<const VT*>(q);
@@ -98,10 +106,64 @@ __global__ void __launch_bounds__(kThreads) binary_kernel(int n, int groups, int
       if (idx < groups) ov[idx] = op(x[g], y[g]);
     }
   }
-  if constexpr (V > 1) {                           // the n % V floats behind the last whole group
+  if constexpr (V > 1) {                           // the n % V elements behind the last whole group
     const int i = groups * V + (int)threadIdx.x;
     if (blockIdx.x == 0 && i < n) out[i] = op(p[i], q[i]);
   }
+}
+
+template <int V, typename Op>
+__global__ void __launch_bounds__(kThreads) binary_kernel(int n, int groups, int chunks, const float* __restrict__ p,
+                                                           const float* __restrict__ q, float* __restrict__ out) {
+  binary_body<V, typename Vec<V>::type, Op>(n, groups, chunks, p, q, out);
+}
+
+// ---------------------------------------------------------------------------------------------- bf16 arithmetic
+using bf16_t = unsigned short;
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ float widen(bf16_t h) { return __uint_as_float((unsigned)h << 16); }
+__device__ __forceinline__ float widen_lo(unsigned w) { return __uint_as_float(w << 16); }          // element 0 of a word
+__device__ __forceinline__ float widen_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }  // element 1
+// float32 -> bf16, to nearest even; a NaN stays a NaN
+__device__ __forceinline__ bf16_t round_one(float f) { return __builtin_bit_cast(bf16_t, (__bf16)f); }
+__device__ __forceinline__ unsigned round_pair(float lo, float hi) {
+  const f32x2 f = {lo, hi};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2));
+}
+
+struct AddReluBf16 {
+  __device__ __forceinline__ bf16_t operator()(bf16_t a, bf16_t b) const {
+    const bf16_t s = round_one(widen(a) + widen(b));
+    return widen(s) < 0.0f ? (bf16_t)0 : s;        // on the rounded sum; NaN < 0 is false
+  }
+  __device__ __forceinline__ unsigned operator()(unsigned a, unsigned b) const {
+    const unsigned s = round_pair(widen_lo(a) + widen_lo(b), widen_hi(a) + widen_hi(b));
+    return (widen_lo(s) < 0.0f ? 0u : s & 0xffffu) | (widen_hi(s) < 0.0f ? 0u : s & 0xffff0000u);
+  }
+  __device__ __forceinline__ uint4 operator()(uint4 a, uint4 b) const {
+    return make_uint4((*this)(a.x, b.x), (*this)(a.y, b.y), (*this)(a.z, b.z), (*this)(a.w, b.w));
+  }
+};
+struct ThresholdBf16 {                             // (grad_out, out) -> grad: grad_out's bits or zero
+  __device__ __forceinline__ bf16_t operator()(bf16_t g, bf16_t o) const {
+    return widen(o) <= 0.0f ? (bf16_t)0 : g;       // NaN <= 0 is false: a NaN out passes the gradient
+  }
+  __device__ __forceinline__ unsigned operator()(unsigned g, unsigned o) const {
+    return (widen_lo(o) <= 0.0f ? 0u : g & 0xffffu) | (widen_hi(o) <= 0.0f ? 0u : g & 0xffff0000u);
+  }
+  __device__ __forceinline__ uint4 operator()(uint4 g, uint4 o) const {
+    return make_uint4((*this)(g.x, o.x), (*this)(g.y, o.y), (*this)(g.z, o.z), (*this)(g.w, o.w));
+  }
+};
+
+template <int V, typename Op>
+__global__ void __launch_bounds__(kThreads) binary_bf16_kernel(int n, int groups, int chunks,
+                                                                const bf16_t* __restrict__ p,
+                                                                const bf16_t* __restrict__ q,
+                                                                bf16_t* __restrict__ out) {
+  binary_body<V, typename Vec16<V>::type, Op>(n, groups, chunks, p, q, out);
 }
 
 // torch's mode='nearest' source index of destination index d
@@ -144,6 +206,45 @@ __global__ void __launch_bounds__(kThreads) upsample_add_kernel(int Hin, int Win
   }
 }
 
+// the same walk over bf16 planes: V = 8 is one 16-byte access of four words
+template <int V>
+__global__ void __launch_bounds__(kThreads) upsample_add_bf16_kernel(int Hin, int Win, int Hout, int Wout, int chunks,
+                                                                      int units, const bf16_t* __restrict__ dst,
+                                                                      const bf16_t* __restrict__ src,
+                                                                      bf16_t* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  int* tab_y = reinterpret_cast<int*>(lds_raw);    // as in upsample_add_kernel
+  int* tab_x = tab_y + Hout;
+  for (int i = threadIdx.x; i < Hout + Wout; i += kThreads) {
+    tab_y[i] = i < Hout ? nearest_index(i, Hin, Hout) * Win : nearest_index(i - Hout, Win, Wout);
+  }
+  __syncthreads();
+  const int P = Hout * Wout, Pin = Hin * Win;
+  const Walk<V> walk(Wout);
+  for (int u = blockIdx.x; u < units; u += gridDim.x) {
+    const int plane = u / chunks, chunk = u - plane * chunks;
+    const int first = walk.first(chunk);
+    const bf16_t* d = dst + (size_t)plane * P;
+    const bf16_t* s = src + (size_t)plane * Pin;
+    bf16_t* o = out + (size_t)plane * P;
+    walk.groups(first, P, [&](int idx, int y, int x) {
+      float v[V];
+      if constexpr (V == 8) {
+        const uint4 dv = *reinterpret_cast<const uint4*>(d + idx);
+        walk.values(v, y, x, [&](int yy, int xx) { return widen(s[tab_y[yy] + tab_x[xx]]); });
+        *reinterpret_cast<uint4*>(o + idx) = make_uint4(round_pair(widen_lo(dv.x) + v[0], widen_hi(dv.x) + v[1]),
+                                                        round_pair(widen_lo(dv.y) + v[2], widen_hi(dv.y) + v[3]),
+                                                        round_pair(widen_lo(dv.z) + v[4], widen_hi(dv.z) + v[5]),
+                                                        round_pair(widen_lo(dv.w) + v[6], widen_hi(dv.w) + v[7]));
+      } else {
+        const bf16_t dv = d[idx];
+        walk.values(v, y, x, [&](int yy, int xx) { return widen(s[tab_y[yy] + tab_x[xx]]); });
+        o[idx] = round_one(widen(dv) + v[0]);
+      }
+    });
+  }
+}
+
 // start[i], i in [0, in]: the first destination index whose source index is >= i (start[in] = out), so that the
 // destinations of source index i are [start[i], start[i + 1])
 __device__ __forceinline__ void build_starts(int* start, int in, int out) {
@@ -154,10 +255,14 @@ __device__ __forceinline__ void build_starts(int* start, int in, int out) {
   }
 }
 
-__global__ void __launch_bounds__(kThreads) upsample_add_backward_kernel(int Hin, int Win, int Hout, int Wout,
-                                                                          int total,
-                                                                          const float* __restrict__ grad_out,
-                                                                          float* __restrict__ grad_src) {
+__device__ __forceinline__ float load_f32(const float* p) { return *p; }
+__device__ __forceinline__ float load_f32(const bf16_t* p) { return widen(*p); }
+__device__ __forceinline__ void store_f32(float* p, float v) { *p = v; }
+__device__ __forceinline__ void store_f32(bf16_t* p, float v) { *p = round_one(v); }
+
+template <typename T>
+__device__ __forceinline__ void upsample_add_backward_body(int Hin, int Win, int Hout, int Wout, int total,
+                                                           const T* __restrict__ grad_out, T* __restrict__ grad_src) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   int* start_y = reinterpret_cast<int*>(lds_raw);  // Hin + 1 entries
   int* start_x = start_y + Hin + 1;                // Win + 1 entries
@@ -168,42 +273,58 @@ __global__ void __launch_bounds__(kThreads) upsample_add_backward_kernel(int Hin
   for (int i = blockIdx.x * kThreads + (int)threadIdx.x; i < total; i += gridDim.x * kThreads) {
     const int plane = i / Pin, pix = i - plane * Pin;
     const int iy = pix / Win, ix = pix - iy * Win;
-    const float* g = grad_out + (size_t)plane * P;
+    const T* g = grad_out + (size_t)plane * P;
     const int y0 = start_y[iy], y1 = start_y[iy + 1], x0 = start_x[ix], x1 = start_x[ix + 1];
     float acc = 0.0f;
     for (int oy = y0; oy < y1; ++oy) {
-      const float* row = g + oy * Wout;
-      for (int ox = x0; ox < x1; ++ox) acc += row[ox];
+      const T* row = g + oy * Wout;
+      for (int ox = x0; ox < x1; ++ox) acc += load_f32(row + ox);
     }
-    grad_src[i] = acc;
+    store_f32(grad_src + i, acc);
   }
 }
 
-template <typename Op>
-int launch_binary(int kernel_id, long long n, const float* p, const float* q, float* out, ocrf_stream_t stream) {
+__global__ void __launch_bounds__(kThreads) upsample_add_backward_kernel(int Hin, int Win, int Hout, int Wout,
+                                                                          int total,
+                                                                          const float* __restrict__ grad_out,
+                                                                          float* __restrict__ grad_src) {
+  upsample_add_backward_body(Hin, Win, Hout, Wout, total, grad_out, grad_src);
+}
+
+__global__ void __launch_bounds__(kThreads) upsample_add_backward_bf16_kernel(int Hin, int Win, int Hout, int Wout,
+                                                                               int total,
+                                                                               const bf16_t* __restrict__ grad_out,
+                                                                               bf16_t* __restrict__ grad_src) {
+  upsample_add_backward_body(Hin, Win, Hout, Wout, total, grad_out, grad_src);
+}
+
+// `wide`: the kernel with groups of kWide elements (16 bytes), `narrow`: the same with one element per access
+template <int kWide, typename T, typename Kernel>
+int launch_binary(int kernel_id, Kernel wide, Kernel narrow, long long n, const T* p, const T* q, T* out,
+                  ocrf_stream_t stream) {
   // every operand below 2 GiB: the kernels index with int
-  if (n <= 0 || n * (long long)sizeof(float) >= kTwoGiB) return (int)hipErrorInvalidValue;
+  if (n <= 0 || n * (long long)sizeof(T) >= kTwoGiB) return (int)hipErrorInvalidValue;
   if (!p || !q || !out) return (int)hipErrorInvalidValue;
   const bool vec = aligned16(p) && aligned16(q) && aligned16(out);
-  const int V = vec ? 4 : 1;
+  const int V = vec ? kWide : 1;
   const int groups = (int)(n / V);
   const int per_chunk = kThreads * kGroups;
-  const int chunks = (groups + per_chunk - 1) / per_chunk;         // 0 for n < 4 with V = 4: the tail lanes alone
+  const int chunks = (groups + per_chunk - 1) / per_chunk;         // 0 for n < V on the wide path: the tail lanes alone
   const unsigned grid = capped_grid(chunks < 1 ? 1 : chunks);
   if (vec) {
-    ocrf::launch(kernel_id, binary_kernel<4, Op>, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, (int)n, groups,
-                 chunks, p, q, out);
+    ocrf::launch(kernel_id, wide, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, (int)n, groups, chunks, p, q, out);
   } else {
-    ocrf::launch(kernel_id, binary_kernel<1, Op>, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, (int)n, groups,
-                 chunks, p, q, out);
+    ocrf::launch(kernel_id, narrow, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, (int)n, groups, chunks, p, q,
+                 out);
   }
   return (int)hipGetLastError();
 }
 
-// the shapes both upsample_add entry points accept; *P / *Pin: floats per destination / source plane
-bool shapes_ok(int B, int C, int Hin, int Win, int Hout, int Wout, long long* P, long long* Pin) {
+// the shapes the upsample_add entry points accept; *P / *Pin: elements (of elem_bytes) per destination / source plane
+bool shapes_ok(int B, int C, int Hin, int Win, int Hout, int Wout, long long* P, long long* Pin,
+               long long elem_bytes = sizeof(float)) {
   if (B <= 0 || C <= 0 || Hin <= 0 || Win <= 0 || Hout < Hin || Wout < Win) return false;
-  if (!planes_ok((long long)B * C, Hout, Wout)) return false;
+  if (!planes_ok((long long)B * C, Hout, Wout, elem_bytes)) return false;
   *P = (long long)Hout * Wout;
   *Pin = (long long)Hin * Win;
   return true;
@@ -214,11 +335,12 @@ bool shapes_ok(int B, int C, int Hin, int Win, int Hout, int Wout, long long* P,
 extern "C" {
 
 int ocrf_add_relu_forward(long long n, const float* a, const float* b, float* out, ocrf_stream_t stream) {
-  return launch_binary<AddRelu>(OCRF_K_ADD_RELU, n, a, b, out, stream);
+  return launch_binary<4>(OCRF_K_ADD_RELU, binary_kernel<4, AddRelu>, binary_kernel<1, AddRelu>, n, a, b, out, stream);
 }
 
 int ocrf_add_relu_backward(long long n, const float* grad_out, const float* out, float* grad, ocrf_stream_t stream) {
-  return launch_binary<Threshold>(OCRF_K_ADD_RELU_BWD, n, grad_out, out, grad, stream);
+  return launch_binary<4>(OCRF_K_ADD_RELU_BWD, binary_kernel<4, Threshold>, binary_kernel<1, Threshold>, n, grad_out, out,
+                          grad, stream);
 }
 
 int ocrf_upsample_add_forward(int B, int C, int Hin, int Win, int Hout, int Wout, const float* dst, const float* src,
@@ -228,7 +350,7 @@ int ocrf_upsample_add_forward(int B, int C, int Hin, int Win, int Hout, int Wout
   if (!dst || !src || !out) return (int)hipErrorInvalidValue;
   const size_t lds = (size_t)(Hout + Wout) * sizeof(int);
   const bool vec = P % 4 == 0 && aligned16(dst) && aligned16(out);
-  const Units n = units_of((long long)B * C, P, vec);
+  const Units n = units_of((long long)B * C, P, vec ? 4 : 1);
   if (n.units >= kTwoGiB) return (int)hipErrorInvalidValue;
   if (vec) {
     ocrf::launch(OCRF_K_UPSAMPLE_ADD, upsample_add_kernel<4>, dim3(n.grid), dim3(kThreads), lds, (hipStream_t)stream,
@@ -250,6 +372,50 @@ int ocrf_upsample_add_backward(int B, int C, int Hin, int Win, int Hout, int Wou
   const long long total = (long long)B * C * Pin;                 // <= B C P < 2^29
   const unsigned grid = capped_grid((total + kThreads - 1) / kThreads);
   ocrf::launch(OCRF_K_UPSAMPLE_ADD_BWD, upsample_add_backward_kernel, dim3(grid), dim3(kThreads), lds,
+               (hipStream_t)stream, Hin, Win, Hout, Wout, (int)total, grad_out, grad_src);
+  return (int)hipGetLastError();
+}
+
+int ocrf_add_relu_forward_bf16(long long n, const unsigned short* a, const unsigned short* b, unsigned short* out,
+                               ocrf_stream_t stream) {
+  return launch_binary<8>(OCRF_K_ADD_RELU_BF16, binary_bf16_kernel<8, AddReluBf16>, binary_bf16_kernel<1, AddReluBf16>, n,
+                          a, b, out, stream);
+}
+
+int ocrf_add_relu_backward_bf16(long long n, const unsigned short* grad_out, const unsigned short* out,
+                                unsigned short* grad, ocrf_stream_t stream) {
+  return launch_binary<8>(OCRF_K_ADD_RELU_BWD_BF16, binary_bf16_kernel<8, ThresholdBf16>,
+                          binary_bf16_kernel<1, ThresholdBf16>, n, grad_out, out, grad, stream);
+}
+
+int ocrf_upsample_add_forward_bf16(int B, int C, int Hin, int Win, int Hout, int Wout, const unsigned short* dst,
+                                   const unsigned short* src, unsigned short* out, ocrf_stream_t stream) {
+  long long P, Pin;
+  if (!shapes_ok(B, C, Hin, Win, Hout, Wout, &P, &Pin, sizeof(bf16_t))) return (int)hipErrorInvalidValue;
+  if (!dst || !src || !out) return (int)hipErrorInvalidValue;
+  const size_t lds = (size_t)(Hout + Wout) * sizeof(int);
+  const bool vec = P % 8 == 0 && aligned16(dst) && aligned16(out);
+  const Units n = units_of((long long)B * C, P, vec ? 8 : 1);
+  if (n.units >= kTwoGiB) return (int)hipErrorInvalidValue;
+  if (vec) {
+    ocrf::launch(OCRF_K_UPSAMPLE_ADD_BF16, upsample_add_bf16_kernel<8>, dim3(n.grid), dim3(kThreads), lds,
+                 (hipStream_t)stream, Hin, Win, Hout, Wout, n.chunks, (int)n.units, dst, src, out);
+  } else {
+    ocrf::launch(OCRF_K_UPSAMPLE_ADD_BF16, upsample_add_bf16_kernel<1>, dim3(n.grid), dim3(kThreads), lds,
+                 (hipStream_t)stream, Hin, Win, Hout, Wout, n.chunks, (int)n.units, dst, src, out);
+  }
+  return (int)hipGetLastError();
+}
+
+int ocrf_upsample_add_backward_bf16(int B, int C, int Hin, int Win, int Hout, int Wout, const unsigned short* grad_out,
+                                    unsigned short* grad_src, ocrf_stream_t stream) {
+  long long P, Pin;
+  if (!shapes_ok(B, C, Hin, Win, Hout, Wout, &P, &Pin, sizeof(bf16_t))) return (int)hipErrorInvalidValue;
+  if (!grad_out || !grad_src) return (int)hipErrorInvalidValue;
+  const size_t lds = (size_t)(Hin + Win + 2) * sizeof(int);       // as in ocrf_upsample_add_backward
+  const long long total = (long long)B * C * Pin;
+  const unsigned grid = capped_grid((total + kThreads - 1) / kThreads);
+  ocrf::launch(OCRF_K_UPSAMPLE_ADD_BWD_BF16, upsample_add_backward_bf16_kernel, dim3(grid), dim3(kThreads), lds,
                (hipStream_t)stream, Hin, Win, Hout, Wout, (int)total, grad_out, grad_src);
   return (int)hipGetLastError();
 }

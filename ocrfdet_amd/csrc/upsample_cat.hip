@@ -178,7 +178,7 @@ int ocrf_upsample_cat_forward(int B, int C2, int C1, int Hin, int Win, int scale
   if (!x1 || !out || (C2 > 0 && !x2)) return (int)hipErrorInvalidValue;
   const size_t lds = (size_t)(Hin + Win) * scale * sizeof(Tap);
   const bool vec = P % 4 == 0 && aligned16(out) && (C2 == 0 || aligned16(x2));
-  const Units n = units_of((long long)B * (C2 + C1), P, vec);
+  const Units n = units_of((long long)B * (C2 + C1), P, vec ? 4 : 1);
   if (n.units >= kTwoGiB) return (int)hipErrorInvalidValue;
   if (vec) {
     ocrf::launch(OCRF_K_UPSAMPLE_CAT, upsample_cat_kernel<4>, dim3(n.grid), dim3(kThreads), lds, (hipStream_t)stream,

@@ -204,9 +204,12 @@ def stereo_cost_volume_hip(metas, bias, raw=False):
 
 
 def stereo_cost_volume(metas, bias, fused=True, raw=False):
-    """The kernel for CUDA float32 features when ``fused``, else the torch formulation (also on the CPU)."""
+    """The kernel for CUDA float32 features when ``fused``, else the torch formulation (also on the CPU).  bfloat16
+    features (an image encoder under bf16 autocast) take the kernel too, after its cast to float32: the volume is then
+    float32, where the reference computes it in the features' dtype."""
     prev, curr = metas['cv_feat_list']
-    if fused and curr.is_cuda and prev.is_cuda and curr.dtype == torch.float32 and prev.dtype == torch.float32:
+    dtypes = (torch.float32, torch.bfloat16)
+    if fused and curr.is_cuda and prev.is_cuda and curr.dtype in dtypes and prev.dtype in dtypes:
         return stereo_cost_volume_hip(metas, bias, raw)
     return stereo_cost_volume_torch(metas, bias, raw)
 

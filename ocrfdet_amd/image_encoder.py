@@ -21,14 +21,18 @@ tail of every block) and ``upsample_add`` (``CustomFPN``'s top-down step), both 
 here.  CUDA float32 contiguous tensors of equal shape (``add_relu``) or with matching B and C and a target no smaller
 than the source (``upsample_add``) take the kernels while ``ResNet.fused_tail`` / ``CustomFPN.fused_merge`` is True;
 everything else (the CPU, other dtypes, non-contiguous maps, other interpolation modes) takes the torch formulation.
+Under ``torch.autocast('cuda', dtype=torch.bfloat16)`` the maps between the convolutions are bfloat16: they take the
+ops' bf16 kernels while ``ResNet.fused_tail_bf16`` / ``CustomFPN.fused_merge_bf16`` are True as well.
 """
+import torch
 import torch.nn.functional as F
 from torch import nn
 from torch.nn.modules.batchnorm import _BatchNorm
 
-from .blocks import BasicBlock, Bottleneck, ConvModule, _Block, build, build_norm, kaiming_init
-from .plane_ops import (FUSED_MERGE_DEFAULT, FUSED_TAIL_DEFAULT, add_relu, add_relu_torch,  # noqa: F401 (re-exported)
-                        upsample_add, upsample_add_fusable, upsample_add_torch)
+from .blocks import BasicBlock, Bottleneck, ConvModule, _Block, build, build_norm, fuse_bf16_tails, kaiming_init
+from .plane_ops import (FUSED_MERGE_BF16_DEFAULT, FUSED_MERGE_DEFAULT, FUSED_TAIL_BF16_DEFAULT,  # noqa: F401 (re-exported)
+                        FUSED_TAIL_DEFAULT, add_relu, add_relu_torch, upsample_add, upsample_add_fusable,
+                        upsample_add_torch)
 
 
 # ------------------------------------------------------------------------------------------------ ResNet
@@ -110,6 +114,16 @@ class ResNet(nn.Module):
             if isinstance(m, _Block):
                 m.fused_tail = bool(flag)
 
+    @property
+    def fused_tail_bf16(self):
+        """Whether bfloat16 tails (bf16 autocast) run as ``add_relu`` while ``fused_tail`` is on; setting it applies to
+        every block."""
+        return all(m.fused_tail_bf16 for m in self.modules() if isinstance(m, _Block))
+
+    @fused_tail_bf16.setter
+    def fused_tail_bf16(self, flag):
+        fuse_bf16_tails(self, flag)
+
     def _freeze_stages(self):
         if self.frozen_stages >= 0:
             self.norm1.eval()
@@ -165,6 +179,7 @@ class CustomFPN(nn.Module):
         self.upsample_cfg = upsample_cfg.copy()
         self.out_ids, self.init_cfg = out_ids, init_cfg
         self.fused_merge = FUSED_MERGE_DEFAULT
+        self.fused_merge_bf16 = FUSED_MERGE_BF16_DEFAULT           # bfloat16 laterals too (only while fused_merge is on)
         if end_level == -1:
             self.backbone_end_level = self.num_ins
         else:
@@ -206,7 +221,8 @@ class CustomFPN(nn.Module):
         cfg = dict(self.upsample_cfg)
         if 'scale_factor' not in cfg:
             cfg['size'] = tuple(dst.shape[2:])
-        if self.fused_merge and set(cfg) <= {'mode', 'size', 'scale_factor'} and cfg.get('mode', 'nearest') == 'nearest':
+        fused = self.fused_merge and (self.fused_merge_bf16 or dst.dtype != torch.bfloat16)
+        if fused and set(cfg) <= {'mode', 'size', 'scale_factor'} and cfg.get('mode', 'nearest') == 'nearest':
             size, scale = cfg.get('size'), cfg.get('scale_factor')
             if upsample_add_fusable(dst, src, size, scale):
                 return upsample_add(dst, src, size=size, scale_factor=scale)

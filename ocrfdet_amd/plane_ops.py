@@ -13,9 +13,15 @@ The first two (``csrc/resnet_fuse.hip``) are bit-equal to ``add_relu_torch`` / `
 third (``csrc/upsample_cat.hip``) takes its interpolation weights from integer arithmetic with one rounding, torch from
 a float product: the two differ in the last bits.
 
+The first two also take bfloat16 tensors (the ``*_bf16`` entry points of the same file), which is what they see between
+the convolutions under ``torch.autocast('cuda', dtype=torch.bfloat16)``: operands, result and gradients are all bf16,
+the sum is one float32 addition rounded once to nearest even, as torch's bf16 ops, and forward and ``add_relu``'s
+backward stay bit-equal to the ``*_torch`` formulations.  ``upsample_cat`` is float32 only (``BEVEncoder`` runs with
+autocast disabled).
+
 The ops themselves never fall back: they raise on an input the kernels do not take.  The modules dispatch with the
-``*_fusable`` predicates: CUDA float32 contiguous tensors take the kernels, everything else (the CPU, other dtypes,
-non-contiguous maps) the ``*_torch`` formulation.
+``*_fusable`` predicates: CUDA contiguous tensors that are all float32 (or, for the first two, all bfloat16) take the
+kernels, everything else (the CPU, float16 and float64, mixed dtypes, non-contiguous maps) the ``*_torch`` formulation.
 """
 import torch
 import torch.nn.functional as F
@@ -29,10 +35,34 @@ from . import _lib
 # (1.02x to 1.09x of the unfused one).
 FUSED_TAIL_DEFAULT = True
 FUSED_MERGE_DEFAULT = True
+# The same for bfloat16 operands (the modules' ``fused_tail_bf16`` / ``fused_merge_bf16``, which apply while
+# ``fused_tail`` / ``fused_merge`` are on), from profiles/image_encoder_bf16_time.txt
+# (tools/time_image_encoder.py --autocast bf16; INTEGRATION 3i has the table).
+# By device time each op is faster than its torch formulation on bf16 tensors at the reference shapes, forward and
+# forward + backward, at 12 and at 48 images (tail 1.11x to 1.90x, merge 1.61x to 2.48x), and the whole encoder under
+# autocast with both flags on is the fastest of the four flag pairs in eval and in training (1.01x to 1.07x of the
+# unfused one, which is what autocast ran before).  By wall time the ops alone lose at 12 images, where a launch costs
+# the host more than the device (0.59x to 0.86x); the encoder in training at 12 images is host-bound either way (0.96x).
+FUSED_TAIL_BF16_DEFAULT = True
+FUSED_MERGE_BF16_DEFAULT = True
+
+# what the kernels of add_relu / upsample_add exist for: the suffix of their entry points
+_SUFFIX = {torch.float32: '', torch.bfloat16: '_bf16'}
 
 
-def _plain(t):
-    return t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+def _plain(t, dtypes=(torch.float32,)):
+    return t.is_cuda and t.dtype in dtypes and t.is_contiguous()
+
+
+def _plain_pair(a, b):
+    """Both CUDA contiguous on one device and both float32 or both bfloat16."""
+    return _plain(a, _SUFFIX) and _plain(b, _SUFFIX) and a.dtype == b.dtype and a.device == b.device
+
+
+def _check_grad(grad_out, dtype, op):
+    """``grad_out`` must come in the dtype of the forward's tensors."""
+    if grad_out.dtype != dtype:
+        raise _lib.OcrfHipError(f'{op} backward: grad_out is {grad_out.dtype}, the forward ran in {dtype}')
 
 
 # ------------------------------------------------------------------------------------------------ add + relu
@@ -42,32 +72,35 @@ def add_relu_torch(a, b):
 
 
 def add_relu_fusable(a, b):
-    return _plain(a) and _plain(b) and a.shape == b.shape and a.device == b.device and a.numel() > 0
+    return _plain_pair(a, b) and a.shape == b.shape and a.numel() > 0
 
 
 class _AddRelu(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):
         out = torch.empty_like(a)
-        _lib.launch('ocrf_add_relu_forward', a.device, a.numel(), a, b, out)
+        _lib.launch('ocrf_add_relu_forward' + _SUFFIX[a.dtype], a.device, a.numel(), a, b, out)
         ctx.save_for_backward(out)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         out, = ctx.saved_tensors
+        _check_grad(grad_out, out.dtype, 'add_relu')
         grad_out = grad_out.contiguous()
         grad = torch.empty_like(out)
-        _lib.launch('ocrf_add_relu_backward', out.device, out.numel(), grad_out, out, grad)
+        _lib.launch('ocrf_add_relu_backward' + _SUFFIX[out.dtype], out.device, out.numel(), grad_out, out, grad)
         return grad, grad
 
 
 def add_relu(a, b):
-    """``add_relu_torch`` as one HIP launch (``ocrf_add_relu_forward`` / ``_backward``).  CUDA float32 contiguous
-    tensors of equal shape only: anything else raises (the blocks dispatch)."""
+    """``add_relu_torch`` as one HIP launch (``ocrf_add_relu_forward`` / ``_backward``, or their ``_bf16`` forms).  CUDA
+    contiguous tensors of equal shape, both float32 or both bfloat16, only: anything else raises (the blocks
+    dispatch)."""
     _lib.require_cuda(a, b)
     if not add_relu_fusable(a, b):
-        raise _lib.OcrfHipError('add_relu takes two non-empty contiguous float32 tensors of equal shape on one device')
+        raise _lib.OcrfHipError('add_relu takes two non-empty contiguous tensors of equal shape on one device, both '
+                                'float32 or both bfloat16')
     return _AddRelu.apply(a, b)
 
 
@@ -97,7 +130,7 @@ def _target(src, size, scale_factor):
 
 
 def upsample_add_fusable(dst, src, size, scale_factor):
-    if not (_plain(dst) and _plain(src) and dst.dim() == 4 and src.dim() == 4 and dst.device == src.device):
+    if not (_plain_pair(dst, src) and dst.dim() == 4 and src.dim() == 4):
         return False
     hw = _target(src, size, scale_factor)
     return (hw is not None and dst.numel() > 0 and src.numel() > 0 and dst.shape[:2] == src.shape[:2]
@@ -110,30 +143,35 @@ class _UpsampleAdd(torch.autograd.Function):
         B, C, Hout, Wout = dst.shape
         Hin, Win = src.shape[2:]
         out = torch.empty_like(dst)
-        _lib.launch('ocrf_upsample_add_forward', dst.device, B, C, Hin, Win, Hout, Wout, dst, src, out)
+        _lib.launch('ocrf_upsample_add_forward' + _SUFFIX[dst.dtype], dst.device, B, C, Hin, Win, Hout, Wout, dst, src,
+                    out)
         ctx.shape = (B, C, Hin, Win, Hout, Wout)
+        ctx.dtype = dst.dtype
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         B, C, Hin, Win, Hout, Wout = ctx.shape
         grad_src = None
+        _check_grad(grad_out, ctx.dtype, 'upsample_add')
         if ctx.needs_input_grad[1]:
             g = grad_out.contiguous()
-            grad_src = torch.empty(B, C, Hin, Win, dtype=torch.float32, device=g.device)
-            _lib.launch('ocrf_upsample_add_backward', g.device, B, C, Hin, Win, Hout, Wout, g, grad_src)
+            grad_src = torch.empty(B, C, Hin, Win, dtype=ctx.dtype, device=g.device)
+            _lib.launch('ocrf_upsample_add_backward' + _SUFFIX[ctx.dtype], g.device, B, C, Hin, Win, Hout, Wout, g,
+                        grad_src)
         return (grad_out if ctx.needs_input_grad[0] else None), grad_src
 
 
 def upsample_add(dst, src, size=None, scale_factor=None):
     """``upsample_add_torch`` in mode ``nearest`` as one HIP launch (``ocrf_upsample_add_forward`` / ``_backward``):
     ``src`` (B, C, Hin, Win) upsampled to the size of ``dst`` (B, C, Hout, Wout) and added to it; ``size`` must be that
-    of ``dst``, or ``scale_factor`` an integer with ``Hout = Hin * scale_factor``.  CUDA float32 contiguous tensors
-    only: anything else raises (``CustomFPN`` dispatches)."""
+    of ``dst``, or ``scale_factor`` an integer with ``Hout = Hin * scale_factor``.  CUDA contiguous tensors, both
+    float32 or both bfloat16, only: anything else raises (``CustomFPN`` dispatches)."""
     _lib.require_cuda(dst, src)
     if not upsample_add_fusable(dst, src, size, scale_factor):
-        raise _lib.OcrfHipError('upsample_add takes contiguous float32 NCHW tensors with the same B and C, dst of the '
-                                'target size and no smaller than src, and either size or an integer scale_factor')
+        raise _lib.OcrfHipError('upsample_add takes contiguous NCHW tensors, both float32 or both bfloat16, with the '
+                                'same B and C, dst of the target size and no smaller than src, and either size or an '
+                                'integer scale_factor')
     return _UpsampleAdd.apply(dst, src)
 
 

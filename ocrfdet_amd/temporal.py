@@ -20,9 +20,9 @@ Precondition: the 4 x 4 matrices of ``sensor2keyegos`` have the last row (0, 0, 
 is not checked: a check would synchronise.
 
 The ops never fall back: ``shift_feature`` raises on an input the kernels do not take.  ``align_and_cat`` and
-``shift_feature_method`` dispatch: CUDA float32 contiguous maps take the kernels (float16 maps after the cast to
-float32 that the reference's ``@force_fp32`` makes), everything else (the CPU, other dtypes, non-contiguous maps, poses
-that require a gradient) the torch formulation.
+``shift_feature_method`` dispatch: CUDA float32 contiguous maps take the kernels (float16 and bfloat16 maps after
+the cast to float32 that the reference's ``@force_fp32`` makes), everything else (the CPU, other dtypes,
+non-contiguous maps, poses that require a gradient) the torch formulation.
 """
 import torch
 import torch.nn.functional as F
@@ -112,15 +112,18 @@ def shift_feature_torch(input, tf):
 
 
 # ------------------------------------------------------------------------------------------------ the kernels
+_HALVES = (torch.float16, torch.bfloat16)
+
+
 def _plain(t):
-    """A map the kernels take, after the cast of a float16 one."""
-    return (t.is_cuda and t.dtype in (torch.float32, torch.float16) and t.is_contiguous() and t.dim() == 4
+    """A map the kernels take, after the cast of a float16 or bfloat16 one."""
+    return (t.is_cuda and t.dtype in (torch.float32, *_HALVES) and t.is_contiguous() and t.dim() == 4
             and t.numel() > 0)
 
 
 def _cast(t):
-    """The reference's ``@force_fp32``: a float16 map is computed in float32."""
-    return t.float() if t.dtype == torch.float16 else t
+    """The reference's ``@force_fp32``: a float16 map, or a bfloat16 one of bf16 autocast, is computed in float32."""
+    return t.float() if t.dtype in _HALVES else t
 
 
 def _tf32(tf, like):
@@ -179,14 +182,15 @@ class _ShiftFeature(torch.autograd.Function):
 def shift_feature(input, tf, out=None):
     """``shift_feature_torch`` as one HIP launch (``ocrf_bev_align_forward``; backward ``ocrf_bev_align_backward``, a
     gather): ``input`` (n, c, h, w) sampled at ``tf`` (n, 3, 3, any floating dtype, on the device of ``input``; rounded
-    to float32).  CUDA float32 contiguous input only, a float16 input is cast to float32 first (``@force_fp32``);
-    anything else raises.  ``tf`` gets no gradient.
+    to float32).  CUDA float32 contiguous input only, a float16 or bfloat16 one is cast to float32 first
+    (``@force_fp32``); anything else raises.  ``tf`` gets no gradient.
 
     ``out``: an (n, c, h, w) float32 view with contiguous (c, h, w) blocks, such as a channel slice of a wider
     concatenation, to write into; it is returned.  This form records no gradient, so ``input`` must not require one."""
     _lib.require_cuda(input, tf)
     if not _plain(input):
-        raise _lib.OcrfHipError('shift_feature takes a non-empty contiguous float32 (or float16) NCHW map on the GPU')
+        raise _lib.OcrfHipError('shift_feature takes a non-empty contiguous float32 (or float16 / bfloat16) NCHW map on the '
+                                'GPU')
     input = _cast(input)
     tf32 = _tf32(tf, input)
     if out is None:
@@ -236,8 +240,8 @@ class _AlignCat(torch.autograd.Function):
 
 
 def align_fusable(feats, tfs):
-    """The kernels take these maps: CUDA float32 (or float16) contiguous, of one shape on one device, and no transform
-    that requires a gradient."""
+    """The kernels take these maps: CUDA float32 (or float16 / bfloat16) contiguous, of one shape on one device, and no
+    transform that requires a gradient."""
     first = feats[0]
     for x in feats:
         if not (_plain(x) and x.shape == first.shape and x.device == first.device):

@@ -29,6 +29,7 @@ reference's ``DepthNet`` when its mmdet3d is importable, else none.  ``cv_frustu
 :783-789) is a non-persistent buffer, so the detector's ``cv_frustum.to(x)`` finds it on the device already.
 """
 import contextlib
+import functools
 import math
 import random
 
@@ -462,6 +463,25 @@ class _Geometry:
                  'raster_plan')
 
 
+def _as_float32(a):
+    if torch.is_tensor(a):
+        return a.float() if a.dtype == torch.bfloat16 else a
+    return [_as_float32(v) for v in a] if isinstance(a, list) else a
+
+
+def _float32_under_autocast(fn):
+    """The neck computes in float32 (its kernels, the calibration algebra and the layers between them): called under
+    ``torch.autocast``, ``fn`` runs with autocast disabled and its bfloat16 tensor arguments, also those inside lists
+    (``img_inputs``), arrive as float32 (autograd hands them bf16 gradients).  Outside autocast nothing changes."""
+    @functools.wraps(fn)
+    def wrapper(self, *args, **kwargs):
+        if not torch.is_autocast_enabled('cuda'):
+            return fn(self, *args, **kwargs)
+        with torch.autocast('cuda', enabled=False):
+            return fn(self, *[_as_float32(a) for a in args], **{k: _as_float32(v) for k, v in kwargs.items()})
+    return wrapper
+
+
 class OcRFViewTransformerFull(nn.Module):
     def __init__(self, pc_range, bev_h=128, bev_w=128, num_height=13, collapse_z=True, loss_semantic_weight=25,
                  depth_threshold=1, semantic_threshold=0.25, depthnet_cfg=dict(), grid_config=None, input_size=None,
@@ -822,11 +842,13 @@ class OcRFViewTransformerFull(nn.Module):
                                  (depth.shape[0], 1, self.bev_h, self.bev_w, feat_cl.shape[-1]))
 
     # -------------------------------------------------------------------------------- core
+    @_float32_under_autocast
     def view_transform(self, input, depth, tran_feat, feat_channels_last=None, cameras=None):
         if self.accelerate:
             self.pre_compute(input)
         return self.view_transform_core(input, depth, tran_feat, feat_channels_last, cameras=cameras)
 
+    @_float32_under_autocast
     def view_transform_core(self, input, depth, tran_feat, feat_channels_last=None, cam_idx_list=None, cameras=None):
         """Same inputs / outputs as the reference (:1040-1201).  ``feat_channels_last`` (B*N,H,W,C),
         when the caller already has it (``forward`` does), skips the permute of :875/:901;
@@ -1265,6 +1287,7 @@ class OcRFViewTransformerFull(nn.Module):
         m = losses.box_mask(gt_bboxes, new_width, new_height, device)
         return m.view(1, 1, new_height, new_width).repeat(1, 3, 1, 1)
 
+    @_float32_under_autocast
     def get_loss(self, depth, semantic, gt_depth, gt_semantic, gt_bboxes, cam_idx_list, render_imgs, gt_images,
                  render_image_G_all, render_image_N_all, render_depth, render_depth_G_all, render_depth_N_all):
         """:1354-1417 -> (loss_depth, loss_ce_semantic, color_loss, ssim_loss, render_depth_loss).  ``cam_idx_list``:
@@ -1301,6 +1324,8 @@ class OcRFViewTransformerFull(nn.Module):
         x, mlp_input = input[0], input[7]
         B, N, C, H, W = x.shape
         y = self.depth_net(x.view(B * N, C, H, W), mlp_input, stereo_metas)
+        if y.dtype == torch.bfloat16:               # a DepthNet under bf16 autocast; from here on float32
+            y = y.float()
         if y.is_cuda and not self.training and not self._recording(y):
             depth, filter_depth, semantic, feat_cl = neck_ops.prefilter(y, self.D, self.out_channels,
                                                                         self.depth_threshold, self.semantic_threshold)

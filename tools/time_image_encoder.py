@@ -13,11 +13,20 @@ around synchronised blocks — at 12 and at 48 images of 3 x 256 x 704 (B = 2 an
 with the kernels' algorithmic bytes against the MI355X's measured HBM copy rate.  The defaults of the two flags in
 ``ocrfdet_amd/plane_ops.py`` follow from this file's output.
 
-    python tools/time_image_encoder.py [--iters N] [--enc-iters N] [--images 12 48] [--out profiles/image_encoder_time.txt]
+``--autocast bf16`` runs the same arms as training under ``torch.autocast('cuda', dtype=torch.bfloat16)`` sees them: the
+two ops on bfloat16 tensors, the encoder inside the autocast region with ``fused_tail_bf16`` / ``fused_merge_bf16``
+following the arm's flags (the unfused arm is what the encoder ran before the ops took bfloat16), and each encoder row
+against its float32 time in ``profiles/image_encoder_time.txt``.  The defaults ``FUSED_TAIL_BF16_DEFAULT`` /
+``FUSED_MERGE_BF16_DEFAULT`` follow from that output, ``profiles/image_encoder_bf16_time.txt``.
+
+    python tools/time_image_encoder.py [--iters N] [--enc-iters N] [--images 12 48] [--autocast bf16]
+                                       [--out profiles/image_encoder_time.txt]
 """
 import argparse
 import collections
+import contextlib
 import os
+import re
 import sys
 import time
 
@@ -28,6 +37,12 @@ sys.path.insert(0, ROOT)
 from ocrfdet_amd import image_encoder as ie  # noqa: E402
 
 HBM_TBS = 6.29                               # MI355X_MICROARCH: measured float4 copy rate
+
+
+def emit(lines, text):
+    """Keep a line of the report, and show it as soon as it is there."""
+    lines.append(text)
+    print(text, flush=True)
 
 
 def _wall(fns, iters, blocks=5):
@@ -70,14 +85,23 @@ def measure(lines, name, variants, iters, reps=5):
     profs = [_profile(fn, reps) for _, fn in variants]
     base_dev, base_wall = profs[-1][1], walls[-1][1]
     for (label, _), (best, med), (launches, dev) in zip(variants, walls, profs):
-        lines.append(f'{name} | {label}: {dev:.4f} ms device, {launches:.0f} launches, wall best {best:.4f} / median '
+        emit(lines, f'{name} | {label}: {dev:.4f} ms device, {launches:.0f} launches, wall best {best:.4f} / median '
                      f'{med:.4f} ms | torch / this: device {base_dev / dev:.2f}x, wall median {base_wall / med:.2f}x')
     return [dev for _, dev in profs]
 
 
 def traffic(lines, what, nbytes, ms):
-    lines.append(f'    {what}: {nbytes / 1e6:.1f} MB -> {nbytes / ms / 1e9:.2f} TB/s, '
+    emit(lines, f'    {what}: {nbytes / 1e6:.1f} MB -> {nbytes / ms / 1e9:.2f} TB/s, '
                  f'{nbytes / ms / 1e9 / HBM_TBS:.0%} of the {HBM_TBS} TB/s copy rate')
+
+
+def float32_rows(path=os.path.join(ROOT, 'profiles', 'image_encoder_time.txt')):
+    """{row name | label: device ms} of the float32 run's encoder rows."""
+    if not os.path.exists(path):
+        return {}
+    with open(path) as f:
+        return {m.group(1): float(m.group(2)) for m in re.finditer(r'^(ImageEncoder [^\n]*?): ([\d.]+) ms device', f.read(),
+                                                                   re.M)}
 
 
 def main():
@@ -85,23 +109,30 @@ def main():
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--enc-iters', type=int, default=3)
     ap.add_argument('--images', type=int, nargs='+', default=[12, 48])
+    ap.add_argument('--autocast', choices=['none', 'bf16'], default='none')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
+    bf16 = a.autocast == 'bf16'
+    dtype, width = (torch.bfloat16, 2) if bf16 else (torch.float32, 4)
+    region = (lambda: torch.autocast('cuda', dtype=torch.bfloat16)) if bf16 else contextlib.nullcontext
+    f32 = float32_rows() if bf16 else {}
     assert torch.cuda.is_available(), 'timing needs the GPU: there is no CPU fallback for a measurement'
     dev = torch.device('cuda:0')
-    lines = [f'device: {torch.cuda.get_device_name(0)}; torch {torch.__version__}; ops {a.iters} and encoder '
-             f'{a.enc_iters} iters x 5 blocks, alternating; device ms from the torch profiler']
+    lines = []
+    emit(lines, f'device: {torch.cuda.get_device_name(0)}; torch {torch.__version__}; ops {a.iters} and encoder '
+             f'{a.enc_iters} iters x 5 blocks, alternating; device ms from the torch profiler'
+             + ('; bfloat16 operands, the encoder under torch.autocast(bf16)' if bf16 else ''))
 
     for n_img in a.images:
         for layer, shape in (('layer1', (n_img, 256, 64, 176)), ('layer4', (n_img, 2048, 8, 22))):
-            x = torch.randn(*shape, device=dev, requires_grad=True)
-            y = torch.randn(*shape, device=dev, requires_grad=True)
-            g = torch.randn(*shape, device=dev)
+            x = torch.randn(*shape, device=dev).to(dtype).requires_grad_(True)
+            y = torch.randn(*shape, device=dev).to(dtype).requires_grad_(True)
+            g = torch.randn(*shape, device=dev).to(dtype)
             name = f'tail {layer} {shape}'
             with torch.no_grad():
                 fd, _ = measure(lines, name + ' forward', [('add_relu', lambda: ie.add_relu(x, y)),
                                                              ('torch', lambda: ie.add_relu_torch(x, y))], a.iters)
-            nbytes = 3 * 4 * x.numel()
+            nbytes = 3 * width * x.numel()
             traffic(lines, 'forward bytes (a, b, out)', nbytes, fd)
 
             def fb(op):
@@ -113,15 +144,15 @@ def main():
                                                            ('torch', fb(ie.add_relu_torch))], a.iters)
             del x, y, g
 
-        dst = torch.randn(n_img, 256, 16, 44, device=dev, requires_grad=True)
-        src = torch.randn(n_img, 256, 8, 22, device=dev, requires_grad=True)
-        g = torch.randn(n_img, 256, 16, 44, device=dev)
+        dst = torch.randn(n_img, 256, 16, 44, device=dev).to(dtype).requires_grad_(True)
+        src = torch.randn(n_img, 256, 8, 22, device=dev).to(dtype).requires_grad_(True)
+        g = torch.randn(n_img, 256, 16, 44, device=dev).to(dtype)
         name = f'merge ({n_img}, 256, 8, 22) -> (16, 44)'
         with torch.no_grad():
             fd, _ = measure(lines, name + ' forward',
                             [('upsample_add', lambda: ie.upsample_add(dst, src, size=(16, 44))),
                              ('torch', lambda: ie.upsample_add_torch(dst, src, size=(16, 44)))], a.iters)
-        traffic(lines, 'forward bytes (dst, src, out)', 4 * (2 * dst.numel() + src.numel()), fd)
+        traffic(lines, 'forward bytes (dst, src, out)', width * (2 * dst.numel() + src.numel()), fd)
 
         def fbm(op):
             def run():
@@ -141,13 +172,13 @@ def main():
         img = torch.randn(n_img // 6, 6, 3, 256, 704, device=dev)
 
         def set_flags(tail, merge):
-            enc.img_backbone.fused_tail = tail
-            enc.img_neck.fused_merge = merge
+            enc.img_backbone.fused_tail = enc.img_backbone.fused_tail_bf16 = tail
+            enc.img_neck.fused_merge = enc.img_neck.fused_merge_bf16 = merge
 
         def fwd(tail, merge):
             def run():
                 set_flags(tail, merge)
-                with torch.no_grad():
+                with torch.no_grad(), region():
                     enc(img, stereo=True)
             return run
 
@@ -155,24 +186,28 @@ def main():
             def run():
                 set_flags(tail, merge)
                 enc.zero_grad(set_to_none=True)
-                x, stereo = enc(img, stereo=True)
-                (x.square().mean() + stereo.square().mean()).backward()
+                with region():
+                    x, stereo = enc(img, stereo=True)
+                (x.float().square().mean() + stereo.float().square().mean()).backward()
             return run
         pairs = [(True, True), (True, False), (False, True), (False, False)]
         label = lambda t, m: f'fused_tail={t}, fused_merge={m}' + (' (torch)' if not (t or m) else '')  # noqa: E731
+        def encoder_rows(name, make):
+            devs = measure(lines, name, [(label(t, m), make(t, m)) for t, m in pairs], a.enc_iters, reps=3)
+            for (t, m), ms in zip(pairs, devs):
+                ref = f32.get(f'{name} | {label(t, m)}')
+                if ref is not None:
+                    emit(lines, f'    {label(t, m)}: float32 {ref:.4f} ms device (profiles/image_encoder_time.txt) / '
+                                 f'bf16 autocast {ms:.4f} = {ref / ms:.2f}x')
         enc.eval()
-        measure(lines, f'ImageEncoder {n_img} x (3, 256, 704) forward, eval',
-                [(label(t, m), fwd(t, m)) for t, m in pairs], a.enc_iters, reps=3)
+        encoder_rows(f'ImageEncoder {n_img} x (3, 256, 704) forward, eval', fwd)
         enc.train()
-        measure(lines, f'ImageEncoder {n_img} x (3, 256, 704) forward + backward, train, with_cp',
-                [(label(t, m), fwd_bwd(t, m)) for t, m in pairs], a.enc_iters, reps=3)
+        encoder_rows(f'ImageEncoder {n_img} x (3, 256, 704) forward + backward, train, with_cp', fwd_bwd)
         del enc, img
         torch.cuda.empty_cache()
-    text = '\n'.join(lines)
-    print(text)
     if a.out:
         with open(a.out, 'w') as f:
-            f.write(text + '\n')
+            f.write('\n'.join(lines) + '\n')
 
 
 if __name__ == '__main__':
