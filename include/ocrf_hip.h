@@ -632,6 +632,20 @@ int ocrf_upsample_cat_forward(int B, int C2, int C1, int Hin, int Win, int scale
                               float *out, ocrf_stream_t stream);
 int ocrf_upsample_cat_backward(int B, int C2, int C1, int Hin, int Win, int scale, const float *grad_out,
                                float *grad_x1, ocrf_stream_t stream);
+/*
+ * The same pair on bfloat16 data, for the BEV encoder under bf16 autocast: every operand and result is bf16, passed as
+ * unsigned short (the upper half of the f32 with the same value), same layouts and arguments.  The kernels are the f32
+ * kernels' bodies instantiated for the 2-byte element: taps and gradients are widened to f32 (exact), the value and the
+ * backward's sum are the f32 expressions above in the same order, and the result is rounded ONCE to bf16, to nearest
+ * even.  Each entry point therefore returns, bit for bit, what its f32 counterpart returns on the widened operands,
+ * rounded once; a copied channel keeps its bits.  A NaN stays a NaN; which NaN is not specified.
+ * 16-byte accesses (8 elements) along the output rows when the output plane is a multiple of 8 elements and out / x2
+ * are 16-byte aligned, 2-byte accesses otherwise.  Limits: those above, with every operand below 2 GiB of bf16.
+ */
+int ocrf_upsample_cat_forward_bf16(int B, int C2, int C1, int Hin, int Win, int scale, const unsigned short *x2,
+                                   const unsigned short *x1, unsigned short *out, ocrf_stream_t stream);
+int ocrf_upsample_cat_backward_bf16(int B, int C2, int C1, int Hin, int Win, int scale, const unsigned short *grad_out,
+                                    unsigned short *grad_x1, ocrf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Temporal BEV alignment (csrc/bev_align.hip, csrc/bev_align_index.h): BEVDet4D.shift_feature
@@ -668,6 +682,20 @@ int ocrf_bev_align_forward(int n, int c, int h, int w, const float *x, const flo
 int ocrf_bev_align_backward(int n, int c, int h, int w, const float *grad_out, long long grad_batch_stride,
                             const float *tf, float *grad_x, ocrf_stream_t stream);
 int ocrf_bev_align_source_box(const float *tf, int h, int w, int qx, int qy, int *box);
+/*
+ * The same pair on bfloat16 maps (kept bf16 under autocast): x / out / grad_out / grad_x are bf16, passed as unsigned
+ * short; tf stays f32; out_batch_stride / grad_batch_stride are counted in elements.  Coordinates, taps, validity and the
+ * box are the f32 ones; taps and gradients are widened to f32 (exact), the value and the gradient sum are the f32
+ * expressions in the same order, and the result is rounded ONCE to bf16, to nearest even: bit for bit what the f32 entry
+ * point returns on the widened operands, rounded once.  A NaN stays a NaN; which NaN is not specified.
+ * 16-byte stores (8 elements) when h * w and out_batch_stride are multiples of 8 and out is 16-byte aligned, 2-byte
+ * stores otherwise.  Limits: those above, the 2 GiB counted in bytes of the 2-byte element.
+ */
+int ocrf_bev_align_forward_bf16(int n, int c, int h, int w, const unsigned short *x, const float *tf,
+                                unsigned short *out, long long out_batch_stride, ocrf_stream_t stream);
+int ocrf_bev_align_backward_bf16(int n, int c, int h, int w, const unsigned short *grad_out,
+                                 long long grad_batch_stride, const float *tf, unsigned short *grad_x,
+                                 ocrf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * The tail of a training iteration (csrc/optim.hip): clip_grad_norm_(max_norm, norm_type=2), torch.optim.AdamW and the
@@ -1187,21 +1215,25 @@ enum {
   OCRF_K_CD_MASK = 99,           /* cd_mask_kernel */
   OCRF_K_CD_SCAN = 100,          /* cd_scan_kernel */
   OCRF_K_CD_WRITE = 101,         /* cd_write_kernel */
-  OCRF_K_UPSAMPLE_CAT = 102,     /* upsample_cat_kernel<V> */
-  OCRF_K_UPSAMPLE_CAT_BWD = 103, /* upsample_cat_backward_kernel */
+  OCRF_K_UPSAMPLE_CAT = 102,     /* upsample_cat_kernel<float, V> */
+  OCRF_K_UPSAMPLE_CAT_BWD = 103, /* upsample_cat_backward_kernel<float> */
   OCRF_K_ADD_RELU = 104,         /* binary_kernel<V, AddRelu> */
   OCRF_K_ADD_RELU_BWD = 105,     /* binary_kernel<V, Threshold> */
   OCRF_K_UPSAMPLE_ADD = 106,     /* upsample_add_kernel<V> */
   OCRF_K_UPSAMPLE_ADD_BWD = 107, /* upsample_add_backward_kernel */
-  OCRF_K_BEV_ALIGN = 108,        /* bev_align_kernel<V> */
-  OCRF_K_BEV_ALIGN_BWD = 109,    /* bev_align_backward_kernel */
+  OCRF_K_BEV_ALIGN = 108,        /* bev_align_kernel<float, V> */
+  OCRF_K_BEV_ALIGN_BWD = 109,    /* bev_align_backward_kernel<float> */
   OCRF_K_OPTIM_SQNORM = 110,     /* optim_grad_sqnorm_kernel */
   OCRF_K_OPTIM_NORM_FINAL = 111, /* optim_norm_final_kernel */
   OCRF_K_OPTIM_STEP = 112,       /* optim_step_kernel */
   OCRF_K_ADD_RELU_BF16 = 113,     /* binary_bf16_kernel<V, AddRelu> */
   OCRF_K_ADD_RELU_BWD_BF16 = 114, /* binary_bf16_kernel<V, Threshold> */
   OCRF_K_UPSAMPLE_ADD_BF16 = 115, /* upsample_add_bf16_kernel<V> */
-  OCRF_K_UPSAMPLE_ADD_BWD_BF16 = 116 /* upsample_add_backward_bf16_kernel */
+  OCRF_K_UPSAMPLE_ADD_BWD_BF16 = 116, /* upsample_add_backward_bf16_kernel */
+  OCRF_K_UPSAMPLE_CAT_BF16 = 117,     /* upsample_cat_kernel<unsigned short, V> */
+  OCRF_K_UPSAMPLE_CAT_BWD_BF16 = 118, /* upsample_cat_backward_kernel<unsigned short> */
+  OCRF_K_BEV_ALIGN_BF16 = 119,        /* bev_align_kernel<unsigned short, V> */
+  OCRF_K_BEV_ALIGN_BWD_BF16 = 120     /* bev_align_backward_kernel<unsigned short> */
 };
 const char *ocrf_kernel_name(int kernel_id);           /* symbol as rocprofv3 prints it */
 /* Diagnostic: a one-thread kernel that stores the device's constant-rate clock (wall_clock64, 100 MHz)

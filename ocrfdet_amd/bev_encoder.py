@@ -9,15 +9,20 @@ The residual blocks are those of ``blocks.py`` with ``style='pytorch'`` and ``di
 
 The convolutions stay with MIOpen.  What is fused is ``FPN_LSS.forward``'s ``cat([x2, up(x1)], 1)`` and ``up2[0]``, as
 ``upsample_cat`` of ``plane_ops.py`` (re-exported here).  CUDA float32 contiguous inputs with an integer
-``scale_factor`` take it while ``fused_upsample`` is True; everything else (the CPU, other dtypes, a non-integer factor)
-takes ``upsample_cat_torch``.
+``scale_factor`` take it while ``fused_upsample`` is True, and bfloat16 ones its ``_bf16`` kernels while
+``fused_upsample_bf16`` is True as well; everything else (the CPU, other dtypes, a non-integer factor) takes
+``upsample_cat_torch``.
+
+``BEVEncoder`` computes in float32, as the reference's ``@force_fp32`` has it.  ``autocast_bf16=True`` is the opt-in
+that lets it run as bf16 autocast runs it: bfloat16 convolutions, a bfloat16 ``_up_cat`` and a bfloat16 result.
 """
 import torch
 from torch import nn
 from torch.utils.checkpoint import checkpoint
 
 from .blocks import BasicBlock, Bottleneck, build, build_norm, unfuse_tails
-from .plane_ops import upsample_cat, upsample_cat_fusable, upsample_cat_torch
+from .plane_ops import (FUSED_UPSAMPLE_BF16_DEFAULT, upsample_cat, upsample_cat_bf16_fusable, upsample_cat_fusable,
+                        upsample_cat_torch)
 
 
 class CustomResNet(nn.Module):
@@ -63,6 +68,7 @@ class FPN_LSS(nn.Module):
         self.input_feature_index = input_feature_index
         self.extra_upsample = extra_upsample is not None
         self.fused_upsample = True
+        self.fused_upsample_bf16 = FUSED_UPSAMPLE_BF16_DEFAULT    # for bfloat16 operands, while fused_upsample is on
         self.up = nn.Upsample(scale_factor=scale_factor, mode='bilinear', align_corners=True)
         mid = out_channels * (2 if self.extra_upsample else 1)
         self.input_conv = nn.Sequential(
@@ -87,7 +93,8 @@ class FPN_LSS(nn.Module):
                 nn.ReLU(inplace=True))
 
     def _up_cat(self, x2, x1, scale):
-        if self.fused_upsample and upsample_cat_fusable(x2, x1, scale):
+        if self.fused_upsample and (upsample_cat_fusable(x2, x1, scale) or (
+                self.fused_upsample_bf16 and upsample_cat_bf16_fusable(x2, x1, scale))):
             return upsample_cat(x2, x1, scale)
         return upsample_cat_torch(x2, x1, scale)
 
@@ -115,15 +122,25 @@ def build_pre_process(cfg):
 
 class BEVEncoder(nn.Module):
     """``BEVDet.bev_encoder`` (bevdet.py:66-72): backbone, neck, ``[0]`` of a list or tuple, in float32.  The submodule
-    names are the detector's attributes, so its checkpoint keys match with an empty prefix."""
+    names are the detector's attributes, so its checkpoint keys match with an empty prefix.
 
-    def __init__(self, backbone_cfg, neck_cfg):
+    ``autocast_bf16`` (default False: the reference's ``@force_fp32``): while bfloat16 autocast is active on the input's
+    device, autocast is left on and the input is not widened (a float32 one is narrowed once to bfloat16), so the
+    convolutions and batch norms run as autocast runs them, ``FPN_LSS._up_cat`` sees bfloat16 and the result is
+    bfloat16.  The parameters stay float32.  Outside bfloat16 autocast the flag changes nothing."""
+
+    def __init__(self, backbone_cfg, neck_cfg, autocast_bf16=False):
         super().__init__()
         self.img_bev_encoder_backbone = build(backbone_cfg, 'CustomResNet', CustomResNet)
         self.img_bev_encoder_neck = build(neck_cfg, 'FPN_LSS', FPN_LSS)
+        self.autocast_bf16 = autocast_bf16
 
     def forward(self, x):
         device = x.device.type if x.device.type in ('cuda', 'cpu') else 'cuda'
+        if (self.autocast_bf16 and torch.is_autocast_enabled(device)
+                and torch.get_autocast_dtype(device) == torch.bfloat16):
+            x = self.img_bev_encoder_neck(self.img_bev_encoder_backbone(x.to(torch.bfloat16)))
+            return x[0] if type(x) in (list, tuple) else x
         with torch.autocast(device, enabled=False):
             x = self.img_bev_encoder_backbone(x.float())
             x = self.img_bev_encoder_neck(x)

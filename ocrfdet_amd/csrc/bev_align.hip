@@ -18,6 +18,13 @@
 // realistic motion that is at most 25 candidates and at most 4 hits.  The lanes of a wave are neighbouring source
 // pixels, so their candidates are neighbouring output pixels.  A singular or strongly shrinking transform makes the box
 // the whole plane: slow, but correct and bounded.
+//
+// bfloat16 (the *_bf16 entry points: bf16 maps kept bf16 under autocast).  The kernels are templates on the element type
+// and the bf16 forms are the same bodies: coordinates, taps, validity and the box come from bev_align_index.h unchanged
+// and in float32, the taps / gradients are 2-byte loads widened exactly, the value and the gradient sum are the float32
+// expressions above, and the result is rounded once to nearest even.  So a bf16 kernel returns, bit for bit, what the
+// float32 kernel returns on the widened operands, rounded once.  Strides are counted in elements; a 16-byte store is
+// V = 8 pixels (h * w and the stride multiples of 8), the narrow form a 2-byte store.
 #include <hip/hip_runtime.h>
 
 #include "bev_align_index.h"
@@ -58,18 +65,20 @@ __device__ __forceinline__ Taps taps_at(const float* t, int i, int j, int h, int
   return p;
 }
 
-__device__ __forceinline__ float sample_value(const float* __restrict__ s, const Taps& p) {
-  const float v00 = p.v00 ? s[p.r0 + p.c0] : 0.0f, v01 = p.v01 ? s[p.r0 + p.c1] : 0.0f;
-  const float v10 = p.v10 ? s[p.r1 + p.c0] : 0.0f, v11 = p.v11 ? s[p.r1 + p.c1] : 0.0f;
+// T: float or bf16_t.  ONE float32 expression for both: the bf16 form widens its taps, the caller rounds the result once
+template <typename T>
+__device__ __forceinline__ float sample_value(const T* __restrict__ s, const Taps& p) {
+  const float v00 = p.v00 ? load_f32(s + (p.r0 + p.c0)) : 0.0f, v01 = p.v01 ? load_f32(s + (p.r0 + p.c1)) : 0.0f;
+  const float v10 = p.v10 ? load_f32(s + (p.r1 + p.c0)) : 0.0f, v11 = p.v11 ? load_f32(s + (p.r1 + p.c1)) : 0.0f;
   const float mx = 1.0f - p.lx, my = 1.0f - p.ly;
   const float top = mx * v00 + p.lx * v01, bot = mx * v10 + p.lx * v11;
   return my * top + p.ly * bot;
 }
 
-template <int V>
+template <typename T, int V>
 __global__ void __launch_bounds__(kThreads) bev_align_kernel(int c, int h, int w, int cblocks, int chunks, int units,
-                                                             const float* __restrict__ x, const float* __restrict__ tf,
-                                                             float* __restrict__ out, long long out_batch_stride) {
+                                                             const T* __restrict__ x, const float* __restrict__ tf,
+                                                             T* __restrict__ out, long long out_batch_stride) {
   const int P = h * w;
   const Walk<V> walk(w);
   for (int u = blockIdx.x; u < units; u += gridDim.x) {
@@ -79,8 +88,8 @@ __global__ void __launch_bounds__(kThreads) bev_align_kernel(int c, int h, int w
     float t[6];
 #pragma unroll
     for (int k = 0; k < 6; ++k) t[k] = tf[b * 9 + k];
-    const float* s = x + ((size_t)b * c + c0) * P;
-    float* o = out + (size_t)b * out_batch_stride + (size_t)c0 * P;
+    const T* s = x + ((size_t)b * c + c0) * P;
+    T* o = out + (size_t)b * out_batch_stride + (size_t)c0 * P;
     walk.groups(walk.first(chunk), P, [&](int idx, int y, int xx) {
       Taps p[V];
 #pragma unroll
@@ -94,15 +103,11 @@ __global__ void __launch_bounds__(kThreads) bev_align_kernel(int c, int h, int w
 #pragma unroll
       for (int ch = 0; ch < kChannels; ++ch) {
         if (ch < nc) {
-          const float* sc = s + ch * P;
+          const T* sc = s + ch * P;
           float v[V];
 #pragma unroll
           for (int k = 0; k < V; ++k) v[k] = sample_value(sc, p[k]);
-          if constexpr (V == 4) {
-            *reinterpret_cast<float4*>(o + ch * P + idx) = make_float4(v[0], v[1], v[2], v[3]);
-          } else {
-            o[ch * P + idx] = v[0];
-          }
+          store_group<V>(o + ch * P + idx, v);
         }
       }
     });
@@ -110,11 +115,12 @@ __global__ void __launch_bounds__(kThreads) bev_align_kernel(int c, int h, int w
 }
 
 // grad_x[b][ch][qy][qx] = sum over the output pixels (i, j) one of whose taps is (qx, qy) of weight * grad_out[b][ch][i][j]
+template <typename T>
 __global__ void __launch_bounds__(kThreads) bev_align_backward_kernel(int c, int h, int w, int cblocks, int total,
-                                                                      const float* __restrict__ grad_out,
+                                                                      const T* __restrict__ grad_out,
                                                                       long long grad_batch_stride,
                                                                       const float* __restrict__ tf,
-                                                                      float* __restrict__ grad_x) {
+                                                                      T* __restrict__ grad_x) {
   const int P = h * w;
   for (int n = blockIdx.x * kThreads + (int)threadIdx.x; n < total; n += gridDim.x * kThreads) {
     const int rest = n / P, pix = n - rest * P;
@@ -126,7 +132,7 @@ __global__ void __launch_bounds__(kThreads) bev_align_backward_kernel(int c, int
     for (int k = 0; k < 6; ++k) t[k] = tf[b * 9 + k];
     const Box box = source_box(t, h, w, qx, qy);
     const float fqx = (float)qx, fqy = (float)qy;
-    const float* g = grad_out + (size_t)b * grad_batch_stride + (size_t)c0 * P;
+    const T* g = grad_out + (size_t)b * grad_batch_stride + (size_t)c0 * P;
     float acc[kBwdChannels];
 #pragma unroll
     for (int ch = 0; ch < kBwdChannels; ++ch) acc[ch] = 0.0f;
@@ -136,33 +142,69 @@ __global__ void __launch_bounds__(kThreads) bev_align_backward_kernel(int c, int
         const bool hit = (s.x0 == fqx || s.x0 + 1.0f == fqx) && (s.y0 == fqy || s.y0 + 1.0f == fqy);
         if (hit) {
           const float wgt = axis_weight(s.y0, s.ly, fqy) * axis_weight(s.x0, s.lx, fqx);
-          const float* gp = g + i * w + j;
+          const T* gp = g + i * w + j;
 #pragma unroll
           for (int ch = 0; ch < kBwdChannels; ++ch) {
-            if (ch < nc) acc[ch] += wgt * gp[ch * P];
+            if (ch < nc) acc[ch] += wgt * load_f32(gp + ch * P);
           }
         }
       }
     }
-    float* d = grad_x + ((size_t)b * c + c0) * P + pix;
+    T* d = grad_x + ((size_t)b * c + c0) * P + pix;
 #pragma unroll
     for (int ch = 0; ch < kBwdChannels; ++ch) {
-      if (ch < nc) d[ch * P] = acc[ch];
+      if (ch < nc) store_f32(d + ch * P, acc[ch]);             // bf16: the one rounding
     }
   }
 }
 
-// The shapes both entry points accept: positive sizes, the contiguous (n, c, h, w) operand and the strided one (n rows
-// of c * h * w floats, `stride` floats apart) both below 2 GiB.  *P: floats per plane
-bool shapes_ok(int n, int c, int h, int w, long long stride, long long* P) {
+// The shapes the entry points accept: positive sizes, the contiguous (n, c, h, w) operand and the strided one (n rows
+// of c * h * w elements, `stride` elements apart) both below 2 GiB, counted in bytes of the element.  *P: elements per
+// plane
+bool shapes_ok(int n, int c, int h, int w, long long stride, long long elem_bytes, long long* P) {
   if (n <= 0 || c <= 0 || h <= 0 || w <= 0) return false;
   const long long planes = (long long)n * c, plane = (long long)h * w;           // each below 2^62
-  const long long limit = kTwoGiB / (long long)sizeof(float);
+  const long long limit = kTwoGiB / elem_bytes;
   if (planes >= limit || plane >= limit || planes * plane >= limit) return false;
   const long long row = (long long)c * plane;
   if (stride < row || stride >= limit || (n - 1) * stride + row >= limit) return false;
   *P = plane;
   return true;
+}
+
+template <typename T>
+int forward(int kernel_id, int n, int c, int h, int w, const T* x, const float* tf, T* out, long long out_batch_stride,
+            ocrf_stream_t stream) {
+  long long P;
+  if (!shapes_ok(n, c, h, w, out_batch_stride, sizeof(T), &P) || !x || !tf || !out) return (int)hipErrorInvalidValue;
+  constexpr int W = kWide<T>;
+  const int cblocks = (c + kChannels - 1) / kChannels;
+  const bool vec = P % W == 0 && out_batch_stride % W == 0 && aligned16(out);
+  const Units u = units_of((long long)n * cblocks, P, vec ? W : 1);
+  if (u.units >= kTwoGiB) return (int)hipErrorInvalidValue;
+  if (vec) {
+    ocrf::launch(kernel_id, bev_align_kernel<T, W>, dim3(u.grid), dim3(kThreads), 0, (hipStream_t)stream, c, h, w,
+                 cblocks, u.chunks, (int)u.units, x, tf, out, out_batch_stride);
+  } else {
+    ocrf::launch(kernel_id, bev_align_kernel<T, 1>, dim3(u.grid), dim3(kThreads), 0, (hipStream_t)stream, c, h, w,
+                 cblocks, u.chunks, (int)u.units, x, tf, out, out_batch_stride);
+  }
+  return (int)hipGetLastError();
+}
+
+template <typename T>
+int backward(int kernel_id, int n, int c, int h, int w, const T* grad_out, long long grad_batch_stride, const float* tf,
+             T* grad_x, ocrf_stream_t stream) {
+  long long P;
+  if (!shapes_ok(n, c, h, w, grad_batch_stride, sizeof(T), &P) || !grad_out || !tf || !grad_x) {
+    return (int)hipErrorInvalidValue;
+  }
+  const int cblocks = (c + kBwdChannels - 1) / kBwdChannels;
+  const long long total = (long long)n * cblocks * P;                            // <= n c h w < 2^30
+  const unsigned grid = capped_grid((total + kThreads - 1) / kThreads);
+  ocrf::launch(kernel_id, bev_align_backward_kernel<T>, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, c, h, w,
+               cblocks, (int)total, grad_out, grad_batch_stride, tf, grad_x);
+  return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -171,32 +213,23 @@ extern "C" {
 
 int ocrf_bev_align_forward(int n, int c, int h, int w, const float* x, const float* tf, float* out,
                            long long out_batch_stride, ocrf_stream_t stream) {
-  long long P;
-  if (!shapes_ok(n, c, h, w, out_batch_stride, &P) || !x || !tf || !out) return (int)hipErrorInvalidValue;
-  const int cblocks = (c + kChannels - 1) / kChannels;
-  const bool vec = P % 4 == 0 && out_batch_stride % 4 == 0 && aligned16(out);
-  const Units u = units_of((long long)n * cblocks, P, vec ? 4 : 1);
-  if (u.units >= kTwoGiB) return (int)hipErrorInvalidValue;
-  if (vec) {
-    ocrf::launch(OCRF_K_BEV_ALIGN, bev_align_kernel<4>, dim3(u.grid), dim3(kThreads), 0, (hipStream_t)stream, c, h, w,
-                 cblocks, u.chunks, (int)u.units, x, tf, out, out_batch_stride);
-  } else {
-    ocrf::launch(OCRF_K_BEV_ALIGN, bev_align_kernel<1>, dim3(u.grid), dim3(kThreads), 0, (hipStream_t)stream, c, h, w,
-                 cblocks, u.chunks, (int)u.units, x, tf, out, out_batch_stride);
-  }
-  return (int)hipGetLastError();
+  return forward(OCRF_K_BEV_ALIGN, n, c, h, w, x, tf, out, out_batch_stride, stream);
 }
 
 int ocrf_bev_align_backward(int n, int c, int h, int w, const float* grad_out, long long grad_batch_stride,
                             const float* tf, float* grad_x, ocrf_stream_t stream) {
-  long long P;
-  if (!shapes_ok(n, c, h, w, grad_batch_stride, &P) || !grad_out || !tf || !grad_x) return (int)hipErrorInvalidValue;
-  const int cblocks = (c + kBwdChannels - 1) / kBwdChannels;
-  const long long total = (long long)n * cblocks * P;                            // <= n c h w < 2^29
-  const unsigned grid = capped_grid((total + kThreads - 1) / kThreads);
-  ocrf::launch(OCRF_K_BEV_ALIGN_BWD, bev_align_backward_kernel, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, c,
-               h, w, cblocks, (int)total, grad_out, grad_batch_stride, tf, grad_x);
-  return (int)hipGetLastError();
+  return backward(OCRF_K_BEV_ALIGN_BWD, n, c, h, w, grad_out, grad_batch_stride, tf, grad_x, stream);
+}
+
+int ocrf_bev_align_forward_bf16(int n, int c, int h, int w, const unsigned short* x, const float* tf,
+                                unsigned short* out, long long out_batch_stride, ocrf_stream_t stream) {
+  return forward(OCRF_K_BEV_ALIGN_BF16, n, c, h, w, x, tf, out, out_batch_stride, stream);
+}
+
+int ocrf_bev_align_backward_bf16(int n, int c, int h, int w, const unsigned short* grad_out,
+                                 long long grad_batch_stride, const float* tf, unsigned short* grad_x,
+                                 ocrf_stream_t stream) {
+  return backward(OCRF_K_BEV_ALIGN_BWD_BF16, n, c, h, w, grad_out, grad_batch_stride, tf, grad_x, stream);
 }
 
 int ocrf_bev_align_source_box(const float* tf, int h, int w, int qx, int qy, int* box) {

@@ -150,14 +150,14 @@ const char* ocrf_kernel_name(int kernel_id) {
     case OCRF_K_CD_MASK: return "cd_mask_kernel";
     case OCRF_K_CD_SCAN: return "cd_scan_kernel";
     case OCRF_K_CD_WRITE: return "cd_write_kernel";
-    case OCRF_K_UPSAMPLE_CAT: return "upsample_cat_kernel<*>";
-    case OCRF_K_UPSAMPLE_CAT_BWD: return "upsample_cat_backward_kernel";
+    case OCRF_K_UPSAMPLE_CAT: return "upsample_cat_kernel<float, *>";
+    case OCRF_K_UPSAMPLE_CAT_BWD: return "upsample_cat_backward_kernel<float>";
     case OCRF_K_ADD_RELU: return "binary_kernel<*, AddRelu>";
     case OCRF_K_ADD_RELU_BWD: return "binary_kernel<*, Threshold>";
     case OCRF_K_UPSAMPLE_ADD: return "upsample_add_kernel<*>";
     case OCRF_K_UPSAMPLE_ADD_BWD: return "upsample_add_backward_kernel";
-    case OCRF_K_BEV_ALIGN: return "bev_align_kernel<*>";
-    case OCRF_K_BEV_ALIGN_BWD: return "bev_align_backward_kernel";
+    case OCRF_K_BEV_ALIGN: return "bev_align_kernel<float, *>";
+    case OCRF_K_BEV_ALIGN_BWD: return "bev_align_backward_kernel<float>";
     case OCRF_K_OPTIM_SQNORM: return "optim_grad_sqnorm_kernel";
     case OCRF_K_OPTIM_NORM_FINAL: return "optim_norm_final_kernel";
     case OCRF_K_OPTIM_STEP: return "optim_step_kernel";
@@ -165,6 +165,10 @@ const char* ocrf_kernel_name(int kernel_id) {
     case OCRF_K_ADD_RELU_BWD_BF16: return "binary_bf16_kernel<*, Threshold>";
     case OCRF_K_UPSAMPLE_ADD_BF16: return "upsample_add_bf16_kernel<*>";
     case OCRF_K_UPSAMPLE_ADD_BWD_BF16: return "upsample_add_backward_bf16_kernel";
+    case OCRF_K_UPSAMPLE_CAT_BF16: return "upsample_cat_kernel<unsigned short, *>";
+    case OCRF_K_UPSAMPLE_CAT_BWD_BF16: return "upsample_cat_backward_kernel<unsigned short>";
+    case OCRF_K_BEV_ALIGN_BF16: return "bev_align_kernel<unsigned short, *>";
+    case OCRF_K_BEV_ALIGN_BWD_BF16: return "bev_align_backward_kernel<unsigned short>";
     default: return "";
   }
 }

@@ -1,5 +1,6 @@
-// What the memory-bound plane kernels (resnet_fuse.hip, upsample_cat.hip) share: their constants, the access width, the
-// host's shape check and launch geometry, and the forward walk over a destination plane.
+// What the memory-bound plane kernels (resnet_fuse.hip, upsample_cat.hip, bev_align.hip) share: their constants, the
+// access width, the host's shape check and launch geometry, the forward walk over a destination plane, and the bf16
+// arithmetic of their *_bf16 forms.
 //
 // Layout.  A forward kernel sees every (b, c) destination plane as a flat run of P = Hout * Wout floats and cuts it into
 // chunks of kThreads x kGroups x V floats: a workgroup takes (plane, chunk) units in a grid-stride loop (the grid is
@@ -50,6 +51,65 @@ struct Vec16<1> {
 };
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// ---------------------------------------------------------------------------------------------- bf16 arithmetic
+// What every bf16 form of these kernels does: widen its operands to float32 (a shift: exact), compute in float32, round
+// once to nearest even.
+using bf16_t = unsigned short;
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ float widen(bf16_t h) { return __uint_as_float((unsigned)h << 16); }
+__device__ __forceinline__ float widen_lo(unsigned w) { return __uint_as_float(w << 16); }          // element 0 of a word
+__device__ __forceinline__ float widen_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }  // element 1
+// float32 -> bf16, to nearest even; a NaN stays a NaN
+__device__ __forceinline__ bf16_t round_one(float f) { return __builtin_bit_cast(bf16_t, (__bf16)f); }
+__device__ __forceinline__ unsigned round_pair(float lo, float hi) {
+  const f32x2 f = {lo, hi};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2));
+}
+
+// One element as float32 and back, for a kernel body that serves both element types: the float32 form moves the value,
+// the bf16 form widens it and rounds it once.
+__device__ __forceinline__ float load_f32(const float* p) { return *p; }
+__device__ __forceinline__ float load_f32(const bf16_t* p) { return widen(*p); }
+__device__ __forceinline__ void store_f32(float* p, float v) { *p = v; }
+__device__ __forceinline__ void store_f32(bf16_t* p, float v) { *p = round_one(v); }
+
+// The same for a group of V consecutive elements, one access: 16 bytes for the wide form (4 floats, 8 bf16), one
+// element for V = 1.  kWide<T> is the wide form's V, GroupOf<T, V> the type that moves a group untouched.
+template <typename T>
+constexpr int kWide = 16 / (int)sizeof(T);
+template <typename T, int V>
+struct GroupOf;
+template <int V>
+struct GroupOf<float, V> {
+  using type = typename Vec<V>::type;
+};
+template <int V>
+struct GroupOf<bf16_t, V> {
+  using type = typename Vec16<V>::type;
+};
+
+template <int V>
+__device__ __forceinline__ void store_group(float* p, const float (&v)[V]) {
+  if constexpr (V == 4) {
+    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+    static_assert(V == 1, "a group of floats is 4 or 1");
+    *p = v[0];
+  }
+}
+template <int V>
+__device__ __forceinline__ void store_group(bf16_t* p, const float (&v)[V]) {
+  if constexpr (V == 8) {
+    *reinterpret_cast<uint4*>(p) = make_uint4(round_pair(v[0], v[1]), round_pair(v[2], v[3]), round_pair(v[4], v[5]),
+                                              round_pair(v[6], v[7]));
+  } else {
+    static_assert(V == 1, "a group of bf16 is 8 or 1");
+    *p = round_one(v[0]);
+  }
+}
 
 // `planes` destination planes of Hout x Wout elements of `elem_bytes` each: the tables fit, and the destination-sized
 // operands (the largest) stay below 2 GiB

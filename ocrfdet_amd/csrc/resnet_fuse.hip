@@ -119,20 +119,7 @@ __global__ void __launch_bounds__(kThreads) binary_kernel(int n, int groups, int
 }
 
 // ---------------------------------------------------------------------------------------------- bf16 arithmetic
-using bf16_t = unsigned short;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float widen(bf16_t h) { return __uint_as_float((unsigned)h << 16); }
-__device__ __forceinline__ float widen_lo(unsigned w) { return __uint_as_float(w << 16); }          // element 0 of a word
-__device__ __forceinline__ float widen_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }  // element 1
-// float32 -> bf16, to nearest even; a NaN stays a NaN
-__device__ __forceinline__ bf16_t round_one(float f) { return __builtin_bit_cast(bf16_t, (__bf16)f); }
-__device__ __forceinline__ unsigned round_pair(float lo, float hi) {
-  const f32x2 f = {lo, hi};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2));
-}
-
+// bf16_t, widen / widen_lo / widen_hi and round_one / round_pair are plane_walk.h's
 struct AddReluBf16 {
   __device__ __forceinline__ bf16_t operator()(bf16_t a, bf16_t b) const {
     const bf16_t s = round_one(widen(a) + widen(b));
@@ -254,11 +241,6 @@ __device__ __forceinline__ void build_starts(int* start, int in, int out) {
     for (int i = lo; i <= hi; ++i) start[i] = d;
   }
 }
-
-__device__ __forceinline__ float load_f32(const float* p) { return *p; }
-__device__ __forceinline__ float load_f32(const bf16_t* p) { return widen(*p); }
-__device__ __forceinline__ void store_f32(float* p, float v) { *p = v; }
-__device__ __forceinline__ void store_f32(bf16_t* p, float v) { *p = round_one(v); }
 
 template <typename T>
 __device__ __forceinline__ void upsample_add_backward_body(int Hin, int Win, int Hout, int Wout, int total,

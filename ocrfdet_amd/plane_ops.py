@@ -16,12 +16,18 @@ a float product: the two differ in the last bits.
 The first two also take bfloat16 tensors (the ``*_bf16`` entry points of the same file), which is what they see between
 the convolutions under ``torch.autocast('cuda', dtype=torch.bfloat16)``: operands, result and gradients are all bf16,
 the sum is one float32 addition rounded once to nearest even, as torch's bf16 ops, and forward and ``add_relu``'s
-backward stay bit-equal to the ``*_torch`` formulations.  ``upsample_cat`` is float32 only (``BEVEncoder`` runs with
-autocast disabled).
+backward stay bit-equal to the ``*_torch`` formulations.
+
+``upsample_cat`` takes bfloat16 tensors too (``ocrf_upsample_cat_forward_bf16`` / ``_backward_bf16``), which is what it
+sees in a ``BEVEncoder`` with ``autocast_bf16=True`` under bf16 autocast: operands, result and gradients are all bf16,
+and the result is, bit for bit, that of the float32 kernel on the widened operands rounded once to nearest even
+(``upsample_cat(x2.float(), x1.float(), s).bfloat16()``; the backward alike).  A ``BEVEncoder`` as it is built keeps
+float32 and never sees bf16 here.
 
 The ops themselves never fall back: they raise on an input the kernels do not take.  The modules dispatch with the
-``*_fusable`` predicates: CUDA contiguous tensors that are all float32 (or, for the first two, all bfloat16) take the
-kernels, everything else (the CPU, float16 and float64, mixed dtypes, non-contiguous maps) the ``*_torch`` formulation.
+``*_fusable`` predicates: CUDA contiguous tensors that are all float32 (or all bfloat16: ``upsample_cat_bf16_fusable``
+for the third op) take the kernels, everything else (the CPU, float16 and float64, mixed dtypes, non-contiguous maps)
+the ``*_torch`` formulation.
 """
 import torch
 import torch.nn.functional as F
@@ -45,6 +51,14 @@ FUSED_MERGE_DEFAULT = True
 # the host more than the device (0.59x to 0.86x); the encoder in training at 12 images is host-bound either way (0.96x).
 FUSED_TAIL_BF16_DEFAULT = True
 FUSED_MERGE_BF16_DEFAULT = True
+# Default of ``FPN_LSS.fused_upsample_bf16`` (bfloat16 operands of ``upsample_cat``, which applies while ``fused_upsample``
+# is on; it only matters inside ``BEVEncoder``'s ``autocast_bf16`` opt-in), decided as the flags above, from
+# profiles/bev_encoder_bf16_time.txt (tools/time_bev_encoder.py --autocast bf16; INTEGRATION 3i has the table).  By device
+# time the bf16 kernels are faster than ``interpolate`` + ``cat`` on the same bf16 tensors at both reference shapes,
+# forward and forward + backward (up + cat 38x / 17x, ``up2[0]`` 10x / 5.1x; wall times agree), and the whole encoder
+# under autocast with the flag on is the fastest of the three arms: 3.32 against 6.65 ms eval forward and 10.0 against
+# 14.0 ms forward + backward in training (float32 inside autocast: 9.08 and 27.6 ms).
+FUSED_UPSAMPLE_BF16_DEFAULT = True
 
 # what the kernels of add_relu / upsample_add exist for: the suffix of their entry points
 _SUFFIX = {torch.float32: '', torch.bfloat16: '_bf16'}
@@ -183,14 +197,24 @@ def upsample_cat_torch(x2, x1, scale):
     return up if x2 is None else torch.cat([x2, up], dim=1)
 
 
-def upsample_cat_fusable(x2, x1, scale):
+def _upsample_cat_takes(x2, x1, scale, dtype):
     if not isinstance(scale, (int, float)) or scale != int(scale) or scale < 1:
         return False
     for t in (x1, x2):
-        if t is not None and not (_plain(t) and t.dim() == 4):
+        if t is not None and not (_plain(t, (dtype,)) and t.dim() == 4):
             return False
     return x2 is None or (x2.shape[0] == x1.shape[0] and x2.shape[2] == x1.shape[2] * int(scale)
                           and x2.shape[3] == x1.shape[3] * int(scale))
+
+
+def upsample_cat_fusable(x2, x1, scale):
+    """The float32 kernels take these operands."""
+    return _upsample_cat_takes(x2, x1, scale, torch.float32)
+
+
+def upsample_cat_bf16_fusable(x2, x1, scale):
+    """The bfloat16 kernels take these operands: ``x1`` and ``x2`` (where there is one) both bfloat16."""
+    return _upsample_cat_takes(x2, x1, scale, torch.bfloat16)
 
 
 class _UpsampleCat(torch.autograd.Function):
@@ -198,30 +222,34 @@ class _UpsampleCat(torch.autograd.Function):
     def forward(ctx, x2, x1, scale):
         B, C1, Hin, Win = x1.shape
         C2 = 0 if x2 is None else x2.shape[1]
-        out = torch.empty(B, C2 + C1, Hin * scale, Win * scale, dtype=torch.float32, device=x1.device)
-        _lib.launch('ocrf_upsample_cat_forward', x1.device, B, C2, C1, Hin, Win, scale, x2, x1, out)
+        out = torch.empty(B, C2 + C1, Hin * scale, Win * scale, dtype=x1.dtype, device=x1.device)
+        _lib.launch('ocrf_upsample_cat_forward' + _SUFFIX[x1.dtype], x1.device, B, C2, C1, Hin, Win, scale, x2, x1, out)
         ctx.shape = (B, C2, C1, Hin, Win, scale)
+        ctx.dtype = x1.dtype
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         B, C2, C1, Hin, Win, scale = ctx.shape
+        _check_grad(grad_out, ctx.dtype, 'upsample_cat')
         grad_out = grad_out.contiguous()
         grad_x2 = grad_x1 = None
         if ctx.needs_input_grad[0] and C2:
             grad_x2 = grad_out[:, :C2]
         if ctx.needs_input_grad[1]:
-            grad_x1 = torch.empty(B, C1, Hin, Win, dtype=torch.float32, device=grad_out.device)
-            _lib.launch('ocrf_upsample_cat_backward', grad_out.device, B, C2, C1, Hin, Win, scale, grad_out, grad_x1)
+            grad_x1 = torch.empty(B, C1, Hin, Win, dtype=ctx.dtype, device=grad_out.device)
+            _lib.launch('ocrf_upsample_cat_backward' + _SUFFIX[ctx.dtype], grad_out.device, B, C2, C1, Hin, Win, scale,
+                        grad_out, grad_x1)
         return grad_x2, grad_x1, None
 
 
 def upsample_cat(x2, x1, scale):
-    """``upsample_cat_torch`` as one HIP launch (``ocrf_upsample_cat_forward`` / ``_backward``): ``x1`` (B, C1, H, W)
-    upsampled by the integer ``scale`` behind the channels of ``x2`` (B, C2, H*scale, W*scale), or alone with ``x2``
-    None.  CUDA float32 contiguous tensors only: anything else raises (``FPN_LSS`` dispatches)."""
+    """``upsample_cat_torch`` as one HIP launch (``ocrf_upsample_cat_forward`` / ``_backward``, or their ``_bf16``
+    forms): ``x1`` (B, C1, H, W) upsampled by the integer ``scale`` behind the channels of ``x2`` (B, C2, H*scale,
+    W*scale), or alone with ``x2`` None.  CUDA contiguous tensors, both float32 or both bfloat16, only: anything else
+    (a mixed pair too) raises (``FPN_LSS`` dispatches).  The result and the gradients have the dtype of the operands."""
     _lib.require_cuda(x1, x2)
-    if not upsample_cat_fusable(x2, x1, scale):
-        raise _lib.OcrfHipError('upsample_cat takes contiguous float32 NCHW tensors, x2 scale times the size of x1, '
-                                'and an integer scale')
+    if not (upsample_cat_fusable(x2, x1, scale) or upsample_cat_bf16_fusable(x2, x1, scale)):
+        raise _lib.OcrfHipError('upsample_cat takes contiguous NCHW tensors, both float32 or both '
+                                'bfloat16, x2 scale times the size of x1, and an integer scale')
     return _UpsampleCat.apply(x2, x1, int(scale))

@@ -5,8 +5,8 @@
 * ``feature_transform``: ``gen_grid``'s ``tf``, the (n, 3, 3) map from a pixel of the key frame's BEV plane to the pixel
   of the adjacent frame's plane that shows the same place, in float64 and in closed form (torch only, no kernel);
 * ``shift_feature_torch(input, tf)``: the reference's formulation, a grid and ``F.grid_sample``;
-* ``shift_feature(input, tf, out=None)``: the same warp as one HIP launch (``csrc/bev_align.hip``), its backward a
-  gather launch without atomics: deterministic;
+* ``shift_feature(input, tf, out=None, keep_bf16=False)``: the same warp as one HIP launch (``csrc/bev_align.hip``), its
+  backward a gather launch without atomics: deterministic;
 * ``align_and_cat``: every frame warped (the key frame copied) straight into its channels of one concatenation;
 * ``gen_grid`` / ``shift_feature_method``: the reference's method signatures, adopted by assignment.
 
@@ -23,11 +23,16 @@ The ops never fall back: ``shift_feature`` raises on an input the kernels do not
 ``shift_feature_method`` dispatch: CUDA float32 contiguous maps take the kernels (float16 and bfloat16 maps after
 the cast to float32 that the reference's ``@force_fp32`` makes), everything else (the CPU, other dtypes,
 non-contiguous maps, poses that require a gradient) the torch formulation.
+
+``keep_bf16=True`` (opt-in; the reference casts) keeps maps that are all bfloat16 as they are: the ``*_bf16`` kernels
+read and write bf16, the result and the gradients are bf16, and each is bit for bit the float32 kernel's result on the
+widened maps rounded once to nearest even.  Maps that are not all bfloat16 are treated as without the keyword.
 """
 import torch
 import torch.nn.functional as F
 
 from . import _lib
+from .plane_ops import _SUFFIX                   # the suffix of the entry points by the dtype of the maps they take
 
 # Default of the dispatch flag of align_and_cat / shift_feature_method, from the measurement in
 # profiles/bev_align_time.txt (tools/time_bev_align.py; INTEGRATION 3g has the table): on (8, 80, 128, 128) maps with 1
@@ -111,6 +116,14 @@ def shift_feature_torch(input, tf):
     return F.grid_sample(input, grid, mode='bilinear', padding_mode='zeros', align_corners=True)
 
 
+def _shift_feature_torch_bf16(input, tf):
+    """``shift_feature_torch`` for a bfloat16 map with a bfloat16 result, as the bf16 kernels compute it: the map widened
+    (exact), grid and ``grid_sample`` in float32, the result rounded once.  (A grid in the map's own dtype would round
+    the sample positions to bf16: 2^-9 of a half plane, 0.12 pixel at a width of 128.)"""
+    with torch.autocast(input.device.type if input.device.type in ('cuda', 'cpu') else 'cuda', enabled=False):
+        return shift_feature_torch(input.float(), tf).to(torch.bfloat16)
+
+
 # ------------------------------------------------------------------------------------------------ the kernels
 _HALVES = (torch.float16, torch.bfloat16)
 
@@ -141,25 +154,36 @@ def _batch_stride(t):
 
 
 def _warp_into(x, tf32, dst):
-    """One forward launch: ``x`` (n, c, h, w) warped into ``dst``, an (n, c, h, w) view whose planes are contiguous and
-    whose samples are ``dst.stride(0)`` floats apart."""
+    """One forward launch: ``x`` (n, c, h, w), float32 or bfloat16, warped into ``dst``, an (n, c, h, w) view of the same
+    dtype whose planes are contiguous and whose samples are ``dst.stride(0)`` elements apart."""
     n, c, h, w = x.shape
-    _lib.launch('ocrf_bev_align_forward', x.device, n, c, h, w, x, tf32, dst, _batch_stride(dst))
+    _lib.launch('ocrf_bev_align_forward' + _SUFFIX[x.dtype], x.device, n, c, h, w, x, tf32, dst, _batch_stride(dst))
 
 
 def _gather_from(grad, tf32, shape):
-    """One backward launch: the gradient of the source of ``_warp_into`` from ``grad``, addressed like ``dst``."""
+    """One backward launch: the gradient of the source of ``_warp_into`` from ``grad``, addressed like ``dst``, in the
+    dtype of ``grad``."""
     n, c, h, w = shape
-    grad_x = torch.empty(n, c, h, w, dtype=torch.float32, device=grad.device)
-    _lib.launch('ocrf_bev_align_backward', grad.device, n, c, h, w, grad, _batch_stride(grad), tf32, grad_x)
+    grad_x = torch.empty(n, c, h, w, dtype=grad.dtype, device=grad.device)
+    _lib.launch('ocrf_bev_align_backward' + _SUFFIX[grad.dtype], grad.device, n, c, h, w, grad, _batch_stride(grad),
+                tf32, grad_x)
     return grad_x
 
 
 def _sliceable(dst, like):
-    """``dst`` can take the warp of ``like``: same shape, float32, same device, contiguous (c, h, w) blocks."""
+    """``dst`` can take the warp of ``like``: same shape, dtype and device, contiguous (c, h, w) blocks."""
     n, c, h, w = like.shape
-    return (dst.shape == like.shape and dst.dtype == torch.float32 and dst.device == like.device
+    return (dst.shape == like.shape and dst.dtype == like.dtype and dst.device == like.device
             and dst.stride()[1:] == (h * w, w, 1) and (n == 1 or dst.stride(0) >= c * h * w))
+
+
+def _all_bf16(feats):
+    return all(x.dtype == torch.bfloat16 for x in feats)
+
+
+def _check_bf16_grad(grad_out):
+    if grad_out.dtype != torch.bfloat16:
+        raise _lib.OcrfHipError(f'bev_align backward: grad_out is {grad_out.dtype}, the forward ran in bfloat16')
 
 
 class _ShiftFeature(torch.autograd.Function):
@@ -179,29 +203,79 @@ class _ShiftFeature(torch.autograd.Function):
         return _gather_from(grad_out.contiguous(), tf32, ctx.shape), None
 
 
-def shift_feature(input, tf, out=None):
+class _ShiftFeatureBf16(torch.autograd.Function):
+    """``_ShiftFeature`` on a bfloat16 map that stays bfloat16: no cast of the inputs, the ``_bf16`` kernels."""
+
+    @staticmethod
+    def forward(ctx, input, tf32):
+        out = torch.empty_like(input)
+        _warp_into(input, tf32, out)
+        ctx.save_for_backward(tf32)
+        ctx.shape = tuple(input.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        tf32, = ctx.saved_tensors
+        _check_bf16_grad(grad_out)
+        return _gather_from(grad_out.contiguous(), tf32, ctx.shape), None
+
+
+def shift_feature(input, tf, out=None, keep_bf16=False):
     """``shift_feature_torch`` as one HIP launch (``ocrf_bev_align_forward``; backward ``ocrf_bev_align_backward``, a
     gather): ``input`` (n, c, h, w) sampled at ``tf`` (n, 3, 3, any floating dtype, on the device of ``input``; rounded
     to float32).  CUDA float32 contiguous input only, a float16 or bfloat16 one is cast to float32 first
     (``@force_fp32``); anything else raises.  ``tf`` gets no gradient.
 
     ``out``: an (n, c, h, w) float32 view with contiguous (c, h, w) blocks, such as a channel slice of a wider
-    concatenation, to write into; it is returned.  This form records no gradient, so ``input`` must not require one."""
+    concatenation, to write into; it is returned.  This form records no gradient, so ``input`` must not require one.
+
+    ``keep_bf16``: a bfloat16 ``input`` is not cast: ``ocrf_bev_align_forward_bf16`` / ``_backward_bf16`` read and write
+    bf16, the result and the gradient are bf16, and ``out`` must then be a bfloat16 view.  Any other input is treated
+    as without it."""
     _lib.require_cuda(input, tf)
     if not _plain(input):
         raise _lib.OcrfHipError('shift_feature takes a non-empty contiguous float32 (or float16 / bfloat16) NCHW map on the '
                                 'GPU')
-    input = _cast(input)
+    keep = keep_bf16 and input.dtype == torch.bfloat16
+    if not keep:
+        input = _cast(input)
     tf32 = _tf32(tf, input)
     if out is None:
-        return _ShiftFeature.apply(input, tf32)
+        return (_ShiftFeatureBf16 if keep else _ShiftFeature).apply(input, tf32)
     if torch.is_grad_enabled() and input.requires_grad:
         raise _lib.OcrfHipError('shift_feature(out=...) records no gradient: detach the input, or use align_and_cat')
     if not _sliceable(out, input):
-        raise _lib.OcrfHipError('out must be a float32 (n, c, h, w) view with contiguous (c, h, w) blocks on the '
-                                'device of the input')
+        raise _lib.OcrfHipError(f'out must be a {"bfloat16" if keep else "float32"} (n, c, h, w) view with contiguous '
+                                '(c, h, w) blocks on the device of the input')
     _warp_into(input, tf32, out)
     return out
+
+
+def _align_into(out, tfs, feats):
+    """``feats[k]`` copied (``tfs[k]`` None) or warped into its channels of ``out``, all of one dtype."""
+    C = feats[0].shape[1]
+    for k, (x, tf32) in enumerate(zip(feats, tfs)):
+        dst = out[:, k * C:(k + 1) * C]
+        if tf32 is None:
+            dst.copy_(x)
+        else:
+            _warp_into(x, tf32, dst)
+
+
+def _align_grads(ctx, grad_out):
+    """The backward of ``_align_into``: the gradients of the frames, in the dtype of ``grad_out``."""
+    B, C, H, W = ctx.shape
+    grad_out = grad_out.contiguous()
+    grads = []
+    for k, tf32 in enumerate(ctx.tfs):
+        if not ctx.needs_input_grad[1 + k]:
+            grads.append(None)                       # the reference computes adjacent frames under no_grad
+        elif tf32 is None:
+            grads.append(grad_out[:, k * C:(k + 1) * C])
+        else:
+            grads.append(_gather_from(grad_out[:, k * C:(k + 1) * C], tf32, ctx.shape))
+    return (None, *grads)
 
 
 class _AlignCat(torch.autograd.Function):
@@ -213,12 +287,7 @@ class _AlignCat(torch.autograd.Function):
     def forward(ctx, tfs, *feats):
         B, C, H, W = feats[0].shape
         out = torch.empty(B, len(feats) * C, H, W, dtype=torch.float32, device=feats[0].device)
-        for k, (x, tf32) in enumerate(zip(feats, tfs)):
-            dst = out[:, k * C:(k + 1) * C]
-            if tf32 is None:
-                dst.copy_(x)
-            else:
-                _warp_into(x, tf32, dst)
+        _align_into(out, tfs, feats)
         ctx.tfs = tfs                                # float32 tensors without a gradient, none of them an input
         ctx.shape = (B, C, H, W)
         return out
@@ -226,17 +295,26 @@ class _AlignCat(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_bwd(device_type='cuda')
     def backward(ctx, grad_out):
-        B, C, H, W = ctx.shape
-        grad_out = grad_out.contiguous()
-        grads = []
-        for k, tf32 in enumerate(ctx.tfs):
-            if not ctx.needs_input_grad[1 + k]:
-                grads.append(None)                   # the reference computes adjacent frames under no_grad
-            elif tf32 is None:
-                grads.append(grad_out[:, k * C:(k + 1) * C])
-            else:
-                grads.append(_gather_from(grad_out[:, k * C:(k + 1) * C], tf32, ctx.shape))
-        return (None, *grads)
+        return _align_grads(ctx, grad_out)
+
+
+class _AlignCatBf16(torch.autograd.Function):
+    """``_AlignCat`` on bfloat16 maps that stay bfloat16: no cast of the inputs, the ``_bf16`` kernels, a bfloat16
+    concatenation and bfloat16 gradients."""
+
+    @staticmethod
+    def forward(ctx, tfs, *feats):
+        B, C, H, W = feats[0].shape
+        out = torch.empty(B, len(feats) * C, H, W, dtype=torch.bfloat16, device=feats[0].device)
+        _align_into(out, tfs, feats)
+        ctx.tfs = tfs
+        ctx.shape = (B, C, H, W)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        _check_bf16_grad(grad_out)
+        return _align_grads(ctx, grad_out)
 
 
 def align_fusable(feats, tfs):
@@ -249,7 +327,8 @@ def align_fusable(feats, tfs):
     return not any(tf is not None and tf.requires_grad and torch.is_grad_enabled() for tf in tfs)
 
 
-def align_and_cat(feats, frame_ids, sensor2keyegos, bda, grid_interval, grid_lower_bound, bda_adj=None, fused=None):
+def align_and_cat(feats, frame_ids, sensor2keyegos, bda, grid_interval, grid_lower_bound, bda_adj=None, fused=None,
+                  keep_bf16=False):
     """The aligned concatenation in front of the BEV encoder: ``feats`` a list of (B, C, H, W) maps, ``frame_ids[k]`` the
     index into the per-frame list ``sensor2keyegos`` of the frame ``feats[k]`` came from.  Frame 0 is the key frame and
     is copied; every other map is warped with ``feature_transform([sensor2keyegos[0], sensor2keyegos[frame_ids[k]]],
@@ -262,15 +341,24 @@ def align_and_cat(feats, frame_ids, sensor2keyegos, bda, grid_interval, grid_low
     ``fused`` (default ``FUSED_ALIGN_DEFAULT``): maps that ``align_fusable`` accepts are written by one HIP launch per
     warped frame straight into their channels of the result, without ``torch.cat``; the backward hands a copied frame a
     view of the incoming gradient, runs one gather launch per warped frame that requires a gradient and nothing for one
-    that does not.  Everything else takes ``shift_feature_torch`` and ``torch.cat``."""
+    that does not.  Everything else takes ``shift_feature_torch`` and ``torch.cat``.
+
+    ``keep_bf16``: maps that are ALL bfloat16 are not cast to float32: the ``*_bf16`` kernels write a bfloat16
+    concatenation (the key frame a bf16 copy), the gradients are bfloat16, and the torch formulation runs on the bf16 maps
+    too.  Maps that are not all bfloat16 (float16, float32, a mixed list) are treated as without it."""
     frame_ids = [int(f) for f in frame_ids]
     if len(frame_ids) != len(feats) or not feats:
         raise ValueError('align_and_cat takes one frame id per feature map')
     tfs = [None if fid == 0 else feature_transform([sensor2keyegos[0], sensor2keyegos[fid]], bda, grid_interval,
                                                    grid_lower_bound, bda_adj=bda_adj) for fid in frame_ids]
+    keep = keep_bf16 and _all_bf16(feats)
     if (FUSED_ALIGN_DEFAULT if fused is None else fused) and align_fusable(feats, tfs):
-        feats = [_cast(x) for x in feats]
-        return _AlignCat.apply(tuple(None if tf is None else _tf32(tf, feats[0]) for tf in tfs), *feats)
+        if not keep:
+            feats = [_cast(x) for x in feats]
+        return (_AlignCatBf16 if keep else _AlignCat).apply(
+            tuple(None if tf is None else _tf32(tf, feats[0]) for tf in tfs), *feats)
+    if keep:
+        return torch.cat([x if tf is None else _shift_feature_torch_bf16(x, tf) for x, tf in zip(feats, tfs)], dim=1)
     return torch.cat([x if tf is None else shift_feature_torch(_cast(x), tf) for x, tf in zip(feats, tfs)], dim=1)
 
 
@@ -291,8 +379,10 @@ def gen_grid(self, input, sensor2keyegos, bda, bda_adj=None):
 def shift_feature_method(self, input, sensor2keyegos, bda, bda_adj=None):
     """``BEVDet4D.shift_feature`` (bevdet.py:372-376), adopted with ``Detector.shift_feature = shift_feature_method``.
     With ``input`` (num_frame - 1, C, H, W) and poses repeated per frame it is the sequential test's alignment
-    (bevdet.py:401-406).  ``self.fused_align`` (default ``FUSED_ALIGN_DEFAULT``) and ``align_fusable`` dispatch."""
+    (bevdet.py:401-406).  ``self.fused_align`` (default ``FUSED_ALIGN_DEFAULT``) and ``align_fusable`` dispatch;
+    ``self.align_keep_bf16`` (default False) is ``shift_feature``'s ``keep_bf16``."""
     tf = _method_transform(self, sensor2keyegos, bda, bda_adj)
+    keep = getattr(self, 'align_keep_bf16', False) and input.dtype == torch.bfloat16
     if getattr(self, 'fused_align', FUSED_ALIGN_DEFAULT) and align_fusable([input], [tf]):
-        return shift_feature(input, tf.to(input.device))
-    return shift_feature_torch(_cast(input), tf)
+        return shift_feature(input, tf.to(input.device), keep_bf16=keep)
+    return _shift_feature_torch_bf16(input, tf) if keep else shift_feature_torch(_cast(input), tf)

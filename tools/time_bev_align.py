@@ -7,6 +7,11 @@ for (8, 80, 128, 128) maps, the key frame plus 1 and plus 8 warped frames, forwa
 
     python tools/time_bev_align.py [--iters N] [--out profiles/bev_align_time.txt]
 
+``--dtype bf16``: the same rows for bfloat16 maps kept bfloat16 (``keep_bf16=True``): ``ocrf_bev_align_forward_bf16`` /
+``_backward_bf16`` against the torch formulation on the bf16 maps (``grid_sample`` + ``cat``).
+
+    python tools/time_bev_align.py --dtype bf16 [--iters N] [--out profiles/bev_align_bf16_time.txt]
+
 Every case runs in a child process of its own under a time limit (``--limit`` seconds); the first case that fails or
 runs out of time ends the run.
 """
@@ -60,7 +65,7 @@ def _profile(fn, reps=5):
     return count / reps, dev_us / 1e3 / reps, {k: v / 1e3 / reps for k, v in own.items()}
 
 
-def run_case(frames, mode, iters):
+def run_case(frames, mode, iters, dtype=None):
     import torch
     from time_bev_encoder import _wall
     from ocrfdet_amd import temporal
@@ -68,21 +73,27 @@ def run_case(frames, mode, iters):
     dev = torch.device('cuda:0')
     B, C, H, W = SHAPE
     train = mode != 'forward'
+    keep = dtype == 'bf16'
+    kw = dict(keep_bf16=True) if keep else {}
     feats = [torch.randn(SHAPE, device=dev, requires_grad=train) for _ in range(frames + 1)]
+    if keep:
+        feats = [f.detach().bfloat16().requires_grad_(train) for f in feats]
     s2k = poses(frames + 1, B, dev)
     bda = torch.eye(3, device=dev).repeat(B, 1, 1)
     interval, lower = torch.tensor([0.8, 0.8, 8.0]), torch.tensor([-51.2, -51.2, -5.0])
     ids = list(range(frames + 1))
     g = torch.randn(B, (frames + 1) * C, H, W, device=dev) if train else None
+    if keep and train:
+        g = g.bfloat16()
 
     def arm(fused):
         def run():
             if not train:
                 with torch.no_grad():
-                    return temporal.align_and_cat(feats, ids, s2k, bda, interval, lower, fused=fused)
+                    return temporal.align_and_cat(feats, ids, s2k, bda, interval, lower, fused=fused, **kw)
             for f in feats:
                 f.grad = None
-            temporal.align_and_cat(feats, ids, s2k, bda, interval, lower, fused=fused).backward(g)
+            temporal.align_and_cat(feats, ids, s2k, bda, interval, lower, fused=fused, **kw).backward(g)
         return run
     fused, torch_ = arm(True), arm(False)
     for fn in (fused, torch_):
@@ -91,10 +102,11 @@ def run_case(frames, mode, iters):
     (fb, fm), (tb, tm) = _wall([fused, torch_], iters)
     fl, fd, own = _profile(fused)
     tl, td, _ = _profile(torch_)
-    print(f'{frames} warped frame(s) of {SHAPE}, {mode}: fused {fd:.4f} ms device, {fl:.0f} launches, wall best {fb:.4f} '
+    print(f'{frames} warped frame(s) of {SHAPE}{" bf16" if keep else ""}, {mode}: fused {fd:.4f} ms device, {fl:.0f} launches, wall best {fb:.4f} '
           f'/ median {fm:.4f} ms | torch {td:.4f} ms device, {tl:.0f} launches, wall best {tb:.4f} / median {tm:.4f} ms '
           f'| torch / fused device {td / fd:.2f}x, wall median {tm / fm:.2f}x')
-    nbytes = 4 * 2 * B * C * H * W                             # a map read once, its channels of the result written once
+    # a map read once, its channels of the result written once
+    nbytes = (2 if keep else 4) * 2 * B * C * H * W
     for which, ms in sorted(own.items()):
         ms /= frames
         print(f'    {which} kernel {ms:.4f} ms per warped frame: {nbytes / 1e6:.1f} MB -> {nbytes / ms / 1e9:.2f} TB/s, '
@@ -107,14 +119,16 @@ def main():
     ap.add_argument('--out', default=None)
     ap.add_argument('--limit', type=int, default=240, help='seconds per case')
     ap.add_argument('--case', type=int, default=None, help='(internal) run this one case in this process')
+    ap.add_argument('--dtype', choices=['bf16'], default=None, help='bfloat16 maps kept bfloat16 (keep_bf16=True)')
     a = ap.parse_args()
+    extra = ['--dtype', a.dtype] if a.dtype else []
     if a.case is not None:
-        run_case(*CASES[a.case], a.iters)
+        run_case(*CASES[a.case], a.iters, a.dtype)
         return 0
     lines = []
     for k in range(len(CASES)):
         try:
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), '--case', str(k), '--iters', str(a.iters)],
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), '--case', str(k), '--iters', str(a.iters)] + extra,
                                stdout=subprocess.PIPE, text=True, timeout=a.limit)
         except subprocess.TimeoutExpired:
             print(f'case {CASES[k]} ran out of its {a.limit} s: stopping', file=sys.stderr)
