@@ -519,6 +519,29 @@ int ocrf_stereo_cost_volume(int BN, int C, int H, int W, int D, const float *pre
                             const float *frustum_d, long long stride_d, const float *k2s_sensor, const float *intrins,
                             const float *post_rots, const float *post_trans, float bias, int mode, float *out,
                             ocrf_stream_t stream);
+/*
+ * The same volume from bfloat16 features (csrc/stereo_bf16.hip), opt-in: two packs and one launch, float32 arithmetic
+ * on the widened values in ocrf_stereo_cost_volume's order, so out holds, bit for bit, what that entry gives on the
+ * features cast to float32.
+ *
+ * ocrf_stereo_pack_bf16: src (BN,C,H,W) bf16 contiguous -> dst (BN,NB,H,W,8) bf16, blocks of 8 channels per pixel, with
+ *   G = C / 4 whole groups and NB = (G + 1) / 2: dst[cam][b][y][x][k] = src[cam][8 b + k][y][x] where 8 b + k < 4 G, else
+ *   +0 (channels past the last whole group are dropped; the upper half of the last block is zero when G is odd).  Every
+ *   element of dst is written; one launch per tensor.  dst 16-byte aligned.
+ * ocrf_stereo_cost_volume_bf16: the arguments of ocrf_stereo_cost_volume with prev, curr PACKED as above (16-byte
+ *   aligned) and C the channel count of the unpacked features; out (BN,D,H,W) f32, mode as above.  One launch,
+ *   deterministic, no atomics.
+ * Limits of both: C >= 4, H >= 2, W >= 2; one camera's packed tensor is addressed in unsigned 32-bit bytes, so
+ *   NB*H*W*16 <= 2^32 - 1; D*H*W < 2^31; fewer than 2^31 workgroups.  Anything else, a NULL or a misaligned packed
+ *   pointer returns hipErrorInvalidValue and launches nothing.
+ */
+int ocrf_stereo_pack_bf16(int BN, int C, int H, int W, const unsigned short *src, unsigned short *dst,
+                          ocrf_stream_t stream);
+int ocrf_stereo_cost_volume_bf16(int BN, int C, int H, int W, int D, const unsigned short *prev,
+                                 const unsigned short *curr, const float *frustum_u, long long stride_u,
+                                 const float *frustum_v, long long stride_v, const float *frustum_d, long long stride_d,
+                                 const float *k2s_sensor, const float *intrins, const float *post_rots,
+                                 const float *post_trans, float bias, int mode, float *out, ocrf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Training targets and losses of the detection head (csrc/center_head.hip): centerpoint_head.py CenterHead
@@ -1233,7 +1256,9 @@ enum {
   OCRF_K_UPSAMPLE_CAT_BF16 = 117,     /* upsample_cat_kernel<unsigned short, V> */
   OCRF_K_UPSAMPLE_CAT_BWD_BF16 = 118, /* upsample_cat_backward_kernel<unsigned short> */
   OCRF_K_BEV_ALIGN_BF16 = 119,        /* bev_align_kernel<unsigned short, V> */
-  OCRF_K_BEV_ALIGN_BWD_BF16 = 120     /* bev_align_backward_kernel<unsigned short> */
+  OCRF_K_BEV_ALIGN_BWD_BF16 = 120,    /* bev_align_backward_kernel<unsigned short> */
+  OCRF_K_STEREO_PACK_BF16 = 121,      /* stereo_pack_bf16_kernel */
+  OCRF_K_STEREO_COST_VOLUME_BF16 = 122 /* stereo_cost_volume_bf16_kernel */
 };
 const char *ocrf_kernel_name(int kernel_id);           /* symbol as rocprofv3 prints it */
 /* Diagnostic: a one-thread kernel that stores the device's constant-rate clock (wall_clock64, 100 MHz)

@@ -169,6 +169,8 @@ const char* ocrf_kernel_name(int kernel_id) {
     case OCRF_K_UPSAMPLE_CAT_BWD_BF16: return "upsample_cat_backward_kernel<unsigned short>";
     case OCRF_K_BEV_ALIGN_BF16: return "bev_align_kernel<unsigned short, *>";
     case OCRF_K_BEV_ALIGN_BWD_BF16: return "bev_align_backward_kernel<unsigned short>";
+    case OCRF_K_STEREO_PACK_BF16: return "stereo_pack_bf16_kernel";
+    case OCRF_K_STEREO_COST_VOLUME_BF16: return "stereo_cost_volume_bf16_kernel";
     default: return "";
   }
 }

@@ -38,109 +38,11 @@
 
 #include "launch.h"
 #include "ocrf_hip.h"
+#include "stereo_common.h"
 
 namespace {
 
-constexpr int kWaves = 4;
-constexpr int kThreads = 64 * kWaves;
-constexpr int kJ = 8;                   // depth bins per chunk held in registers
-
-struct Cam {
-  float pri[9];                         // inv(post_rot)
-  float comb[9];                        // R_k2s . inv(K)
-  float K[9];
-  float t[3], pt[3];                    // t_k2s, post_trans
-  float pr2[4];                         // post_rot[:2, :2]
-};
-
-__device__ __forceinline__ void inv3(const float* m, float* r) {
-  const float c00 = m[4] * m[8] - m[5] * m[7];
-  const float c01 = m[5] * m[6] - m[3] * m[8];
-  const float c02 = m[3] * m[7] - m[4] * m[6];
-  const float det = m[0] * c00 + m[1] * c01 + m[2] * c02;
-  const float id = 1.0f / det;
-  r[0] = c00 * id;
-  r[1] = (m[2] * m[7] - m[1] * m[8]) * id;
-  r[2] = (m[1] * m[5] - m[2] * m[4]) * id;
-  r[3] = c01 * id;
-  r[4] = (m[0] * m[8] - m[2] * m[6]) * id;
-  r[5] = (m[2] * m[3] - m[0] * m[5]) * id;
-  r[6] = c02 * id;
-  r[7] = (m[1] * m[6] - m[0] * m[7]) * id;
-  r[8] = (m[0] * m[4] - m[1] * m[3]) * id;
-}
-
-__device__ __forceinline__ void load_cam(int cam, const float* k2s, const float* intrins, const float* post_rots,
-                                         const float* post_trans, Cam* c) {
-  const float* S = k2s + cam * 16;
-  const float* Kp = intrins + cam * 9;
-  const float* P = post_rots + cam * 9;
-  float Ki[9];
-  for (int i = 0; i < 9; ++i) c->K[i] = Kp[i];
-  inv3(c->K, Ki);
-  float Pm[9];
-  for (int i = 0; i < 9; ++i) Pm[i] = P[i];
-  inv3(Pm, c->pri);
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j)
-      c->comb[i * 3 + j] = S[i * 4 + 0] * Ki[0 * 3 + j] + S[i * 4 + 1] * Ki[1 * 3 + j] + S[i * 4 + 2] * Ki[2 * 3 + j];
-    c->t[i] = S[i * 4 + 3];
-    c->pt[i] = post_trans[cam * 3 + i];
-  }
-  c->pr2[0] = Pm[0];
-  c->pr2[1] = Pm[1];
-  c->pr2[2] = Pm[3];
-  c->pr2[3] = Pm[4];
-}
-
-// Normalised grid coordinate of frustum cell (u, v, dep): gen_grid's steps 1-6 and the normalisation
-__device__ __forceinline__ void grid_point(const Cam& c, float u, float v, float dep, float wi1, float hi1, float* px,
-                                           float* py) {
-  const float a0 = u - c.pt[0], a1 = v - c.pt[1], a2 = dep - c.pt[2];
-  float p0 = c.pri[0] * a0 + c.pri[1] * a1 + c.pri[2] * a2;
-  float p1 = c.pri[3] * a0 + c.pri[4] * a1 + c.pri[5] * a2;
-  const float p2 = c.pri[6] * a0 + c.pri[7] * a1 + c.pri[8] * a2;
-  p0 = p0 * p2;
-  p1 = p1 * p2;
-  const float q0 = c.comb[0] * p0 + c.comb[1] * p1 + c.comb[2] * p2 + c.t[0];
-  const float q1 = c.comb[3] * p0 + c.comb[4] * p1 + c.comb[5] * p2 + c.t[1];
-  const float q2 = c.comb[6] * p0 + c.comb[7] * p1 + c.comb[8] * p2 + c.t[2];
-  const bool neg = !(q2 >= 1e-3f);       // neg_mask (NaN included: such a cell samples nothing)
-  const float r0 = c.K[0] * q0 + c.K[1] * q1 + c.K[2] * q2;
-  const float r1 = c.K[3] * q0 + c.K[4] * q1 + c.K[5] * q2;
-  const float r2 = c.K[6] * q0 + c.K[7] * q1 + c.K[8] * q2;
-  const float x = r0 / r2, y = r1 / r2;
-  const float s0 = c.pr2[0] * x + c.pr2[1] * y + c.pt[0];
-  const float s1 = c.pr2[2] * x + c.pr2[3] * y + c.pt[1];
-  *px = neg ? -2.0f : s0 / wi1 * 2.0f - 1.0f;
-  *py = neg ? -2.0f : s1 / hi1 * 2.0f - 1.0f;
-}
-
-// grid_sample's bilinear taps (align_corners=True, zeros padding) as clamped in-plane offsets and masked weights:
-// an out-of-range corner keeps weight 0 and reads an in-range address, so every load is in bounds.  Offsets are in
-// bytes within one channel plane: the voffset of a buffer load whose soffset selects the plane.
-__device__ __forceinline__ void taps(float px, float py, int H, int W, unsigned* o, float* w) {
-  const float ix = ((px + 1.0f) / 2.0f) * (float)(W - 1);
-  const float iy = ((py + 1.0f) / 2.0f) * (float)(H - 1);
-  // both corners of an axis outside (or NaN): nothing is sampled
-  const bool ok = ix > -1.0f && ix < (float)W && iy > -1.0f && iy < (float)H;
-  const float fx = ok ? floorf(ix) : 0.0f, fy = ok ? floorf(iy) : 0.0f;
-  const int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
-  const float nw = (fx + 1.0f - ix) * (fy + 1.0f - iy);
-  const float ne = (ix - fx) * (fy + 1.0f - iy);
-  const float sw = (fx + 1.0f - ix) * (iy - fy);
-  const float se = (ix - fx) * (iy - fy);
-  const bool bx0 = ok && x0 >= 0, bx1 = ok && x1 <= W - 1, by0 = ok && y0 >= 0, by1 = ok && y1 <= H - 1;
-  const int cx0 = bx0 ? x0 : 0, cx1 = bx1 ? x1 : W - 1, cy0 = by0 ? y0 : 0, cy1 = by1 ? y1 : H - 1;
-  o[0] = 4u * (unsigned)(cy0 * W + cx0);
-  o[1] = 4u * (unsigned)(cy0 * W + cx1);
-  o[2] = 4u * (unsigned)(cy1 * W + cx0);
-  o[3] = 4u * (unsigned)(cy1 * W + cx1);
-  w[0] = (bx0 && by0) ? nw : 0.0f;
-  w[1] = (bx1 && by0) ? ne : 0.0f;
-  w[2] = (bx0 && by1) ? sw : 0.0f;
-  w[3] = (bx1 && by1) ? se : 0.0f;
-}
+using namespace ocrf::stereo;
 
 __device__ __forceinline__ float ld(__amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned soff) {
   return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (int)voff, (int)soff, 0));
@@ -180,13 +82,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3
     const int d0 = ch * kJ;
     unsigned o[kJ][4];
     float wt[kJ][4];
-#pragma unroll
-    for (int j = 0; j < kJ; ++j) {
-      const int d = min(d0 + j, D - 1);
-      float px, py;
-      grid_point(cm, u, v, fd[(long long)d * sd], wi1, hi1, &px, &py);
-      taps(px, py, H, W, o[j], wt[j]);
-    }
+    chunk_taps<sizeof(float), kJ>(cm, u, v, fd, sd, d0, D, wi1, hi1, H, W, o, wt);
     float cost[kJ], grp[kJ];
     unsigned zero = 0u;
 #pragma unroll
@@ -202,13 +98,10 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3
 #pragma unroll
         for (int j = 0; j < kJ; ++j) {
           if (cc == 0) grp[j] = 0.0f;
-          float s = ld(rs, o[j][0], plane) * wt[j][0];
-          s = s + ld(rs, o[j][1], plane) * wt[j][1];
-          s = s + ld(rs, o[j][2], plane) * wt[j][2];
-          s = s + ld(rs, o[j][3], plane) * wt[j][3];
+          const float s = warp_value(ld(rs, o[j][0], plane), ld(rs, o[j][1], plane), ld(rs, o[j][2], plane),
+                                     ld(rs, o[j][3], plane), wt[j]);
           warp[j] = s;
-          const float a = fabsf(cur - s);
-          grp[j] = grp[j] + a;
+          grp[j] = group_add(grp[j], cur, s);
         }
         if (c == cb) {
 #pragma unroll
@@ -218,37 +111,10 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3
 #pragma unroll
       for (int j = 0; j < kJ; ++j) cost[j] += grp[j];
     }
-#pragma unroll
-    for (int j = 0; j < kJ; ++j) {
-      if (d0 + j < D) {
-        const float r = -(((zero >> j) & 1u) ? cost[j] + bias : cost[j]);
-        if (live) out_px[(size_t)(d0 + j) * HW] = r;
-        const float m = fmaxf(run_max, r);
-        run_sum = run_sum * expf(run_max - m) + expf(r - m);
-        run_max = m;
-      }
-    }
+    chunk_emit<kJ>(cost, zero, bias, d0, D, live, out_px, HW, &run_max, &run_sum);
   }
   if (raw_only) return;                 // uniform over the workgroup: no barrier is skipped by some waves only
-  s_max[q][lane] = run_max;
-  s_sum[q][lane] = run_sum;
-  __syncthreads();
-  float M = s_max[0][lane];
-  for (int k = 1; k < kWaves; ++k) M = fmaxf(M, s_max[k][lane]);
-  float S = 0.0f;
-  for (int k = 0; k < kWaves; ++k) S += s_sum[k][lane] * expf(s_max[k][lane] - M);
-  const float inv = 1.0f / S;
-  if (!live) return;
-  for (int ch = q; ch < n_chunks; ch += kWaves) {
-    const int d0 = ch * kJ;
-#pragma unroll
-    for (int j = 0; j < kJ; ++j) {
-      if (d0 + j < D) {
-        float* p = out_px + (size_t)(d0 + j) * HW;
-        *p = expf(*p - M) * inv;
-      }
-    }
-  }
+  softmax_finish(s_max, s_sum, q, lane, run_max, run_sum, live, n_chunks, D, out_px, HW);
 }
 
 }  // namespace

@@ -10,6 +10,11 @@ volume (``gen_grid`` + ``calculate_cost_volumn``, :538-596), has two formulation
 * the torch one, ``stereo_cost_volume_torch``: the CPU path, and the GPU path when ``DepthNet.fused_cost_volume`` is
   False.  Its 3x3 inverses are closed-form as in the kernel, so it does not synchronise either.
 
+bfloat16 features (an image encoder under bf16 autocast) are cast to float32 for the kernel by default.  Opt-in
+(``DepthNet.fused_cost_volume_bf16``, ``stereo_cost_volume(..., keep_bf16=True)``) they stay bfloat16: two
+``ocrf_stereo_pack_bf16`` launches put 8 channels of a pixel side by side and ``ocrf_stereo_cost_volume_bf16``
+(csrc/stereo_bf16.hip) gathers them 16 bytes at a time; the float32 volume is bit for bit the default's.
+
 Both run under ``no_grad`` as in the reference (:617): the cost volume has no backward.  ``use_dcn=True`` needs mmcv's
 deformable convolution and is not supported.
 """
@@ -22,10 +27,13 @@ from . import _lib
 from .blocks import BasicBlock, kaiming_init, unfuse_tails
 
 __all__ = ['BasicBlock', 'Mlp', 'SELayer', 'ASPP', '_ASPPModule', 'DepthNet', 'stereo_cost_volume',
-           'stereo_cost_volume_torch', 'stereo_cost_volume_hip', 'stereo_grid_torch', 'supports']
+           'stereo_cost_volume_torch', 'stereo_cost_volume_hip', 'stereo_cost_volume_hip_bf16', 'stereo_pack_bf16',
+           'stereo_pack_bf16_torch', 'stereo_grid_torch', 'supports']
 
 GROUP = 4                   # channels per group of the reference's loop (:580)
 PLANE_BYTES_MAX = 2 ** 32 - 1   # one camera's prev in bytes: the kernel addresses it in unsigned 32-bit
+PACK = 8                    # channels per pixel of a packed bfloat16 block: two groups, 16 bytes
+PACKED_BYTES_MAX = 2 ** 32 - 1  # one camera's packed bfloat16 prev in bytes, addressed likewise
 
 
 # --------------------------------------------------------------------------------------------- building blocks
@@ -203,13 +211,81 @@ def stereo_cost_volume_hip(metas, bias, raw=False):
     return out
 
 
-def stereo_cost_volume(metas, bias, fused=True, raw=False):
+def packed_blocks(C):
+    """Blocks of ``PACK`` channels that hold the C // 4 whole groups of C channels."""
+    return (C // GROUP + 1) // 2
+
+
+def stereo_pack_bf16_torch(x):
+    """(BN, C, H, W) -> (BN, NB, H, W, 8), the layout ``ocrf_stereo_cost_volume_bf16`` reads, by torch ops on any
+    device: ``out[n, b, y, x, k] = x[n, 8 b + k, y, x]`` for the channels of the C // 4 whole groups, +0 in the upper half
+    of the last block when their number is odd; channels past the last whole group are dropped."""
+    BN, C, H, W = x.shape
+    G, NB = C // GROUP, packed_blocks(C)
+    out = x.new_zeros(BN, NB * PACK, H, W)
+    out[:, :GROUP * G] = x[:, :GROUP * G]
+    return out.view(BN, NB, PACK, H, W).permute(0, 1, 3, 4, 2).contiguous()
+
+
+def stereo_pack_bf16(x):
+    """``stereo_pack_bf16_torch`` of a CUDA bfloat16 tensor by ``ocrf_stereo_pack_bf16``: one launch that writes every
+    element of the result."""
+    _lib.require_cuda(x)
+    if x.dtype != torch.bfloat16 or x.dim() != 4:
+        raise ValueError(f'stereo_pack_bf16 takes a (BN, C, H, W) bfloat16 tensor, got {tuple(x.shape)} {x.dtype}')
+    BN, C, H, W = x.shape
+    if C < GROUP or BN < 1 or H < 2 or W < 2:
+        raise ValueError(f'stereo_pack_bf16 needs at least {GROUP} channels and a 2 x 2 map, got {tuple(x.shape)}')
+    NB = packed_blocks(C)
+    if NB * H * W * PACK * 2 > PACKED_BYTES_MAX:
+        raise ValueError(f'stereo_pack_bf16: {NB * H * W * PACK * 2} packed bytes per camera, at most 2^32 - 1 '
+                         '(32-bit block addressing)')
+    x = x.detach().contiguous()
+    out = torch.empty(BN, NB, H, W, PACK, device=x.device, dtype=torch.bfloat16)
+    _lib.launch('ocrf_stereo_pack_bf16', x.device, BN, C, H, W, x, out)
+    return out
+
+
+def stereo_cost_volume_hip_bf16(metas, bias, raw=False):
+    """``stereo_cost_volume_hip`` for bfloat16 features without the cast to float32: two ``ocrf_stereo_pack_bf16``
+    launches and ``ocrf_stereo_cost_volume_bf16``.  The float32 result holds the bits ``stereo_cost_volume_hip`` gives on
+    ``.float()`` of the same features."""
+    prev, curr, D, H, W = _split(metas)
+    BN, C = curr.shape[:2]
+    if C < GROUP or prev.shape[1] != C:
+        raise ValueError(f'stereo features must have the same channel count >= {GROUP}: {prev.shape} vs {curr.shape}')
+    if prev.dtype != torch.bfloat16 or curr.dtype != torch.bfloat16:
+        raise ValueError(f'stereo_cost_volume_hip_bf16 takes bfloat16 features, got {prev.dtype} and {curr.dtype}')
+    packed = packed_blocks(C) * H * W * PACK * 2
+    if packed > PACKED_BYTES_MAX:
+        raise ValueError(f'stereo cost volume: {packed} packed bytes per camera must be at most 2^32 - 1 (32-bit '
+                         'block addressing)')
+    if D * H * W >= 2 ** 31:
+        raise ValueError(f'stereo cost volume: D * H * W = {D * H * W} must be below 2^31')
+    _lib.require_cuda(prev, curr)
+    dev = curr.device
+    prev, curr = stereo_pack_bf16(prev), stereo_pack_bf16(curr)
+    cal = [metas[k].detach().to(dev, torch.float32).reshape(BN, -1).contiguous()
+           for k in ('k2s_sensor', 'intrins', 'post_rots', 'post_trans')]
+    fr = metas['frustum'].detach().to(dev, torch.float32)
+    u, v, d = fr[0, 0, :, 0], fr[0, :, 0, 1], fr[:, 0, 0, 2]
+    out = torch.empty(BN, D, H, W, device=dev)
+    _lib.launch('ocrf_stereo_cost_volume_bf16', dev, BN, C, H, W, D, prev, curr, u, u.stride(0), v, v.stride(0), d,
+                d.stride(0), *cal, float(bias), 1 if raw else 0, out)
+    return out
+
+
+def stereo_cost_volume(metas, bias, fused=True, raw=False, keep_bf16=False):
     """The kernel for CUDA float32 features when ``fused``, else the torch formulation (also on the CPU).  bfloat16
     features (an image encoder under bf16 autocast) take the kernel too, after its cast to float32: the volume is then
-    float32, where the reference computes it in the features' dtype."""
+    float32, where the reference computes it in the features' dtype.  ``keep_bf16``: a CUDA bfloat16 pair skips that
+    cast and takes ``stereo_cost_volume_hip_bf16`` (the same float32 volume, bit for bit); anything else goes where it
+    goes without the flag."""
     prev, curr = metas['cv_feat_list']
     dtypes = (torch.float32, torch.bfloat16)
     if fused and curr.is_cuda and prev.is_cuda and curr.dtype in dtypes and prev.dtype in dtypes:
+        if keep_bf16 and curr.dtype == prev.dtype == torch.bfloat16:
+            return stereo_cost_volume_hip_bf16(metas, bias, raw)
         return stereo_cost_volume_hip(metas, bias, raw)
     return stereo_cost_volume_torch(metas, bias, raw)
 
@@ -223,6 +299,10 @@ def supports(cfg):
 class DepthNet(nn.Module):
     """view_transformer.py:464-626.  ``forward(x, mlp_input, stereo_metas=None)`` returns cat(depth logits
     (depth_channels), context (context_channels)) along channels."""
+
+    # bfloat16 stereo features keep their dtype up to ocrf_stereo_cost_volume_bf16 (two packs + one launch) instead of
+    # being cast to float32 for ocrf_stereo_cost_volume; the volume is the same, bit for bit.  Off by default
+    fused_cost_volume_bf16 = False
 
     def __init__(self, in_channels, mid_channels, context_channels, depth_channels, use_dcn=True, use_aspp=True,
                  with_cp=False, stereo=False, bias=0.0, aspp_mid_channels=-1):
@@ -262,7 +342,8 @@ class DepthNet(nn.Module):
         self.fused_cost_volume = True
 
     def cost_volume(self, stereo_metas):
-        return stereo_cost_volume(stereo_metas, self.bias, fused=self.fused_cost_volume)
+        return stereo_cost_volume(stereo_metas, self.bias, fused=self.fused_cost_volume,
+                                  keep_bf16=self.fused_cost_volume_bf16)
 
     def forward(self, x, mlp_input, stereo_metas=None):
         mlp_input = self.bn(mlp_input.reshape(-1, mlp_input.shape[-1]))
