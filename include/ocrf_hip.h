@@ -842,6 +842,60 @@ int ocrf_upsample_add_backward_bf16(int B, int C, int Hin, int Win, int Hout, in
                                     unsigned short *grad_src, ocrf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Batch norm fused with the ReLU and the residual addition behind it (csrc/bn_act.hip; ocrfdet_amd/norm_ops.py):
+ * out = [relu](bn(x) [+ residual]) over (N, C, H, W) contiguous tensors, forward and backward.  Deterministic: no
+ * atomics, no workgroup waits for another, no host reads; a reduction that spans workgroups is two launches with
+ * `partials` between them.  x, residual, out, grad_out, dx and dresidual are f32, or bf16 (unsigned short) in the _bf16
+ * forms; every per-channel vector, `partials` and all arithmetic are f32, and each result element is rounded once.
+ * 16-byte accesses where a plane's piece allows it (every base pointer 16-byte aligned), single elements at its ragged
+ * head and tail.
+ *
+ * The N * H * W values of a channel are cut into ocrf_bn_chunks(N, C, H, W) chunks of 4096 (a function of the shape
+ * alone; host only, 0 for a shape the kernels refuse).
+ * ocrf_bn_stats: partials (C, chunks, 4) <- (count, mean as anchor and offset, M2) of every chunk, M2 the sum of squared
+ *   deviations from the chunk's mean, combined with the pairwise update (Chan et al.): nothing cancels.
+ * ocrf_bn_finalize: one wave per channel merges the chunks in a fixed order.  from_running == 0: mean, invstd =
+ *   1 / sqrt(M2 / n + eps), scale = weight invstd, shift = bias - mean scale; with running_mean and running_var not
+ *   NULL they are updated, running <- (1 - m) running + m (mean | M2 / (n - 1)), m = momentum, or
+ *   1 / *num_batches_tracked (a device int64, read by the kernel) when momentum < 0.  from_running == 1: mean =
+ *   running_mean, invstd = 1 / sqrt(running_var + eps), scale and shift from those; nothing is updated.
+ * ocrf_bn_act_forward: v = fmaf(x, scale[c], shift[c]); residual not NULL: v = v + residual (one f32 addition);
+ *   relu != 0: v < 0 ? 0 : v (a NaN stays a NaN).
+ * ocrf_bn_act_backward_reduce: partials (C, chunks, 2) <- (sum g, sum g x^) of every chunk, x^ = (x - mean) invstd,
+ *   g = out <= 0 ? 0 : grad_out (torch's threshold_backward), or grad_out with out == NULL (the forward had no ReLU).
+ * ocrf_bn_act_backward: merges the partial sums in a fixed order; dx = weight invstd (g - sum g / n - x^ sum(g x^) / n)
+ *   with batch_stats != 0, weight invstd g with 0; dresidual = g; dweight = sum g x^, dbias = sum g, once per channel.
+ *   dx, dresidual, dweight, dbias may each be NULL and are then not written; partials may be NULL when neither dx with
+ *   batch_stats nor a parameter gradient needs the sums.
+ * Limits: N, C, H, W > 0 and fewer than 2^31 elements; anything else returns hipErrorInvalidValue and launches nothing.
+ */
+int ocrf_bn_chunks(int N, int C, int H, int W);
+int ocrf_bn_stats(int N, int C, int H, int W, const float *x, float *partials, ocrf_stream_t stream);
+int ocrf_bn_finalize(int N, int C, int H, int W, int from_running, const float *partials, const float *weight,
+                     const float *bias, float *running_mean, float *running_var, const long long *num_batches_tracked,
+                     float momentum, float eps, float *mean, float *invstd, float *scale, float *shift,
+                     ocrf_stream_t stream);
+int ocrf_bn_act_forward(int N, int C, int H, int W, const float *x, const float *residual, const float *scale,
+                        const float *shift, int relu, float *out, ocrf_stream_t stream);
+int ocrf_bn_act_backward_reduce(int N, int C, int H, int W, const float *grad_out, const float *x, const float *out,
+                                const float *mean, const float *invstd, float *partials, ocrf_stream_t stream);
+int ocrf_bn_act_backward(int N, int C, int H, int W, const float *grad_out, const float *x, const float *out,
+                         const float *mean, const float *invstd, const float *weight, const float *partials,
+                         int batch_stats, float *dx, float *dresidual, float *dweight, float *dbias,
+                         ocrf_stream_t stream);
+int ocrf_bn_stats_bf16(int N, int C, int H, int W, const unsigned short *x, float *partials, ocrf_stream_t stream);
+int ocrf_bn_act_forward_bf16(int N, int C, int H, int W, const unsigned short *x, const unsigned short *residual,
+                             const float *scale, const float *shift, int relu, unsigned short *out,
+                             ocrf_stream_t stream);
+int ocrf_bn_act_backward_reduce_bf16(int N, int C, int H, int W, const unsigned short *grad_out,
+                                     const unsigned short *x, const unsigned short *out, const float *mean,
+                                     const float *invstd, float *partials, ocrf_stream_t stream);
+int ocrf_bn_act_backward_bf16(int N, int C, int H, int W, const unsigned short *grad_out, const unsigned short *x,
+                              const unsigned short *out, const float *mean, const float *invstd, const float *weight,
+                              const float *partials, int batch_stats, unsigned short *dx, unsigned short *dresidual,
+                              float *dweight, float *dbias, ocrf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Index preparation of the two poolings on the device (csrc/index_prep.hip).
  *
  * ocrf_lss_prepare replaces get_lidar_coor + voxel_pooling_prepare_v2
@@ -1258,7 +1312,16 @@ enum {
   OCRF_K_BEV_ALIGN_BF16 = 119,        /* bev_align_kernel<unsigned short, V> */
   OCRF_K_BEV_ALIGN_BWD_BF16 = 120,    /* bev_align_backward_kernel<unsigned short> */
   OCRF_K_STEREO_PACK_BF16 = 121,      /* stereo_pack_bf16_kernel */
-  OCRF_K_STEREO_COST_VOLUME_BF16 = 122 /* stereo_cost_volume_bf16_kernel */
+  OCRF_K_STEREO_COST_VOLUME_BF16 = 122, /* stereo_cost_volume_bf16_kernel */
+  OCRF_K_BN_STATS = 123,              /* bn_stats_kernel<float, V> */
+  OCRF_K_BN_FINALIZE = 124,           /* bn_finalize_kernel */
+  OCRF_K_BN_ACT_FWD = 125,            /* bn_act_forward_kernel<float, V> */
+  OCRF_K_BN_ACT_BWD_REDUCE = 126,     /* bn_act_backward_reduce_kernel<float, V> */
+  OCRF_K_BN_ACT_BWD = 127,            /* bn_act_backward_kernel<float, V> */
+  OCRF_K_BN_STATS_BF16 = 128,         /* bn_stats_kernel<unsigned short, V> */
+  OCRF_K_BN_ACT_FWD_BF16 = 129,       /* bn_act_forward_kernel<unsigned short, V> */
+  OCRF_K_BN_ACT_BWD_REDUCE_BF16 = 130, /* bn_act_backward_reduce_kernel<unsigned short, V> */
+  OCRF_K_BN_ACT_BWD_BF16 = 131        /* bn_act_backward_kernel<unsigned short, V> */
 };
 const char *ocrf_kernel_name(int kernel_id);           /* symbol as rocprofv3 prints it */
 /* Diagnostic: a one-thread kernel that stores the device's constant-rate clock (wall_clock64, 100 MHz)

@@ -20,6 +20,8 @@ Drop-in mirrors of the reference's Python surface for that path (and nothing els
   build_norm_layer, kaiming_init                  center_head)
   (the encoders' fused passes between             ocrfdet_amd.plane_ops (add_relu, upsample_add, upsample_cat;
   convolutions)                                   re-exported by the encoder modules)
+  nn.BatchNorm2d + ReLU (+ the residual           ocrfdet_amd.norm_ops (bn_act, bn_act_torch, bn_act_fusable; opt-in
+  addition) inside the blocks                     through blocks.fuse_norms)
   BEVDet4D.gen_grid / shift_feature and the       ocrfdet_amd.temporal (feature_transform, shift_feature,
   cat of the aligned frames                       align_and_cat, gen_grid, shift_feature_method, also
                                                   exported here)

@@ -8,12 +8,19 @@ The residual tail ``relu(out + identity)`` of a block is ``plane_ops.add_relu`` 
 contiguous maps while the block's ``fused_tail`` is True, else ``add_relu_torch``.  Under bf16 autocast ``out`` and
 ``identity`` are both bfloat16 and take the op's bf16 kernels while ``fused_tail_bf16`` is True as well; a mixed pair
 stays on torch, which promotes.  ``with_cp=True`` checkpoints the whole block (tail included) in the non-reentrant form.
+
+``fused_norm`` (off by default; ``fuse_norms`` sets it) moves the batch norms into ``norm_ops.bn_act`` as well: with it
+on, ``relu(bn(conv(x)))`` is one op, the last norm takes the residual tail with it (``relu(bn(x) + identity)``), and a
+``ConvModule`` runs its norm with its ReLU, or alone when it has no activation, wherever ``bn_act_fusable`` accepts
+the operands.  Everything else (the flag off, the CPU, other dtypes, ``SyncBN``, another activation, a residual of
+another dtype) runs the expressions it runs with the flag off.
 """
 import torch
 from torch import nn
 from torch.nn.modules.batchnorm import _BatchNorm
 from torch.utils.checkpoint import checkpoint
 
+from .norm_ops import bn_act, bn_act_fusable
 from .plane_ops import FUSED_TAIL_BF16_DEFAULT, FUSED_TAIL_DEFAULT, add_relu, add_relu_fusable, add_relu_torch
 
 
@@ -60,7 +67,20 @@ class _Block(nn.Module):
     """What the two mmdet 2.x blocks share: the ``norm{i}`` properties, checkpointing and the residual tail."""
     fused_tail = FUSED_TAIL_DEFAULT
     fused_tail_bf16 = FUSED_TAIL_BF16_DEFAULT      # bfloat16 operands take the op too (only while fused_tail is on)
+    fused_norm = False                             # the norms run norm_ops.bn_act where it takes them (fuse_norms)
     with_cp = False
+
+    def _norm_relu(self, bn, x):
+        """``relu(bn(x))`` of the fused forward."""
+        if bn_act_fusable(bn, x):
+            return bn_act(bn, x)
+        return self.relu(bn(x))
+
+    def _norm_tail(self, bn, x, identity):
+        """``relu(bn(x) + identity)`` of the fused forward."""
+        if bn_act_fusable(bn, x, identity):
+            return bn_act(bn, x, residual=identity)
+        return self._tail(bn(x), identity)
 
     def _tail(self, out, identity):
         if (self.fused_tail and (self.fused_tail_bf16 or out.dtype != torch.bfloat16)
@@ -101,10 +121,17 @@ class BasicBlock(_Block):
         return self.bn2
 
     def _forward(self, x):
+        if self.fused_norm:
+            return self._forward_fused_norm(x)
         identity = x if self.downsample is None else self.downsample(x)
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.bn2(self.conv2(out))
         return self._tail(out, identity)
+
+    def _forward_fused_norm(self, x):
+        identity = x if self.downsample is None else self.downsample(x)
+        out = self._norm_relu(self.bn1, self.conv1(x))
+        return self._norm_tail(self.bn2, self.conv2(out), identity)
 
 
 class Bottleneck(_Block):
@@ -136,11 +163,19 @@ class Bottleneck(_Block):
         return self.bn3
 
     def _forward(self, x):
+        if self.fused_norm:
+            return self._forward_fused_norm(x)
         identity = x if self.downsample is None else self.downsample(x)
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.relu(self.bn2(self.conv2(out)))
         out = self.bn3(self.conv3(out))
         return self._tail(out, identity)
+
+    def _forward_fused_norm(self, x):
+        identity = x if self.downsample is None else self.downsample(x)
+        out = self._norm_relu(self.bn1, self.conv1(x))
+        out = self._norm_relu(self.bn2, self.conv2(out))
+        return self._norm_tail(self.bn3, self.conv3(out), identity)
 
 
 def fuse_bf16_tails(module, flag=True):
@@ -148,6 +183,13 @@ def fuse_bf16_tails(module, flag=True):
     for m in module.modules():
         if isinstance(m, _Block):
             m.fused_tail_bf16 = bool(flag)
+
+
+def fuse_norms(module, flag=True):
+    """Set ``fused_norm`` on every block and every ``ConvModule`` inside ``module``."""
+    for m in module.modules():
+        if isinstance(m, (_Block, ConvModule)):
+            m.fused_norm = bool(flag)
 
 
 def unfuse_tails(module):
@@ -164,6 +206,7 @@ _ACTIVATIONS = dict(ReLU=nn.ReLU, LeakyReLU=nn.LeakyReLU, Sigmoid=nn.Sigmoid, Ta
 class ConvModule(nn.Module):
     """mmcv ``ConvModule`` in its default order conv -> norm -> act: with ``bias='auto'``, ``conv`` has a bias exactly
     when there is no norm; the norm is ``bn``, the activation ``activate``."""
+    fused_norm = False                             # as _Block.fused_norm: the norm and a ReLU behind it run bn_act
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias='auto', conv_cfg=None,
                  norm_cfg=None, act_cfg=None, inplace=True):
@@ -186,6 +229,9 @@ class ConvModule(nn.Module):
 
     def forward(self, x):
         x = self.conv(x)
+        if (self.fused_norm and self.with_norm and (not self.with_activation or type(self.activate) is nn.ReLU)
+                and bn_act_fusable(self.bn, x)):
+            return bn_act(self.bn, x, relu=self.with_activation)
         if self.with_norm:
             x = self.bn(x)
         if self.with_activation:

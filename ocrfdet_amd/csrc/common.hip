@@ -171,6 +171,15 @@ const char* ocrf_kernel_name(int kernel_id) {
     case OCRF_K_BEV_ALIGN_BWD_BF16: return "bev_align_backward_kernel<unsigned short>";
     case OCRF_K_STEREO_PACK_BF16: return "stereo_pack_bf16_kernel";
     case OCRF_K_STEREO_COST_VOLUME_BF16: return "stereo_cost_volume_bf16_kernel";
+    case OCRF_K_BN_STATS: return "bn_stats_kernel<float, *>";
+    case OCRF_K_BN_FINALIZE: return "bn_finalize_kernel";
+    case OCRF_K_BN_ACT_FWD: return "bn_act_forward_kernel<float, *>";
+    case OCRF_K_BN_ACT_BWD_REDUCE: return "bn_act_backward_reduce_kernel<float, *>";
+    case OCRF_K_BN_ACT_BWD: return "bn_act_backward_kernel<float, *>";
+    case OCRF_K_BN_STATS_BF16: return "bn_stats_kernel<unsigned short, *>";
+    case OCRF_K_BN_ACT_FWD_BF16: return "bn_act_forward_kernel<unsigned short, *>";
+    case OCRF_K_BN_ACT_BWD_REDUCE_BF16: return "bn_act_backward_reduce_kernel<unsigned short, *>";
+    case OCRF_K_BN_ACT_BWD_BF16: return "bn_act_backward_kernel<unsigned short, *>";
     default: return "";
   }
 }
