@@ -721,6 +721,29 @@ int ocrf_bev_align_backward_bf16(int n, int c, int h, int w, const unsigned shor
                                  ocrf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Frame poses of the 4D detectors (csrc/frame_poses.hip): the pose algebra of BEVDet4D.prepare_inputs
+ * (mmdet3d/models/detectors/bevdet.py:435-456) and the per-frame get_mlp_input of extract_img_feat (ocrfdet.py:229-231)
+ * in ONE launch, one thread per (sample, frame, camera).  Deterministic, no atomics, no workspace, no host reads.
+ *
+ * Inputs, f32 contiguous: sensor2egos, ego2globals (B, F, N, 4, 4) affine (last row (0, 0, 0, 1), not checked); rots,
+ * intrins, post_rots (B, F, N, 3, 3); trans, post_trans (B, F, N, 3); bda (B, 3, 3).  0 <= T < F (temporal_frame).
+ * Outputs, f32 contiguous, every element written:
+ *   sensor2keyegos (B, F, N, 4, 4) = inv(ego2globals[b][0][0]) . ego2globals[b][f][n] . sensor2egos[b][f][n]
+ *   curr2adjsensor (B, T, N, 4, 4) = inv(ego2globals[b][f+1][n] . sensor2egos[b][f+1][n]) . ego2globals[b][f][n] .
+ *                                    sensor2egos[b][f][n]; may be NULL when T = 0
+ *   mlp_input (F, B, N, 27): per frame f what get_mlp_input(rots[:, 0], trans[:, 0], intrins[:, f], post_rots[:, f],
+ *                            post_trans[:, f], bda) returns (view_transformer.py:696-722); copies, bit-equal
+ * The products and inverses are evaluated in f64 and each result is rounded once to f32.  An inverse is the closed form
+ * of an affine map: the 3 x 3 block as adjugate / determinant, the translation -inv(R) t; no orthonormality is assumed,
+ * a singular block gives inf / nan.  Limits: B, F, N > 0 and B * F * N < 2^24; anything else returns
+ * hipErrorInvalidValue and launches nothing.
+ */
+int ocrf_frame_poses(int B, int F, int N, int T, const float *sensor2egos, const float *ego2globals, const float *rots,
+                     const float *trans, const float *intrins, const float *post_rots, const float *post_trans,
+                     const float *bda, float *sensor2keyegos, float *curr2adjsensor, float *mlp_input,
+                     ocrf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * The tail of a training iteration (csrc/optim.hip): clip_grad_norm_(max_norm, norm_type=2), torch.optim.AdamW and the
  * weight EMA of mmdet3d/core/hook/ema.py:48-60 (v *= d; v += (1 - d) * msd[k]) over ALL tensors of a model in three
  * launches, whatever their count (configs/ocrfdet/ocrfdet.py:259-274, 329-330).  f32, contiguous tensors.
@@ -1321,7 +1344,8 @@ enum {
   OCRF_K_BN_STATS_BF16 = 128,         /* bn_stats_kernel<unsigned short, V> */
   OCRF_K_BN_ACT_FWD_BF16 = 129,       /* bn_act_forward_kernel<unsigned short, V> */
   OCRF_K_BN_ACT_BWD_REDUCE_BF16 = 130, /* bn_act_backward_reduce_kernel<unsigned short, V> */
-  OCRF_K_BN_ACT_BWD_BF16 = 131        /* bn_act_backward_kernel<unsigned short, V> */
+  OCRF_K_BN_ACT_BWD_BF16 = 131,       /* bn_act_backward_kernel<unsigned short, V> */
+  OCRF_K_FRAME_POSES = 132            /* frame_poses_kernel */
 };
 const char *ocrf_kernel_name(int kernel_id);           /* symbol as rocprofv3 prints it */
 /* Diagnostic: a one-thread kernel that stores the device's constant-rate clock (wall_clock64, 100 MHz)

@@ -28,6 +28,8 @@ Drop-in mirrors of the reference's Python surface for that path (and nothing els
   torch.optim.AdamW + clip_grad_norm_ (mmcv's     ocrfdet_amd.optim (FusedAdamW, ModelEMA, paramwise_groups, also
   grad_clip), ...core.hook.ema.ModelEMA, mmcv's   exported here)
   DefaultOptimizerConstructor custom_keys
+  ...detectors.ocrfdet.OcRFDet4D and              ocrfdet_amd.detector (OcRFDet4D, prepare_inputs, frame_poses,
+  BEVDet4D.prepare_inputs                         frame_poses_torch, also exported here)
   ==============================================  =================================================
 
 Every op calls the C ABI of ``csrc/libocrf_hip.so`` (``include/ocrf_hip.h``) through ctypes with
@@ -40,6 +42,7 @@ _LAZY = ('ResNet', 'CustomFPN', 'ImageEncoder')
 _LAZY_TEMPORAL = ('feature_transform', 'shift_feature', 'shift_feature_torch', 'align_and_cat', 'gen_grid',
                   'shift_feature_method')
 _LAZY_OPTIM = ('FusedAdamW', 'ModelEMA', 'paramwise_groups')
+_LAZY_DETECTOR = ('OcRFDet4D', 'prepare_inputs', 'frame_poses', 'frame_poses_torch')
 
 
 def __getattr__(name):
@@ -55,4 +58,7 @@ def __getattr__(name):
     if name in _LAZY_OPTIM:
         from . import optim
         return getattr(optim, name)
+    if name in _LAZY_DETECTOR:
+        from . import detector
+        return getattr(detector, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -180,6 +180,7 @@ const char* ocrf_kernel_name(int kernel_id) {
     case OCRF_K_BN_ACT_FWD_BF16: return "bn_act_forward_kernel<unsigned short, *>";
     case OCRF_K_BN_ACT_BWD_REDUCE_BF16: return "bn_act_backward_reduce_kernel<unsigned short, *>";
     case OCRF_K_BN_ACT_BWD_BF16: return "bn_act_backward_kernel<unsigned short, *>";
+    case OCRF_K_FRAME_POSES: return "frame_poses_kernel";
     default: return "";
   }
 }

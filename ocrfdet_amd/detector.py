@@ -1,0 +1,384 @@
+"""The detector: ``OcRFDet4D`` (mmdet3d/models/detectors/ocrfdet.py:141-386), a ``BEVStereo4D`` / ``BEVDet4D``
+(bevdet.py:274-723), over this package's native modules, without mmcv, mmdet or mmdet3d.
+
+* ``frame_poses_torch`` / ``frame_poses``: the pose algebra of ``BEVDet4D.prepare_inputs`` (bevdet.py:435-456) and the
+  per-frame ``get_mlp_input`` of ``extract_img_feat`` (ocrfdet.py:229-231).  The reference runs two ``torch.inverse``
+  calls on float64 4 x 4 stacks (a host synchronisation each) and one ``get_mlp_input`` per frame.  Here the same
+  products are evaluated in float64 with the inverses in closed form (affine maps: adjugate / determinant of the 3 x 3
+  block, as ``temporal._inverse3``), without a host read; on CUDA float32 inputs as ONE launch
+  (``ocrf_frame_poses``, ``csrc/frame_poses.hip``).
+* ``prepare_inputs``: ``BEVDet4D.prepare_inputs`` (bevdet.py:412-476) as a function: the 12-entry ``img_inputs`` split
+  into per-frame lists.
+* ``OcRFDet4D``: the class.  Constructor keys, attribute names and ``state_dict`` keys are the reference's.
+
+**Precondition:** ``sensor2egos`` and ``ego2globals`` have the last row (0, 0, 0, 1), as the dataset's always have.  It
+is not checked: a check would synchronise.  Nothing assumes an orthonormal rotation; a singular matrix gives inf / nan.
+
+Out of scope: mmcv's ``Config`` and registries, ``DataContainer`` unwrapping, ``train_step``, the dataset pipeline,
+``grid_mask``, ``extract_img_feat_sequential`` and ``pred_prev`` (both raise ``NotImplementedError``).
+"""
+import torch
+from torch import nn
+
+from . import _lib, temporal
+from .blocks import build
+
+LOSS_KEYS_NECK = ('loss_depth', 'loss_ce_semantic', 'loss_gs_color', 'loss_gs_ssim', 'loss_render_depth')
+
+
+# ------------------------------------------------------------------------------------------------ frame poses
+def _affine_inverse(m):
+    """Inverse of (..., 4, 4) float64 affine maps [R t; 0 0 0 1] in closed form: inv(R) from the adjugate, -inv(R) t."""
+    lead = m.shape[:-2]
+    rinv = temporal._inverse3(m[..., :3, :3].reshape(-1, 3, 3)).view(*lead, 3, 3)
+    t = -(rinv * m[..., None, :3, 3]).sum(-1)
+    top = torch.cat([rinv, t[..., None]], -1)
+    last = torch.zeros_like(m[..., 3:, :])
+    last[..., 0, 3] = 1.0
+    return torch.cat([top, last], -2)
+
+
+def mlp_input_torch(rots, trans, intrins, post_rots, post_trans, bda):
+    """(F, B, N, 27): for every frame f what ``get_mlp_input(rots[:, 0], trans[:, 0], intrins[:, f], post_rots[:, f],
+    post_trans[:, f], bda)`` returns (view_transformer.py:696-722), from (B, F, N, ...) inputs.  Copies only."""
+    B, F, N = rots.shape[:3]
+    a = bda.view(B, 1, 1, 3, 3).expand(B, F, N, 3, 3)
+    v = torch.stack([intrins[..., 0, 0], intrins[..., 1, 1], intrins[..., 0, 2], intrins[..., 1, 2],
+                     post_rots[..., 0, 0], post_rots[..., 0, 1], post_trans[..., 0], post_rots[..., 1, 0],
+                     post_rots[..., 1, 1], post_trans[..., 1], a[..., 0, 0], a[..., 0, 1], a[..., 1, 0], a[..., 1, 1],
+                     a[..., 2, 2]], dim=-1)
+    s2e = torch.cat([rots[:, 0], trans[:, 0].reshape(B, N, 3, 1)], dim=-1).reshape(B, 1, N, 12).expand(B, F, N, 12)
+    return torch.cat([v, s2e], dim=-1).permute(1, 0, 2, 3).contiguous()
+
+
+def _check_pose_shapes(sensor2egos, ego2globals, rots, trans, intrins, post_rots, post_trans, bda, temporal_frame):
+    if sensor2egos.dim() != 5 or sensor2egos.shape[-2:] != (4, 4):
+        raise ValueError(f'sensor2egos must be (B, F, N, 4, 4), got {tuple(sensor2egos.shape)}')
+    B, F, N = sensor2egos.shape[:3]
+    want = dict(ego2globals=(B, F, N, 4, 4), rots=(B, F, N, 3, 3), trans=(B, F, N, 3), intrins=(B, F, N, 3, 3),
+                post_rots=(B, F, N, 3, 3), post_trans=(B, F, N, 3), bda=(B, 3, 3))
+    got = dict(ego2globals=ego2globals, rots=rots, trans=trans, intrins=intrins, post_rots=post_rots,
+               post_trans=post_trans, bda=bda)
+    for name, shape in want.items():
+        if tuple(got[name].shape) != shape:
+            raise ValueError(f'{name} must be {shape}, got {tuple(got[name].shape)}')
+    if not 0 <= int(temporal_frame) < F:
+        raise ValueError(f'temporal_frame must be in [0, {F}), got {temporal_frame}')
+    return B, F, N
+
+
+def frame_poses_torch(sensor2egos, ego2globals, rots, trans, intrins, post_rots, post_trans, bda, temporal_frame):
+    """The frame poses in torch, on any device, for any floating dtype; differentiable, no ``torch.inverse``, no host
+    read.  Inputs (B, F, N, ...) as ``include/ocrf_hip.h`` lists them; ``T = temporal_frame``.  Returns
+
+    * ``sensor2keyegos`` (B, F, N, 4, 4) = inv(ego2globals[:, 0, 0]) . ego2globals . sensor2egos,
+    * ``curr2adjsensor`` (B, T, N, 4, 4) = inv(ego2globals[:, 1:T+1] . sensor2egos[:, 1:T+1]) . ego2globals[:, :T] .
+      sensor2egos[:, :T], or None when T = 0,
+    * ``mlp_input`` (F, B, N, 27) (``mlp_input_torch``),
+
+    the products evaluated in float64 and rounded once to the dtype of ``sensor2egos``."""
+    T = int(temporal_frame)
+    _check_pose_shapes(sensor2egos, ego2globals, rots, trans, intrins, post_rots, post_trans, bda, T)
+    dtype = sensor2egos.dtype
+    e2g, s2e = ego2globals.double(), sensor2egos.double()
+    sensor2global = e2g @ s2e
+    global2keyego = _affine_inverse(e2g[:, 0, 0])[:, None, None]
+    sensor2keyegos = (global2keyego @ sensor2global).to(dtype)
+    curr2adjsensor = None
+    if T > 0:
+        curr2adjsensor = (_affine_inverse(sensor2global[:, 1:T + 1]) @ sensor2global[:, :T]).to(dtype)
+    return sensor2keyegos, curr2adjsensor, mlp_input_torch(rots, trans, intrins, post_rots, post_trans, bda)
+
+
+def frame_poses_fusable(*tensors):
+    """The kernel takes these: CUDA float32 tensors on one device, none of which records a gradient."""
+    dev = tensors[0].device
+    return all(t.is_cuda and t.dtype == torch.float32 and t.device == dev
+               and not (t.requires_grad and torch.is_grad_enabled()) for t in tensors)
+
+
+def frame_poses(sensor2egos, ego2globals, rots, trans, intrins, post_rots, post_trans, bda, temporal_frame, fused=True):
+    """``frame_poses_torch`` with a dispatch: CUDA float32 inputs with ``fused=True`` take ``ocrf_frame_poses``, one
+    launch without a host read (the outputs get no gradient); everything else, the CPU included, the torch formulation.
+    The two agree within one float32 ulp in the poses (both round a float64 result once) and bit for bit in
+    ``mlp_input``."""
+    tensors = (sensor2egos, ego2globals, rots, trans, intrins, post_rots, post_trans, bda)
+    if not (fused and frame_poses_fusable(*tensors)):
+        return frame_poses_torch(*tensors, temporal_frame)
+    T = int(temporal_frame)
+    B, F, N = _check_pose_shapes(*tensors, T)
+    tensors = [t.detach().contiguous() for t in tensors]
+    dev = sensor2egos.device
+    sensor2keyegos = torch.empty(B, F, N, 4, 4, dtype=torch.float32, device=dev)
+    curr2adjsensor = torch.empty(B, T, N, 4, 4, dtype=torch.float32, device=dev) if T > 0 else None
+    mlp_input = torch.empty(F, B, N, 27, dtype=torch.float32, device=dev)
+    _lib.launch('ocrf_frame_poses', dev, B, F, N, T, *tensors, sensor2keyegos, curr2adjsensor, mlp_input)
+    return sensor2keyegos, curr2adjsensor, mlp_input
+
+
+# ------------------------------------------------------------------------------------------------ prepare_inputs
+def _frames(t):
+    return list(t.unbind(1))
+
+
+def prepare_inputs(inputs, num_frame, temporal_frame, extra_ref_frames, stereo=True, fused=True):
+    """``BEVDet4D.prepare_inputs`` (bevdet.py:412-476) for the 12-entry ``img_inputs`` = (imgs (B, N * num_frame, C, H,
+    W), rots, trans, intrins, post_rots, post_trans, bda, sensor2egos, ego2globals, imgs_wo_norm, imgs_wo_aug, c2w).
+    Returns a pair:
+
+    * the reference's 13-tuple ``(imgs, rots, trans, intrins, post_rots, post_trans, bda, sensor2keyegos, ego2globals,
+      curr2adjsensor, imgs_wo_norm, imgs_wo_aug, c2w)``: every entry but ``bda`` a list over the frames;
+      ``curr2adjsensor`` holds ``temporal_frame`` poses and ``extra_ref_frames`` times ``None`` (``stereo=True``), or is
+      ``None`` (``stereo=False``);
+    * the list over the frames of ``mlp_input`` (B, N, 27), what ``extract_img_feat`` gets from ``get_mlp_input``.
+
+    The poses come from ``frame_poses(..., fused=fused)``."""
+    if len(inputs) != 12:
+        raise ValueError(f'img_inputs has 12 entries, got {len(inputs)}')
+    B, N, C, H, W = inputs[0].shape
+    if N % num_frame:
+        raise ValueError(f'{N} images are not {num_frame} frames of the same cameras')
+    N = N // num_frame
+    imgs = _frames(inputs[0].view(B, N, num_frame, C, H, W).transpose(1, 2))
+    rots, trans, intrins, post_rots, post_trans, bda, sensor2egos, ego2globals = inputs[1:9]
+    imgs_wo_norm = _frames(inputs[9].view(B, N, num_frame, 3, H, W).transpose(1, 2))
+    imgs_wo_aug = _frames(inputs[10].view(B, N, num_frame, 3, H, W).transpose(1, 2))
+    sensor2egos = sensor2egos.view(B, num_frame, N, 4, 4)
+    ego2globals = ego2globals.view(B, num_frame, N, 4, 4)
+    rots, intrins, post_rots = (t.view(B, num_frame, N, 3, 3) for t in (rots, intrins, post_rots))
+    trans, post_trans = (t.view(B, num_frame, N, 3) for t in (trans, post_trans))
+    c2w = inputs[11].view(B, num_frame, N, 4, 4)
+    T = temporal_frame if stereo else 0
+    sensor2keyegos, curr2adj, mlp_input = frame_poses(sensor2egos, ego2globals, rots, trans, intrins, post_rots,
+                                                      post_trans, bda, T, fused=fused)
+    curr2adjsensor = None
+    if stereo:
+        curr2adjsensor = _frames(curr2adj) + [None] * extra_ref_frames
+        assert len(curr2adjsensor) == num_frame
+    out = (imgs, _frames(rots), _frames(trans), _frames(intrins), _frames(post_rots), _frames(post_trans), bda,
+           _frames(sensor2keyegos), _frames(ego2globals), curr2adjsensor, imgs_wo_norm, imgs_wo_aug, _frames(c2w))
+    return out, list(mlp_input.unbind(0))
+
+
+# ------------------------------------------------------------------------------------------------ the detector
+def _build(cfg, kind, factory):
+    """A sub-module from its config dict, or the module itself when it is already built."""
+    if cfg is None or isinstance(cfg, nn.Module):
+        return cfg
+    return build(cfg, kind, factory)
+
+
+def _pts(cfg):
+    """``train_cfg.pts`` / ``test_cfg.pts`` of a config (a dict, or anything with a ``pts`` attribute)."""
+    if cfg is None:
+        return None
+    return cfg.get('pts') if isinstance(cfg, dict) else getattr(cfg, 'pts', None)
+
+
+class OcRFDet4D(nn.Module):
+    """``OcRFDet4D`` of the reference config (configs/ocrfdet/ocrfdet.py:44-154): ResNet + CustomFPN, the stereo
+    ``OcRFViewTransformerFull``, ``pre_process``, the BEV encoder and ``CenterHead``, with the reference's constructor
+    keys, attribute names (``img_backbone``, ``img_neck``, ``img_view_transformer``, ``img_bev_encoder_backbone``,
+    ``img_bev_encoder_neck``, ``pre_process_net``, ``pts_bbox_head``) and therefore ``state_dict`` keys.
+
+    Every sub-module is built from its config dict by this package's class of the dict's ``type``, or taken as it is
+    when an ``nn.Module`` is passed.  ``train_cfg.pts`` and ``test_cfg.pts`` are merged into the head's dict, as the
+    reference's ``MVXTwoStageDetector`` does.
+
+    ``fused_poses`` (class attribute, default True): the frame poses and ``mlp_input`` of a forward come from one HIP
+    launch when ``img_inputs`` is on the GPU; False takes ``frame_poses_torch``.  ``fused_align`` (default
+    ``temporal.FUSED_ALIGN_DEFAULT``) is ``align_and_cat``'s flag."""
+
+    fused_poses = True
+    fused_align = None
+    autocast_bf16 = False            # BEVEncoder's opt-in; False is the reference's @force_fp32
+
+    def __init__(self, img_view_transformer, img_backbone=None, img_neck=None, img_bev_encoder_backbone=None,
+                 img_bev_encoder_neck=None, pre_process=None, pts_bbox_head=None, num_adj=1,
+                 align_after_view_transfromation=False, with_prev=True, train_cfg=None, test_cfg=None,
+                 use_grid_mask=False, pretrained=None, init_cfg=None, type=None):
+        super().__init__()
+        if type not in (None, 'OcRFDet4D'):
+            raise NotImplementedError(f'type {type}: only OcRFDet4D')
+        if use_grid_mask:
+            raise NotImplementedError('use_grid_mask: GridMask is not part of this package')
+        from .bev_encoder import CustomResNet, FPN_LSS
+        from .center_head import CenterHead
+        from .image_encoder import CustomFPN, ResNet
+        from .view_transformer_ocrf import OcRFViewTransformerFull
+        self.train_cfg, self.test_cfg = train_cfg, test_cfg
+        self.img_backbone = _build(img_backbone, 'ResNet', ResNet)
+        if img_neck is not None:
+            self.img_neck = _build(img_neck, 'CustomFPN', CustomFPN)
+        self.img_view_transformer = _build(img_view_transformer, 'OcRFViewTransformerFull', OcRFViewTransformerFull)
+        if img_bev_encoder_neck is not None and img_bev_encoder_backbone is not None:
+            self.img_bev_encoder_backbone = _build(img_bev_encoder_backbone, 'CustomResNet', CustomResNet)
+            self.img_bev_encoder_neck = _build(img_bev_encoder_neck, 'FPN_LSS', FPN_LSS)
+        self.pre_process = pre_process is not None
+        if self.pre_process:
+            self.pre_process_net = _build(pre_process, 'CustomResNet', CustomResNet)
+        if pts_bbox_head is not None:
+            if isinstance(pts_bbox_head, dict):
+                pts_bbox_head = dict(pts_bbox_head, train_cfg=_pts(train_cfg), test_cfg=_pts(test_cfg))
+            self.pts_bbox_head = _build(pts_bbox_head, 'CenterHead', CenterHead)
+        self.align_after_view_transfromation = align_after_view_transfromation
+        self.with_prev = with_prev
+        # BEVDet4D.__init__ (bevdet.py:300) and BEVStereo4D.__init__ (:596-598)
+        self.num_frame = num_adj + 1
+        self.extra_ref_frames = 1
+        self.temporal_frame = self.num_frame
+        self.num_frame += self.extra_ref_frames
+
+    @property
+    def with_img_neck(self):
+        return getattr(self, 'img_neck', None) is not None
+
+    @property
+    def with_pts_bbox(self):
+        return getattr(self, 'pts_bbox_head', None) is not None
+
+    # ---------------------------------------------------------------- the stages: this package's native formulations
+    def image_encoder(self, img, stereo=False):
+        """``BEVDet.image_encoder`` (bevdet.py:44-64, no ``grid_mask``): ``ImageEncoder.image_encoder`` over this
+        module's ``img_backbone`` / ``img_neck``."""
+        from .image_encoder import ImageEncoder
+        return ImageEncoder.image_encoder(self, img, stereo=stereo)
+
+    def extract_stereo_ref_feat(self, x):
+        """``BEVStereo4D.extract_stereo_ref_feat`` (bevdet.py:600-614) for a ResNet: the stem and ``layer1``."""
+        from .image_encoder import ImageEncoder
+        return ImageEncoder.extract_stereo_ref_feat(self, x)
+
+    def bev_encoder(self, x):
+        """``BEVDet.bev_encoder`` (bevdet.py:66-72): ``BEVEncoder.forward`` over this module's two attributes."""
+        from .bev_encoder import BEVEncoder
+        return BEVEncoder.forward(self, x)
+
+    def prepare_inputs(self, inputs, stereo=False):
+        return prepare_inputs(inputs, self.num_frame, self.temporal_frame, self.extra_ref_frames, stereo=stereo,
+                              fused=self.fused_poses)
+
+    # ---------------------------------------------------------------- ocrfdet.py:144-173
+    def prepare_bev_feat(self, img, rot, tran, sensor2keyego, ego2global, intrin, post_rot, post_tran, bda, mlp_input,
+                         feat_prev_iv, k2s_sensor, extra_ref_frame, imgs_wo_norm, imgs_wo_aug, c2w):
+        if extra_ref_frame:
+            return None, None, None, self.extract_stereo_ref_feat(img), None
+        x, stereo_feat = self.image_encoder(img, stereo=True)
+        vt = self.img_view_transformer
+        metas = dict(k2s_sensor=k2s_sensor, intrins=intrin, post_rots=post_rot, post_trans=post_tran,
+                     frustum=vt.cv_frustum.to(x), cv_downsample=4, downsample=vt.downsample,
+                     grid_config=vt.grid_config, cv_feat_list=[feat_prev_iv, stereo_feat])
+        bev_feat, depth, bev_mask, extras = vt(
+            [x, rot, tran, intrin, post_rot, post_tran, bda, mlp_input, img, imgs_wo_norm, imgs_wo_aug, c2w], metas)
+        if self.pre_process:
+            bev_feat = self.pre_process_net(bev_feat)[0]
+        return bev_feat, depth, bev_mask, stereo_feat, extras
+
+    def extract_img_feat_sequential(self, inputs, feat_prev):
+        raise NotImplementedError('extract_img_feat_sequential: the streaming test is not part of this package')
+
+    # ---------------------------------------------------------------- ocrfdet.py:206-279
+    def extract_img_feat(self, img, img_metas=None, pred_prev=False, sequential=False, **kwargs):
+        """Frames ``num_frame - 1 ... 0``: the extra reference frame yields only the stereo feature, adjacent frames run
+        under ``no_grad``, the key frame with gradients; the BEV features are concatenated oldest first, key frame last.
+        Returns ``([x], depth, bev_mask, extras)`` in training and ``([x], depth, bev_mask)`` otherwise."""
+        if sequential:
+            return self.extract_img_feat_sequential(img, **kwargs)
+        if pred_prev:
+            raise NotImplementedError('pred_prev: the reference asserts False here')
+        (imgs, rots, trans, intrins, post_rots, post_trans, bda, sensor2keyegos, ego2globals, curr2adjsensor,
+         imgs_wo_norm, imgs_wo_aug, c2ws), mlp_inputs = self.prepare_inputs(img, stereo=True)
+        bev_feat_list = []
+        depth_key_frame = bev_mask_key_frame = extras = None
+        feat_prev_iv = None
+        for fid in range(self.num_frame - 1, -1, -1):
+            key_frame = fid == 0
+            extra_ref_frame = fid == self.num_frame - self.extra_ref_frames
+            if not (key_frame or self.with_prev):
+                continue
+            sensor2keyego, ego2global = sensor2keyegos[fid], ego2globals[fid]
+            if self.align_after_view_transfromation:
+                sensor2keyego, ego2global = sensor2keyegos[0], ego2globals[0]
+            inputs_curr = (imgs[fid], rots[fid], trans[fid], sensor2keyego, ego2global, intrins[fid], post_rots[fid],
+                           post_trans[fid], bda, mlp_inputs[fid], feat_prev_iv, curr2adjsensor[fid], extra_ref_frame,
+                           imgs_wo_norm[fid], imgs_wo_aug[fid], c2ws[fid])
+            if key_frame:
+                bev_feat, depth_key_frame, bev_mask_key_frame, feat_curr_iv, extras = self.prepare_bev_feat(*inputs_curr)
+            else:
+                with torch.no_grad():
+                    bev_feat, _, _, feat_curr_iv, _ = self.prepare_bev_feat(*inputs_curr)
+            if not extra_ref_frame:
+                bev_feat_list.append(bev_feat)
+            feat_prev_iv = feat_curr_iv
+        n_adj = self.num_frame - self.extra_ref_frames - 1
+        if not self.with_prev:
+            key = bev_feat_list[0]
+            zeros = key.new_zeros((key.shape[0], key.shape[1] * n_adj) + tuple(key.shape[2:]))
+            bev_feat = torch.cat([zeros, key], dim=1)            # a warp of zeros is zeros: nothing to align
+        elif self.align_after_view_transfromation:
+            vt = self.img_view_transformer
+            frame_ids = [self.num_frame - 2 - k for k in range(self.num_frame - 2)] + [0]
+            bev_feat = temporal.align_and_cat(bev_feat_list, frame_ids, sensor2keyegos, bda, vt.grid_interval,
+                                              vt.grid_lower_bound, fused=self.fused_align)
+        else:
+            bev_feat = torch.cat(bev_feat_list, dim=1)
+        x = self.bev_encoder(bev_feat)
+        if self.training:
+            return [x], depth_key_frame, bev_mask_key_frame, extras
+        return [x], depth_key_frame, bev_mask_key_frame
+
+    def extract_feat(self, points, img, img_metas=None, **kwargs):
+        """ocrfdet.py:34-46: ``(img_feats, pts_feats = None, depth, bev_mask[, extras])``."""
+        out = self.extract_img_feat(img, img_metas, **kwargs)
+        return (out[0], None) + tuple(out[1:])
+
+    def forward_pts_train(self, pts_feats, gt_bboxes_3d, gt_labels_3d, img_metas=None, gt_bboxes_ignore=None):
+        """``CenterPoint`` / ``MVXTwoStageDetector.forward_pts_train``: the head, then its loss."""
+        outs = self.pts_bbox_head(pts_feats)
+        return self.pts_bbox_head.loss(gt_bboxes_3d, gt_labels_3d, outs)
+
+    # ---------------------------------------------------------------- ocrfdet.py:331-386
+    def forward_train(self, points=None, img_metas=None, gt_bboxes_3d=None, gt_labels_3d=None, gt_labels=None,
+                      gt_bboxes=None, img_inputs=None, proposals=None, gt_bboxes_ignore=None, **kwargs):
+        gt_depth, gt_semantic, gt_bev_mask = kwargs.pop('gt_depth'), kwargs.pop('gt_semantic'), kwargs.pop('gt_bev_mask')
+        img_feats, _, depth, bev_mask, extras = self.extract_feat(points, img=img_inputs, img_metas=img_metas, **kwargs)
+        (render_imgs, gt_images, render_image_G_all, render_image_N_all, opacity_alpha_view, cam_idx_list, render_depth,
+         render_depth_G_all, render_depth_N_all) = extras
+        vt = self.img_view_transformer
+        values = vt.get_loss(depth, bev_mask[1], gt_depth, gt_semantic, gt_bboxes, cam_idx_list, render_imgs, gt_images,
+                             render_image_G_all, render_image_N_all, render_depth, render_depth_G_all,
+                             render_depth_N_all)
+        losses = dict(zip(LOSS_KEYS_NECK, values))
+        if opacity_alpha_view is not None:
+            losses.update(vt.prob.get_bev_opacity_loss(gt_bev_mask, opacity_alpha_view.squeeze(1)))
+        losses.update(vt.prob.get_bev_mask_loss(gt_bev_mask, bev_mask[0]))
+        losses.update(self.forward_pts_train(img_feats, gt_bboxes_3d, gt_labels_3d, img_metas, gt_bboxes_ignore))
+        return losses
+
+    def simple_test_pts(self, x, img_metas, rescale=False):
+        """``CenterPoint.simple_test_pts``: the head, ``get_bboxes``, and ``bbox3d2result``'s dict on the host."""
+        outs = self.pts_bbox_head(x)
+        bbox_list = self.pts_bbox_head.get_bboxes(outs, img_metas, rescale=rescale)
+        return [dict(boxes_3d=boxes.to('cpu'), scores_3d=scores.cpu(), labels_3d=labels.cpu())
+                for boxes, scores, labels in bbox_list]
+
+    def simple_test(self, points=None, img_metas=None, img=None, rescale=False, img_inputs=None, **kwargs):
+        """ocrfdet.py:48-63: a list over the samples of ``dict(pts_bbox=dict(boxes_3d, scores_3d, labels_3d))``.
+        ``img_metas``: a list of per-sample dicts, or None (then one empty dict per sample)."""
+        img = img_inputs if img is None else img
+        img_feats = self.extract_feat(points, img=img, img_metas=img_metas, **kwargs)[0]
+        if img_metas is None:
+            img_metas = [dict() for _ in range(img[0].shape[0])]
+        return [dict(pts_bbox=pts_bbox) for pts_bbox in self.simple_test_pts(img_feats, img_metas, rescale=rescale)]
+
+    def forward_dummy(self, points=None, img_metas=None, img_inputs=None, **kwargs):
+        img_feats = self.extract_feat(points, img=img_inputs, img_metas=img_metas, **kwargs)[0]
+        assert self.with_pts_bbox
+        return self.pts_bbox_head(img_feats)
+
+    def forward(self, return_loss=True, **kwargs):
+        """mmdet3d's ``Base3DDetector.forward``: ``forward_train`` or ``simple_test`` (no test-time augmentation, no
+        ``DataContainer`` unwrapping: ``img_inputs`` is the 12-entry list itself)."""
+        if return_loss:
+            return self.forward_train(**kwargs)
+        return self.simple_test(**kwargs)
