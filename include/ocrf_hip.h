@@ -744,6 +744,55 @@ int ocrf_frame_poses(int B, int F, int N, int T, const float *sensor2egos, const
                      ocrf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Image stage of the input pipeline (csrc/image_prep.hip): Pillow's resize (BICUBIC, 8-bit), crop, left-right flip and
+ * NEAREST rotate, and mmcv's imnormalize, as PrepareImageInputs applies them to every camera frame
+ * (mmdet3d/datasets/pipelines/loading.py:1071-1123), for all M frames in three launches: a horizontal and a vertical
+ * resampling pass in Pillow's integer arithmetic, and an epilogue that writes the three float outputs.  Bit-equal to
+ * Pillow by construction: the coefficient tables are built on the host (ocrfdet_amd/inputs.py).  Deterministic, no
+ * atomics, no host reads.
+ *
+ * frames (M, Hs, Ws, 3) u8 RGB, M = cameras * F with a camera's F frames adjacent; they share the camera's augmentation.
+ * table: n_table int32 words.  Camera g owns words [g * OCRF_IMAGE_PREP_ROW, (g + 1) * OCRF_IMAGE_PREP_ROW):
+ *   0 r0, 1 rows      the source rows [r0, r0 + rows) the vertical taps of the crop read; rows <= r_max
+ *   2 hb, 3 hk, 4 hks horizontal pass: word offsets of bounds (fW x 2: first source column, tap count) and of the
+ *                     coefficients (hks x fW, tap-major, 22 fractional bits), one entry per column of the CROP; a column
+ *                     outside the resized image has tap count 0
+ *   5 vb, 6 vk, 7 vks vertical pass: bounds (fH x 2) and coefficients (fH x vks, row-major) per row of the crop, the
+ *                     first tap an absolute source row
+ *   8 flip, 9 identity (rotate(0): a copy), 10..15 a0..a5: Image.rotate's affine map in 16.16 fixed point
+ * A pass over an axis whose size does not change is the one-tap table with coefficient 2^22.
+ * tmp (M, r_max, fW, 3) u8 and crop (M, fH, fW, 3) u8 are scratch; crop holds resize + crop afterwards.
+ * Outputs (M, 3, fH, fW) f32, every element written:
+ *   imgs         normalise(rotate(flip(crop)))      imgs_wo_aug  normalise(crop)      imgs_wo_norm  float(flip(crop)), RGB
+ *   normalise: output channel c = (float(rgb[2 - c]) - mean[c]) * stdinv[c] (imnormalize with to_rgb=True on an RGB array)
+ * Limits: M <= 65535, M a multiple of F, source sides <= OCRF_IMAGE_PREP_MAX_SOURCE, output sides <=
+ * OCRF_IMAGE_PREP_MAX_OUTPUT, 0 < r_max <= Hs; anything else returns hipErrorInvalidValue and launches nothing.  A table
+ * entry that points outside the table or the source yields zeros.
+ */
+#define OCRF_IMAGE_PREP_ROW 16
+#define OCRF_IMAGE_PREP_MAX_SOURCE 32767
+#define OCRF_IMAGE_PREP_MAX_OUTPUT 8192
+int ocrf_image_prep(int M, int F, int Hs, int Ws, int fH, int fW, int r_max, const unsigned char *frames,
+                    const int *table, long long n_table, unsigned char *tmp, unsigned char *crop, float mean0,
+                    float mean1, float mean2, float stdinv0, float stdinv1, float stdinv2, float *imgs,
+                    float *imgs_wo_aug, float *imgs_wo_norm, ocrf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Point labels of the input pipeline (csrc/point_labels.hip): point_label_transform (loading.py:858-891) for all
+ * cameras in two launches.  points (cameras, P, 4) f64: (u, v, depth, label) padded to P; counts (cameras) i32: the real
+ * length of each row.  cams (cameras, OCRF_POINT_LABELS_ROW) f64: resize, crop[0], crop[1], flip (0 / 1), cos and sin
+ * of rotate / 180 * pi (computed on the host), two unused.  winner (cameras, H, W) i32 scratch: ALL ZERO on entry, all
+ * zero again when the launches end; one stream at a time.  Outputs (cameras, H, W) f32, every element written: gt_depth
+ * (depth of the last point that lands on the pixel, else 0) and gt_semantic (that point's label >= 0).  float64
+ * arithmetic in the reference's order, no fused multiply-add; coordinates truncate toward zero; a point with a
+ * coordinate of magnitude >= 32768 (where numpy's int16 cast wraps) or NaN is dropped.  Deterministic: an integer
+ * atomicMax over point indices.  P = 0 launches the second kernel only.
+ */
+#define OCRF_POINT_LABELS_ROW 8
+int ocrf_point_labels(int cameras, int P, int H, int W, const double *points, const int *counts, const double *cams,
+                      int *winner, float *gt_depth, float *gt_semantic, ocrf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * The tail of a training iteration (csrc/optim.hip): clip_grad_norm_(max_norm, norm_type=2), torch.optim.AdamW and the
  * weight EMA of mmdet3d/core/hook/ema.py:48-60 (v *= d; v += (1 - d) * msd[k]) over ALL tensors of a model in three
  * launches, whatever their count (configs/ocrfdet/ocrfdet.py:259-274, 329-330).  f32, contiguous tensors.
@@ -1345,7 +1394,12 @@ enum {
   OCRF_K_BN_ACT_FWD_BF16 = 129,       /* bn_act_forward_kernel<unsigned short, V> */
   OCRF_K_BN_ACT_BWD_REDUCE_BF16 = 130, /* bn_act_backward_reduce_kernel<unsigned short, V> */
   OCRF_K_BN_ACT_BWD_BF16 = 131,       /* bn_act_backward_kernel<unsigned short, V> */
-  OCRF_K_FRAME_POSES = 132            /* frame_poses_kernel */
+  OCRF_K_FRAME_POSES = 132,           /* frame_poses_kernel */
+  OCRF_K_IMAGE_PREP_HORIZONTAL = 133, /* image_prep_horizontal_kernel */
+  OCRF_K_IMAGE_PREP_VERTICAL = 134,   /* image_prep_vertical_kernel */
+  OCRF_K_IMAGE_PREP_EPILOGUE = 135,   /* image_prep_epilogue_kernel */
+  OCRF_K_POINT_LABELS_MARK = 136,     /* point_labels_mark_kernel */
+  OCRF_K_POINT_LABELS_RESOLVE = 137   /* point_labels_resolve_kernel */
 };
 const char *ocrf_kernel_name(int kernel_id);           /* symbol as rocprofv3 prints it */
 /* Diagnostic: a one-thread kernel that stores the device's constant-rate clock (wall_clock64, 100 MHz)

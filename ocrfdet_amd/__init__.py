@@ -30,6 +30,10 @@ Drop-in mirrors of the reference's Python surface for that path (and nothing els
   DefaultOptimizerConstructor custom_keys
   ...detectors.ocrfdet.OcRFDet4D and              ocrfdet_amd.detector (OcRFDet4D, prepare_inputs, frame_poses,
   BEVDet4D.prepare_inputs                         frame_poses_torch, also exported here)
+  ...datasets.pipelines.loading                   ocrfdet_amd.inputs (sample_augmentation, post_homography,
+  PrepareImageInputs (image and point-label       sample_bda_augmentation, bev_transform, assemble_img_inputs,
+  stage), LoadAnnotationsBEVDepth.bev_transform   prepare_images, point_label_maps and their *_torch forms, also
+                                                  exported here)
   ==============================================  =================================================
 
 Every op calls the C ABI of ``csrc/libocrf_hip.so`` (``include/ocrf_hip.h``) through ctypes with
@@ -43,6 +47,9 @@ _LAZY_TEMPORAL = ('feature_transform', 'shift_feature', 'shift_feature_torch', '
                   'shift_feature_method')
 _LAZY_OPTIM = ('FusedAdamW', 'ModelEMA', 'paramwise_groups')
 _LAZY_DETECTOR = ('OcRFDet4D', 'prepare_inputs', 'frame_poses', 'frame_poses_torch')
+_LAZY_INPUTS = ('sample_augmentation', 'post_homography', 'sample_bda_augmentation', 'bev_transform',
+                'assemble_img_inputs', 'prepare_images', 'prepare_images_torch', 'point_label_maps',
+                'point_label_maps_torch')
 
 
 def __getattr__(name):
@@ -61,4 +68,7 @@ def __getattr__(name):
     if name in _LAZY_DETECTOR:
         from . import detector
         return getattr(detector, name)
+    if name in _LAZY_INPUTS:
+        from . import inputs
+        return getattr(inputs, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

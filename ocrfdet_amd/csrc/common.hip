@@ -181,6 +181,11 @@ const char* ocrf_kernel_name(int kernel_id) {
     case OCRF_K_BN_ACT_BWD_REDUCE_BF16: return "bn_act_backward_reduce_kernel<unsigned short, *>";
     case OCRF_K_BN_ACT_BWD_BF16: return "bn_act_backward_kernel<unsigned short, *>";
     case OCRF_K_FRAME_POSES: return "frame_poses_kernel";
+    case OCRF_K_IMAGE_PREP_HORIZONTAL: return "image_prep_horizontal_kernel";
+    case OCRF_K_IMAGE_PREP_VERTICAL: return "image_prep_vertical_kernel";
+    case OCRF_K_IMAGE_PREP_EPILOGUE: return "image_prep_epilogue_kernel";
+    case OCRF_K_POINT_LABELS_MARK: return "point_labels_mark_kernel";
+    case OCRF_K_POINT_LABELS_RESOLVE: return "point_labels_resolve_kernel";
     default: return "";
   }
 }
