@@ -1282,6 +1282,52 @@ int ocrf_cbam_tail(const float *y, const float *scale, const float *stats, const
                    const float *res, const float *wm, float bm, int B, int C, int Y, int X, float *logit,
                    float *block_out, ocrf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Deformable convolution, DCN v1 (csrc/deform_conv.hip, csrc/deform_taps.h): the data-dependent bilinear gather of
+ * mmcv 1.x deform_conv2d (the deformable im2col) and its transpose.  The dense products around them (weight x col,
+ * weight^T x grad_out, grad_out x col^T) are GEMMs and stay with the caller (ocrfdet_amd/deform_conv.py).  f32, no
+ * workspace, no host reads.
+ *
+ * Geometry.  x (n, C, H, W), offset (n, dg * 2 * kh * kw, Ho, Wo), both contiguous; K = kh * kw, P = Ho * Wo,
+ *   Ho = (H + 2 pad_h - dil_h (kh - 1) - 1) / stride_h + 1 (Wo alike), which the entry points compute themselves.
+ *   Input channel c belongs to deformable group g = c / (C / dg).
+ * Sampling rule.  For tap k = i * kw + j of group g at output position (ho, wo), offset channel g * 2K + 2k is the ROW
+ *   offset and 2k + 1 the COLUMN offset:
+ *     h = (float)(ho * stride_h - pad_h + i * dil_h) + off_h,   w = (float)(wo * stride_w - pad_w + j * dil_w) + off_w.
+ *   The sample is 0 unless h > -1 && w > -1 && h < H && w < W (in float, so that a NaN fails).  Inside, hl = floorf(h),
+ *   lh = h - hl (w alike), and the corners (hl | hl + 1, wl | wl + 1) carry (1 - lh | lh) * (1 - lw | lw); a corner
+ *   outside the map contributes 0.  The test comes before any conversion to int: for ANY float offset (NaN, infinities,
+ *   1e30) the weights are 0 and the indices lie inside the map.
+ *
+ * ocrf_deform_im2col: col[b - n0][c * K + k][ho * Wo + wo] = the sample, for the images n0 <= b < n1; col holds
+ *   (n1 - n0, C * K, P) floats.  One launch, every element written exactly once.  A thread takes one (image, group,
+ *   chunk of 32 channels, tap, position), forms the coordinates and the four weights once and walks its channels; lanes
+ *   are neighbouring positions, so the offset loads and the col stores are coalesced.
+ * ocrf_deform_col2im: gcol laid out like col for the images n0 <= b < n1 -> grad_x and grad_offset of those images
+ *   (both addressed as the whole (n, ...) tensors).  A thread takes one (image, group, tap, position), walks the group's
+ *   channels in ascending order, adds the four corner terms gcol * weight to grad_x with float atomicAdd (the hardware
+ *   add, no compare-and-swap loop) and sums
+ *     d sample / d h = (1 - lw) (x[hl+1][wl] - x[hl][wl]) + lw (x[hl+1][wl+1] - x[hl][wl+1])   (w alike)
+ *   times gcol in registers; each grad_offset element is written once.  grad_offset is deterministic; grad_x is a
+ *   scatter to data-dependent targets and reproducible only to rounding (the order of the adds is not fixed).  The
+ *   entry point zeroes grad_x of its images itself (hipMemsetAsync on the stream) and then launches once.  At an
+ *   integer coordinate the derivative is the one floorf implies (from the right).
+ * ocrf_deform_taps: host only, touches no GPU.  The kernels' own coordinate function (deform_taps.h) for one tap:
+ *   base_h = ho * stride_h - pad_h + i * dil_h, base_w alike.  weights[0..3] and index[0..3] (row * W + column, clamped
+ *   into the map) of the corners (hl, wl), (hl, wl + 1), (hl + 1, wl), (hl + 1, wl + 1); frac[0..1] = lh, lw (0 when the
+ *   range test fails).
+ * Limits: every size positive, stride and dilation >= 1, pad >= 0, C a multiple of dg, H, W, pad and the kernel's
+ *   extent below 2^20, Ho and Wo >= 1, 0 <= n0 < n1 <= n, and x, offset, col (of the images given) each below 2 GiB
+ *   (the kernels index with int); anything else returns hipErrorInvalidValue and launches nothing.
+ */
+int ocrf_deform_im2col(int n, int C, int H, int W, int kh, int kw, int stride_h, int stride_w, int pad_h, int pad_w,
+                       int dil_h, int dil_w, int dg, int n0, int n1, const float *x, const float *offset, float *col,
+                       ocrf_stream_t stream);
+int ocrf_deform_col2im(int n, int C, int H, int W, int kh, int kw, int stride_h, int stride_w, int pad_h, int pad_w,
+                       int dil_h, int dil_w, int dg, int n0, int n1, const float *gcol, const float *x,
+                       const float *offset, float *grad_x, float *grad_offset, ocrf_stream_t stream);
+int ocrf_deform_taps(int H, int W, int base_h, int base_w, float off_h, float off_w, float *weights, int *index,
+                     float *frac);
 
 /* ------------------------------------------------------------------------------------------
  * Per-kernel device timer (measurement aid for bench.py; not part of the reference's surface)
@@ -1399,7 +1445,9 @@ enum {
   OCRF_K_IMAGE_PREP_VERTICAL = 134,   /* image_prep_vertical_kernel */
   OCRF_K_IMAGE_PREP_EPILOGUE = 135,   /* image_prep_epilogue_kernel */
   OCRF_K_POINT_LABELS_MARK = 136,     /* point_labels_mark_kernel */
-  OCRF_K_POINT_LABELS_RESOLVE = 137   /* point_labels_resolve_kernel */
+  OCRF_K_POINT_LABELS_RESOLVE = 137,  /* point_labels_resolve_kernel */
+  OCRF_K_DEFORM_IM2COL = 138,         /* deform_im2col_kernel */
+  OCRF_K_DEFORM_COL2IM = 139          /* deform_col2im_kernel */
 };
 const char *ocrf_kernel_name(int kernel_id);           /* symbol as rocprofv3 prints it */
 /* Diagnostic: a one-thread kernel that stores the device's constant-rate clock (wall_clock64, 100 MHz)

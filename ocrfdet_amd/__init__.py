@@ -34,6 +34,9 @@ Drop-in mirrors of the reference's Python surface for that path (and nothing els
   PrepareImageInputs (image and point-label       sample_bda_augmentation, bev_transform, assemble_img_inputs,
   stage), LoadAnnotationsBEVDepth.bev_transform   prepare_images, point_label_maps and their *_torch forms, also
                                                   exported here)
+  mmcv.ops DeformConv2d, DeformConv2dPack         ocrfdet_amd.deform_conv (deform_conv2d, deform_conv2d_torch,
+  (type 'DCN'), deform_conv2d                     DeformConv2d, DeformConv2dPack, build_dcn; opt-in in depthnet
+                                                  through NATIVE_DCN, in center_head through DCNSeparateHead)
   ==============================================  =================================================
 
 Every op calls the C ABI of ``csrc/libocrf_hip.so`` (``include/ocrf_hip.h``) through ctypes with

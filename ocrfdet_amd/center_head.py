@@ -22,8 +22,10 @@ float32 in the reference's operation order, the Gaussian in float64 as numpy com
 ``get_bboxes`` (top-K decode, circle and rotated BEV NMS, merge) is in ``center_decode.py``: fused by
 ``csrc/center_decode.hip`` in four launches with no host synchronisation (``get_bboxes_padded``), or by its torch
 formulation on the CPU, for inputs that are not float32 CUDA tensors and with ``fused_decode = False``.  A head built
-without ``bbox_coder`` or ``test_cfg`` (training only) cannot decode and raises ``NotImplementedError``; so does
-``DCNSeparateHead``.
+without ``bbox_coder`` or ``test_cfg`` (training only) cannot decode and raises ``NotImplementedError``.
+
+``DCNSeparateHead`` (``separate_head=dict(type='DCNSeparateHead', dcn_config=dict(type='DCN', ...))``) is built on
+``deform_conv.DeformConv2dPack``; a ``dcn_config`` of any other type raises ``NotImplementedError``.
 """
 import copy
 import ctypes
@@ -34,6 +36,7 @@ import torch.nn as nn
 from . import _lib
 from . import center_decode as cd
 from .blocks import ConvModule, kaiming_init
+from .deform_conv import build_dcn
 
 __all__ = ['ConvBNReLU', 'SeparateHead', 'DCNSeparateHead', 'CenterHead', 'HeatmapLoss', 'RegLoss', 'clip_sigmoid',
            'gaussian_focal_loss', 'targets_torch', 'heatmap_loss_torch', 'reg_loss_torch', 'pack_boxes', 'reduce_counts']
@@ -87,8 +90,38 @@ class SeparateHead(nn.Module):
 
 
 class DCNSeparateHead(nn.Module):
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError('DCNSeparateHead needs deformable convolution, which this project does not have')
+    """The reference's ``DCNSeparateHead`` (centerpoint_head.py:125-240): one deformable convolution in front of the
+    heatmap head (``feature_adapt_cls`` -> ``cls_head``) and one in front of the regression heads (``feature_adapt_reg``
+    -> ``task_head``, a ``SeparateHead`` without the heatmap).  ``dcn_config``: ``dict(type='DCN', in_channels=...,
+    out_channels=..., kernel_size=..., padding=..., groups=..., ...)``, built by ``deform_conv.build_dcn``; any other
+    type (or none) raises ``NotImplementedError``.
+
+    ``init_weights`` does what the reference's ``init_cfg = dict(type='Kaiming', layer='Conv2d')`` does: every
+    ``nn.Conv2d`` inside the head, the ``conv_offset`` of the two deformable convolutions included, gets Kaiming-normal
+    weights; the deformable weights themselves keep their construction-time initialisation."""
+
+    def __init__(self, in_channels, num_cls, heads, dcn_config, head_conv=64, final_kernel=1, init_bias=-2.19,
+                 conv_cfg=dict(type='Conv2d'), norm_cfg=dict(type='BN2d'), bias='auto', init_cfg=None, **kwargs):
+        assert init_cfg is None, 'To prevent abnormal initialization behavior, init_cfg is not allowed to be set'
+        super().__init__()
+        heads = dict(heads)
+        heads.pop('heatmap', None)
+        self.feature_adapt_cls = build_dcn(dcn_config)
+        self.feature_adapt_reg = build_dcn(dcn_config)
+        self.cls_head = nn.Sequential(
+            ConvBNReLU(in_channels, head_conv, 3, padding=1, conv_cfg=conv_cfg, bias=bias, norm_cfg=norm_cfg),
+            nn.Conv2d(head_conv, num_cls, 3, stride=1, padding=1, bias=bool(bias)))
+        self.init_bias = init_bias
+        self.task_head = SeparateHead(in_channels, heads, head_conv=head_conv, final_kernel=final_kernel, bias=bias)
+
+    def init_weights(self):
+        kaiming_init(self)
+        self.cls_head[-1].bias.data.fill_(self.init_bias)
+
+    def forward(self, x):
+        ret = self.task_head(self.feature_adapt_reg(x))
+        ret['heatmap'] = self.cls_head(self.feature_adapt_cls(x))
+        return ret
 
 
 def clip_sigmoid(x, eps=1e-4):

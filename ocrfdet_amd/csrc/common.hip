@@ -186,6 +186,8 @@ const char* ocrf_kernel_name(int kernel_id) {
     case OCRF_K_IMAGE_PREP_EPILOGUE: return "image_prep_epilogue_kernel";
     case OCRF_K_POINT_LABELS_MARK: return "point_labels_mark_kernel";
     case OCRF_K_POINT_LABELS_RESOLVE: return "point_labels_resolve_kernel";
+    case OCRF_K_DEFORM_IM2COL: return "deform_im2col_kernel";
+    case OCRF_K_DEFORM_COL2IM: return "deform_col2im_kernel";
     default: return "";
   }
 }

@@ -15,8 +15,9 @@ bfloat16 features (an image encoder under bf16 autocast) are cast to float32 for
 ``ocrf_stereo_pack_bf16`` launches put 8 channels of a pixel side by side and ``ocrf_stereo_cost_volume_bf16``
 (csrc/stereo_bf16.hip) gathers them 16 bytes at a time; the float32 volume is bit for bit the default's.
 
-Both run under ``no_grad`` as in the reference (:617): the cost volume has no backward.  ``use_dcn=True`` needs mmcv's
-deformable convolution and is not supported.
+Both run under ``no_grad`` as in the reference (:617): the cost volume has no backward.  ``use_dcn=True`` (the
+reference's default, :515-526) is refused unless ``NATIVE_DCN`` is set: then ``deform_conv.DeformConv2dPack`` follows the
+ASPP as in the reference.
 """
 import torch
 import torch.nn.functional as F
@@ -24,6 +25,7 @@ from torch import nn
 from torch.utils.checkpoint import checkpoint
 
 from . import _lib
+from . import deform_conv
 from .blocks import BasicBlock, kaiming_init, unfuse_tails
 
 __all__ = ['BasicBlock', 'Mlp', 'SELayer', 'ASPP', '_ASPPModule', 'DepthNet', 'stereo_cost_volume',
@@ -34,6 +36,9 @@ GROUP = 4                   # channels per group of the reference's loop (:580)
 PLANE_BYTES_MAX = 2 ** 32 - 1   # one camera's prev in bytes: the kernel addresses it in unsigned 32-bit
 PACK = 8                    # channels per pixel of a packed bfloat16 block: two groups, 16 bytes
 PACKED_BYTES_MAX = 2 ** 32 - 1  # one camera's packed bfloat16 prev in bytes, addressed likewise
+# use_dcn=True builds the native deformable convolution (deform_conv.DeformConv2dPack).  Off by default: while it is
+# False, use_dcn=True is refused and ``supports({})`` is False, as before the native operator existed
+NATIVE_DCN = False
 
 
 # --------------------------------------------------------------------------------------------- building blocks
@@ -292,8 +297,9 @@ def stereo_cost_volume(metas, bias, fused=True, raw=False, keep_bf16=False):
 
 # --------------------------------------------------------------------------------------------- DepthNet
 def supports(cfg):
-    """Whether ``DepthNet(..., **cfg)`` can be built natively (no deformable convolution)."""
-    return not cfg.get('use_dcn', True)
+    """Whether ``DepthNet(..., **cfg)`` can be built natively: without deformable convolution, or with it when
+    ``NATIVE_DCN`` is set."""
+    return NATIVE_DCN or not cfg.get('use_dcn', True)
 
 
 class DepthNet(nn.Module):
@@ -307,9 +313,9 @@ class DepthNet(nn.Module):
     def __init__(self, in_channels, mid_channels, context_channels, depth_channels, use_dcn=True, use_aspp=True,
                  with_cp=False, stereo=False, bias=0.0, aspp_mid_channels=-1):
         super().__init__()
-        if use_dcn:
-            raise NotImplementedError('DepthNet(use_dcn=True) needs mmcv\'s deformable convolution, which has no '
-                                      'native implementation here (INTEGRATION.md 3c)')
+        if use_dcn and not NATIVE_DCN:
+            raise NotImplementedError('DepthNet(use_dcn=True) needs mmcv\'s deformable convolution; the native one is '
+                                      'opt-in: set depthnet.NATIVE_DCN = True (INTEGRATION.md 3c, 3m)')
         self.reduce_conv = nn.Sequential(nn.Conv2d(in_channels, mid_channels, 3, stride=1, padding=1),
                                          nn.BatchNorm2d(mid_channels), nn.ReLU(inplace=True))
         self.context_conv = nn.Conv2d(mid_channels, context_channels, 1, stride=1, padding=0)
@@ -331,6 +337,9 @@ class DepthNet(nn.Module):
                   BasicBlock(mid_channels, mid_channels)]
         if use_aspp:
             layers.append(ASPP(mid_channels, mid_channels if aspp_mid_channels < 0 else aspp_mid_channels))
+        if use_dcn:
+            layers.append(deform_conv.build_dcn(dict(type='DCN', in_channels=mid_channels, out_channels=mid_channels,
+                                                     kernel_size=3, padding=1, groups=4, im2col_step=128)))
         layers.append(nn.Conv2d(mid_channels, depth_channels, 1, stride=1, padding=0))
         self.depth_conv = nn.Sequential(*layers)
         # off because the tail is unmeasured at these shapes; flipping it is a separate change with its own
