@@ -533,9 +533,11 @@ __device__ __forceinline__ void dyn_record(const SetParams& sp, long gi, const f
 //   [19] some view is deep  [96, 128) deep[v]: the last render of view v walked far into its list (>= kDeepReach entries:
 //   its pixels do not saturate early) — the head kernel then prepares the view's WHOLE list and the candidates of its bins
 //   are compacted per call (raster_plan_compact_kernel)
-//   [20] this call's compaction ran (written by raster_plan_compact_kernel)  [128, 134) its three tables' addresses (b_seg,
-//   ccnt, ccand as 64-bit words): the blend reads them from here only when a tile pair is deep — as kernel arguments they
-//   cost six more scalar registers everywhere, and the kernel already spills scalars (measured: +25 us on the init set)
+//   [20] this call's compaction ran (cleared by raster_plan_head_kernel's bookkeeping thread in every call that updates,
+//   raised behind it by raster_plan_compact_kernel when it ran: never an earlier call's)
+//   [128, 134) its three tables' addresses (b_seg, ccnt, ccand as 64-bit words): the blend reads them from here only when
+//   a tile pair is deep — as kernel arguments they cost six more scalar registers everywhere, and the kernel already
+//   spills scalars (measured: +25 us on the init set)
 constexpr int kCtlQueue = 16, kCtlArrive = 17, kCtlDeferred = 18, kCtlAnyDeep = 19, kCtlCompacted = 20, kCtlHead = 32,
               kCtlReach = 64, kCtlDeep = 96, kCtlTables = 128;      // (1024 bytes: dyn_layout)
 constexpr int kDeepReach = 8192;
@@ -636,6 +638,10 @@ __global__ __launch_bounds__(kBlock) void raster_plan_head_kernel(HeadArgs a) {
     if (threadIdx.x == 0) {
       reinterpret_cast<unsigned long long*>(a.ctl + kCtlTables)[3] = reinterpret_cast<unsigned long long>(a.hint);
       a.ctl[kCtlQueue] = 0;                        // ticket counter of the blend that follows
+      // no compaction yet this call: the compact kernel, when the host launches it behind this one, raises the word
+      // again.  A blend-only call (phase 2) chooses its build from a host read of its own and must not take an EARLIER
+      // call's tables (other rects) for this call's
+      a.ctl[kCtlCompacted] = 0;
       if (flag) flag[1] = 0;                       // arrival counter of the armed per-call blend (rasterize.hip)
     }
     if (a.call_cams) {

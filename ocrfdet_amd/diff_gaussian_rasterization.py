@@ -275,14 +275,15 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.has_cov = cov3Ds_precomp is not None and cov3Ds_precomp.numel() > 0
         # the forward's outputs are saved through autograd (not as plain attributes): the backward
         # rebuilds S = C_out - T_final * bg from them, so an in-place edit of the rendered image
-        # (clamp_, mul_) must raise instead of silently changing the gradients
+        # (clamp_, mul_) must raise instead of silently changing the gradients.  The same holds for the SH
+        # coefficients and their clamp mask, which the backward of the colours reads: last in the tuple
+        sh_saved = (sh, sh_clamped) if ctx.has_sh else ()
         if ctx.has_cov:
             ctx.save_for_backward(means3D, colors_precomp, opacities, cov3Ds_precomp, color, out['final_T'],
-                                  out.get('n_contrib'))
+                                  out.get('n_contrib'), *sh_saved)
         else:
             ctx.save_for_backward(means3D, colors_precomp, opacities, scales, rotations, color, out['final_T'],
-                                  out.get('n_contrib'))
-        ctx.sh_state = (sh, sh_clamped) if ctx.has_sh else None
+                                  out.get('n_contrib'), *sh_saved)
         return color, radii, depth
 
     @staticmethod
@@ -290,7 +291,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         """With SH colours: dL/dcolors goes on to the coefficients and, through the view direction, to the means."""
         if not ctx.has_sh:
             return g['means3D'], None, g['colors']
-        sh, clamped = ctx.sh_state
+        sh, clamped = ctx.saved_tensors[-2:]
         rs = ctx.raster_settings
         d_means, d_sh = sh_to_rgb_backward(means3D, rs.campos, sh, rs.sh_degree, clamped, g['colors'], g['means3D'])
         return d_means, d_sh.to(sh.dtype), None
@@ -301,7 +302,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings."""
         rs = ctx.raster_settings
         if ctx.has_cov:
-            means3D, colors, opacities, cov, fwd_color, fwd_T, fwd_n = ctx.saved_tensors
+            means3D, colors, opacities, cov, fwd_color, fwd_T, fwd_n = ctx.saved_tensors[:7]
             fwd = dict(color=fwd_color.unsqueeze(0), final_T=fwd_T, n_contrib=fwd_n)
             g = rasterize_views_backward(grad_color.unsqueeze(0), fwd, means3D, colors, opacities, None, None,
                                          rs.viewmatrix.reshape(1, 4, 4), rs.projmatrix.reshape(1, 4, 4),
@@ -311,7 +312,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             grads = (d_means, g['means2D'][0], d_sh, d_col, g['opacities'].reshape(opacities.shape),
                      None, None, g['cov3D'].reshape(cov.shape), None)
             return tuple(v if need else None for v, need in zip(grads, ctx.needs_input_grad))
-        means3D, colors, opacities, scales, rotations, fwd_color, fwd_T, fwd_n = ctx.saved_tensors
+        means3D, colors, opacities, scales, rotations, fwd_color, fwd_T, fwd_n = ctx.saved_tensors[:8]
         fwd = dict(color=fwd_color.unsqueeze(0), final_T=fwd_T, n_contrib=fwd_n)
         g = rasterize_views_backward(grad_color.unsqueeze(0), fwd, means3D, colors, opacities, scales, rotations,
                                      rs.viewmatrix.reshape(1, 4, 4), rs.projmatrix.reshape(1, 4, 4),

@@ -92,6 +92,46 @@ def test_render_with_shs_is_the_render_of_the_sh_colours(cuda):
         assert float(t['shs'].grad[:, (deg + 1) ** 2:].abs().max()) == 0 if deg < 3 else True
 
 
+def test_sh_coefficients_edited_in_place_before_backward_raise(cuda):
+    """The SH coefficients and their clamp mask are saved through autograd like every other tensor the backward reads
+    (``_RasterizeGaussians.forward``): an in-place edit of ``shs`` between forward and backward raises torch's version
+    error instead of silently giving the gradients of other coefficients.  ``shs`` is a non-leaf (``leaf * 1.0``: torch
+    refuses in-place edits of a leaf that requires grad by itself, and that product saves nothing of its own, so the
+    error is this function's).  Untouched, the same run gives the gradients of the chain of the two backwards, to the
+    bars of ``test_render_with_shs_is_the_render_of_the_sh_colours``."""
+    rng = np.random.default_rng(6)
+    W, H, P, deg = 96, 64, 1500, 3
+    xyz, _, opac, sc, rot = helpers.random_gaussians(rng, P)
+    shs = (rng.standard_normal((P, 16, 3)) * 0.5).astype(np.float32)
+    _, _, _, _, s = _camera(cuda, W, H, (0.3, -0.2, 0.1))
+    w = None
+    grads = {}
+    for edit in (False, True):
+        t = {k: _t(v, cuda).requires_grad_(True) for k, v in dict(xyz=xyz, shs=shs, opac=opac, sc=sc, rot=rot).items()}
+        coeff = t['shs'] * 1.0
+        img, _, _ = dgr.GaussianRasterizer(s)(t['xyz'], None, t['opac'], shs=coeff, scales=t['sc'], rotations=t['rot'])
+        w = torch.rand_like(img) if w is None else w
+        loss = (img * w).sum()
+        if edit:
+            coeff.mul_(2.0)
+            with pytest.raises(RuntimeError, match='modified by an inplace operation'):
+                loss.backward()
+            assert t['shs'].grad is None and t['xyz'].grad is None
+        else:
+            loss.backward()
+            grads = {k: v.grad for k, v in t.items()}
+    u = {k: _t(v, cuda).requires_grad_(True) for k, v in dict(xyz=xyz, opac=opac, sc=sc, rot=rot).items()}
+    col, clamped = dgr.sh_to_rgb(u['xyz'].detach(), s.campos, _t(shs, cuda), deg)
+    col.requires_grad_(True)
+    img2, _, _ = dgr.GaussianRasterizer(s)(u['xyz'], None, u['opac'], colors_precomp=col, scales=u['sc'], rotations=u['rot'])
+    (img2 * w).sum().backward()
+    d_means, d_sh = dgr.sh_to_rgb_backward(u['xyz'].detach(), s.campos, _t(shs, cuda), deg, clamped, col.grad,
+                                           u['xyz'].grad.clone())
+    for name, got, want in (('shs', grads['shs'], d_sh), ('means3D', grads['xyz'], d_means),
+                            ('opacities', grads['opac'], u['opac'].grad), ('scales', grads['sc'], u['sc'].grad)):
+        assert float((got - want).abs().max()) <= 1e-4 * float(want.abs().max()) + 1e-7, name
+
+
 def test_sh_gradients_vs_float64_autograd_of_the_oracle_formulation(cuda):
     """The whole SH stage against torch autograd in float64 (the transcription tests/test_oracle_sh.py pins the oracle
     with): d colour / d coefficients and d colour / d mean for a random upstream gradient, degree 3."""
