@@ -1336,7 +1336,8 @@ int ocrf_deform_taps(int H, int W, int base_h, int base_w, float off_h, float of
  * a hipEvent pair recorded on the launch stream (hipExtLaunchKernelGGL), up to `capacity`
  * launches.  ocrf_timer_read waits for the recorded pairs and returns their elapsed
  * milliseconds.  Several timers (for different kernel ids) may be armed at once; arming with
- * timer == NULL disarms all of them.  Host-side only. */
+ * timer == NULL disarms all of them.  Host-side only.  The rasteriser's front end (preprocess, scan,
+ * gather) is launched by the backward too, under the same ids; nothing in the package arms those. */
 enum {
   OCRF_K_BEV_POOL_FWD = 1,      /* bev_pool_tile_kernel */
   OCRF_K_BEV_POOL_FIXUP = 2,    /* (retired) */

@@ -680,7 +680,7 @@ __global__ __launch_bounds__(kBlock) void bev_pool_grad_scalar_kernel(
 
 inline bool vec_ok(int c) { return c >= 32 && c <= 256 && (c % 4) == 0; }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+using ocrf::align_up;
 
 // ---- host-side geometry of the prep block, the slabs and one launch ------------------------------
 struct PoolGeom {

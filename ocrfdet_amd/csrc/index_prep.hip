@@ -594,7 +594,7 @@ __global__ void ht_counts_kernel(const long long* __restrict__ total, int* __res
   counts[1] = failed ? -1 : (int)(*total & 0x7FFFFFFFll);
 }
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+using ocrf::align_up;
 
 inline int radix_passes(unsigned n_vox_total) {
   int bits = 1;

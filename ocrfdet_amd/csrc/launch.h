@@ -45,6 +45,9 @@ inline void launch(int kernel_id, F kernel, dim3 grid, dim3 block, size_t lds, h
 // sequence).  A kernel is also cheaper than the memset path for these sizes (32-320 KB).
 hipError_t zero_async(void* dst, size_t bytes, hipStream_t stream);
 
+// workspace carving: `v` rounded up to a multiple of `a`
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
 // raster_plan.hip: diagnostic knobs reached through ocrf_tune_set (keys 10-19)
 void raster_plan_tune(int key, int value);
 // hoa.hip: keys 20-29

@@ -57,7 +57,7 @@ constexpr int kSrcWaves = rbody::kSrcWavesB;
 constexpr int kCapPos = kStageP + kScanUnrollP * kBlock;
 constexpr unsigned kPosMask = 0x3FFFFFFFu;
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+using ocrf::align_up;
 
 struct PlanLayout {
   size_t header, cams, g_mask, g_off, e_q0, e_q1, s_id, s_key, s_pix, s_e, bytes;

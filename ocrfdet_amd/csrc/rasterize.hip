@@ -1280,30 +1280,88 @@ __global__ __launch_bounds__(kBlock) void raster_preprocess_backward_kernel(
   dL_drotations[4 * idx + 3] = 2 * r * (Q[1][0] - Q[0][1]) + 2 * x * (Q[0][2] + Q[2][0]) + 2 * y * (Q[2][1] + Q[1][2]) - 4 * z * (Q[1][1] + Q[0][0]);
 }
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+using ocrf::align_up;
 
-struct RasterWs {
-  size_t vis_rec, rects, xy, conic_o, b_rect, b_comp, hist, starts, cursor, status, total, acc, radii, bwd_total;
+// The workspace of the per-call pipeline, laid out and carved in one place: the forward chain, the backward and
+// raster_chain_hist all take their buffers from here, the size queries their totals (workspace == nullptr).
+struct RasterBufs {
+  uint4* vis_rec;
+  Rect *rects, *b_rect;
+  float2* xy;
+  float4* conic_o;
+  unsigned long long* b_comp;
+  int *hist, *vis_count, *starts, *cursor, *status;      // hist and vis_count are one block of hist_words ints
+  size_t hist_words;
+  float* acc;                                             // backward only: past `total`
+  int* radii;
+  size_t total, bwd_total;                                // bytes the forward / the backward needs
 };
 
-inline void raster_layout(int P, int n_views, RasterWs* ws) {
+inline RasterBufs raster_layout(void* workspace, int P, int n_views) {
   const size_t n = (size_t)P * n_views;
+  RasterBufs b;
   size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes, 256); return o; };
-  ws->vis_rec = take(n * sizeof(uint4));
-  ws->rects = take(n * sizeof(Rect));
-  ws->xy = take(n * sizeof(float2));
-  ws->conic_o = take(n * sizeof(float4));
-  ws->b_rect = take(n * sizeof(Rect));
-  ws->b_comp = take(n * 8);
-  ws->hist = take((size_t)n_views * (kBuckets + 1) * sizeof(int));      // + the per-view visible counts
-  ws->starts = take((size_t)n_views * (kBuckets + 1) * sizeof(int));
-  ws->cursor = take((size_t)n_views * kBuckets * sizeof(int));
-  ws->status = take(256);
-  ws->total = off;
-  ws->acc = take(n * 9 * sizeof(float));          // backward only
-  ws->radii = take(n * sizeof(int));
-  ws->bwd_total = off;
+  auto take = [&](auto*& p, size_t bytes) {      // integer arithmetic: a size query lays out at address 0
+    p = reinterpret_cast<decltype(+p)>(reinterpret_cast<uintptr_t>(workspace) + off);
+    off += align_up(bytes, 256);
+  };
+  take(b.vis_rec, n * sizeof(uint4));
+  take(b.rects, n * sizeof(Rect));
+  take(b.xy, n * sizeof(float2));
+  take(b.conic_o, n * sizeof(float4));
+  take(b.b_rect, n * sizeof(Rect));
+  take(b.b_comp, n * 8);
+  b.hist_words = (size_t)n_views * (kBuckets + 1);      // + the per-view visible counts
+  take(b.hist, b.hist_words * sizeof(int));
+  b.vis_count = b.hist + (size_t)n_views * kBuckets;
+  take(b.starts, (size_t)n_views * (kBuckets + 1) * sizeof(int));
+  take(b.cursor, (size_t)n_views * kBuckets * sizeof(int));
+  take(b.status, 256);
+  b.total = off;
+  take(b.acc, n * 9 * sizeof(float));
+  take(b.radii, n * sizeof(int));
+  b.bwd_total = off;
+  return b;
+}
+
+enum class Lists {
+  // The reference's lists, record for record: every (Gaussian, tile) pair of the reference's rect.  The per-pixel
+  // contributor index counts records of THESE lists, and the backward walks the lists of the forward that wrote the
+  // index it is given: so a forward that tracks the index (out_n_contrib) builds them, and the backward always does.
+  kReference,
+  // Rects tightened by the opacity (raster_common.h): the same image from fewer records, for a forward that does not
+  // track the index.
+  kTightened
+};
+
+// The front end both directions share: histogram zero-fill (unless the caller cleared raster_chain_hist() itself),
+// preprocess, bucket scan, scatter -> the bucket-ordered lists (b.starts, b.b_rect, b.b_comp) the blend walks.  What
+// a forward and its backward must agree on are exactly these parameters.
+hipError_t raster_front_end(const RasterBufs& b, Lists lists, int P, int n_views, int views_per_set, int W, int H, int gx,
+                            int gy, const float* means3D, const float* opacities, const float* scales,
+                            float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                            const Camera* cams, const int* view_sel, const int* gate, bool shared_means, int* radii,
+                            uint32_t* tiles_touched, int* status, bool hist_is_zero, hipStream_t stream) {
+  hipError_t e = hipSuccess;
+  if (!hist_is_zero) e = ocrf::zero_async(b.hist, b.hist_words * sizeof(int), stream);
+  if (e != hipSuccess) return e;
+  const int n_chunks = (P + kChunk - 1) / kChunk, n_pre = (P + kPreChunk - 1) / kPreChunk;
+  const dim3 pgrid(n_chunks, n_views);
+  const dim3 xgrid((unsigned)((n_pre + 7) / 8 * 8 * n_views));         // (chunk, view) pairs, XCD-aware order
+  ocrf::launch(OCRF_K_RASTER_PREPROCESS, raster_preprocess_kernel, xgrid, dim3(kBlock), 0, stream, P, n_views,
+               n_pre, W, H, gx, gy, means3D, opacities, scales, scale_modifier, rotations, cov3D_precomp,
+               cams, b.vis_rec, b.vis_count, b.rects, b.xy, b.conic_o, radii, tiles_touched, b.hist, views_per_set,
+               view_sel, gate, shared_means ? 0 : P, lists == Lists::kTightened ? 1 : 0);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  ocrf::launch(OCRF_K_RASTER_SCAN, raster_bucket_scan_kernel, dim3(n_views), dim3(kBlock), 0, stream,
+               static_cast<const int*>(b.hist), b.starts, b.cursor, status, gate);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  ocrf::launch(OCRF_K_RASTER_GATHER, raster_scatter_kernel, pgrid, dim3(kBlock), 0, stream, P,
+               static_cast<const uint4*>(b.vis_rec), static_cast<const int*>(b.vis_count), b.cursor, b.b_rect, b.b_comp,
+               gate);
+  return hipGetLastError();
 }
 
 }  // namespace
@@ -1315,10 +1373,9 @@ namespace ocrf {
 // the bucket histograms (+ per-view visible counts) inside a chain workspace: what a caller that arms the chain
 // (hist_is_zero) has to clear itself before the chain's first kernel
 int* raster_chain_hist(void* workspace, int P, int n_views, size_t* n_words) {
-  RasterWs ws;
-  raster_layout(P, n_views, &ws);
-  *n_words = (size_t)n_views * (kBuckets + 1);
-  return reinterpret_cast<int*>(static_cast<char*>(workspace) + ws.hist);
+  const RasterBufs b = raster_layout(workspace, P, n_views);
+  *n_words = b.hist_words;
+  return b.hist;
 }
 
 int raster_forward_chain(int P, int n_sets, int views_per_set, int H, int W, const float* means3D, const float* colors,
@@ -1345,43 +1402,20 @@ int raster_forward_chain(int P, int n_sets, int views_per_set, int H, int W, con
     return (int)hipErrorInvalidValue;
   const int gx = (W + kTileX - 1) / kTileX, gy = (H + kTileY - 1) / kTileY;
   if (gx > 65535 || gy > 65535) return (int)hipErrorInvalidValue;
-  RasterWs ws;
-  raster_layout(P, n_views, &ws);
-  if (!workspace || workspace_bytes < ws.total) return (int)hipErrorInvalidValue;
-  char* base = static_cast<char*>(workspace);
-  auto* vis_rec = reinterpret_cast<uint4*>(base + ws.vis_rec);
-  auto* rects = reinterpret_cast<Rect*>(base + ws.rects);
-  auto* xy = reinterpret_cast<float2*>(base + ws.xy);
-  auto* conic_o = reinterpret_cast<float4*>(base + ws.conic_o);
-  auto* b_rect = reinterpret_cast<Rect*>(base + ws.b_rect);
-  auto* b_comp = reinterpret_cast<unsigned long long*>(base + ws.b_comp);
-  auto* hist = reinterpret_cast<int*>(base + ws.hist);
-  auto* starts = reinterpret_cast<int*>(base + ws.starts);
-  auto* cursor = reinterpret_cast<int*>(base + ws.cursor);
-  int* st = status ? status : reinterpret_cast<int*>(base + ws.status);
-  const Camera* cams = reinterpret_cast<const Camera*>(cameras);
-
-  int* vis_count = hist + (size_t)n_views * kBuckets;
-  hipError_t e = hipSuccess;
-  if (!hist_is_zero) e = ocrf::zero_async(hist, (size_t)n_views * (kBuckets + 1) * sizeof(int), stream);
+  if (!workspace) return (int)hipErrorInvalidValue;
+  const RasterBufs b = raster_layout(workspace, P, n_views);
+  if (workspace_bytes < b.total) return (int)hipErrorInvalidValue;
+  int* st = status ? status : b.status;
+  const hipError_t e = raster_front_end(b, out_n_contrib ? Lists::kReference : Lists::kTightened, P, n_views, views_per_set,
+                                        W, H, gx, gy, means3D, opacities, scales, scale_modifier, rotations,
+                                        cov3D_precomp, reinterpret_cast<const Camera*>(cameras), view_sel, gate,
+                                        shared_means, radii, tiles_touched, st, hist_is_zero, stream);
   if (e != hipSuccess) return (int)e;
-  const int n_chunks = (P + kChunk - 1) / kChunk, n_pre = (P + kPreChunk - 1) / kPreChunk;
-  const dim3 pgrid(n_chunks, n_views);
-  const dim3 xgrid((unsigned)((n_pre + 7) / 8 * 8 * n_views));         // (chunk, view) pairs, XCD-aware order
-  ocrf::launch(OCRF_K_RASTER_PREPROCESS, raster_preprocess_kernel, xgrid, dim3(kBlock), 0, stream, P, n_views,
-               n_pre, W, H, gx, gy, means3D, opacities, scales, scale_modifier, rotations, cov3D_precomp,
-               cams, vis_rec, vis_count, rects, xy, conic_o, radii, tiles_touched, hist, views_per_set, view_sel, gate,
-               shared_means ? 0 : P, out_n_contrib == nullptr ? 1 : 0);
-  e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
-  ocrf::launch(OCRF_K_RASTER_SCAN, raster_bucket_scan_kernel, dim3(n_views), dim3(kBlock), 0, stream,
-               static_cast<const int*>(hist), starts, cursor, st, gate);
-  e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
-  ocrf::launch(OCRF_K_RASTER_GATHER, raster_scatter_kernel, pgrid, dim3(kBlock), 0, stream, P,
-               static_cast<const uint4*>(vis_rec), static_cast<const int*>(vis_count), cursor, b_rect, b_comp, gate);
-  e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
+  const auto starts = b.starts;      // the names the blend's dispatch macros below use
+  const auto rects = b.rects, b_rect = b.b_rect;
+  const auto b_comp = b.b_comp;
+  const auto xy = b.xy;
+  const auto conic_o = b.conic_o;
   const size_t lds = (size_t)kCapRec * 8 + (size_t)kStage * (16 + 16 + 16);
   const dim3 bgrid(gx, (gy + 1) / 2, n_views);        // one workgroup per vertical pair of tiles
   if (g_stamps) {      // diagnostic build of the same kernel (median depth), with or without the contributor index
@@ -1421,9 +1455,7 @@ int ocrf_diag_raster_stamps(unsigned long long* buf) { g_stamps = buf; return 0;
 
 size_t ocrf_rasterize_workspace_bytes(int P, int n_views) {
   if (P <= 0 || n_views <= 0) return 0;
-  RasterWs ws;
-  raster_layout(P, n_views, &ws);
-  return ws.total;
+  return raster_layout(nullptr, P, n_views).total;
 }
 
 int ocrf_rasterize_forward_sets(int P, int n_sets, int views_per_set, int H, int W, const float* means3D,
@@ -1453,9 +1485,7 @@ int ocrf_rasterize_forward(int P, int n_views, int H, int W, const float* means3
 
 size_t ocrf_rasterize_backward_workspace_bytes(int P, int n_views) {
   if (P <= 0 || n_views <= 0) return 0;
-  RasterWs ws;
-  raster_layout(P, n_views, &ws);
-  return ws.bwd_total;
+  return raster_layout(nullptr, P, n_views).bwd_total;
 }
 
 static int rasterize_backward_impl(int P, int n_views, int H, int W, const float* means3D, const float* colors,
@@ -1474,56 +1504,32 @@ static int rasterize_backward_impl(int P, int n_views, int H, int W, const float
     return (int)hipErrorInvalidValue;
   const int gx = (W + kTileX - 1) / kTileX, gy = (H + kTileY - 1) / kTileY;
   if (gx > 65535 || gy > 65535) return (int)hipErrorInvalidValue;
-  RasterWs ws;
-  raster_layout(P, n_views, &ws);
-  if (!workspace || workspace_bytes < ws.bwd_total) return (int)hipErrorInvalidValue;
-  char* base = static_cast<char*>(workspace);
-  auto* vis_rec = reinterpret_cast<uint4*>(base + ws.vis_rec);
-  auto* rects = reinterpret_cast<Rect*>(base + ws.rects);
-  auto* xy = reinterpret_cast<float2*>(base + ws.xy);
-  auto* conic_o = reinterpret_cast<float4*>(base + ws.conic_o);
-  auto* b_rect = reinterpret_cast<Rect*>(base + ws.b_rect);
-  auto* b_comp = reinterpret_cast<unsigned long long*>(base + ws.b_comp);
-  auto* hist = reinterpret_cast<int*>(base + ws.hist);
-  auto* starts = reinterpret_cast<int*>(base + ws.starts);
-  auto* cursor = reinterpret_cast<int*>(base + ws.cursor);
-  int* st = reinterpret_cast<int*>(base + ws.status);
-  auto* acc = reinterpret_cast<float*>(base + ws.acc);
-  auto* radii = reinterpret_cast<int*>(base + ws.radii);
+  if (!workspace) return (int)hipErrorInvalidValue;
+  const RasterBufs b = raster_layout(workspace, P, n_views);
+  if (workspace_bytes < b.bwd_total) return (int)hipErrorInvalidValue;
   const Camera* cams = reinterpret_cast<const Camera*>(cameras);
-  // rebuild the bucket-ordered lists exactly as the forward did (same kernels, same inputs)
-  int* vis_count = hist + (size_t)n_views * kBuckets;
-  hipError_t e = ocrf::zero_async(hist, (size_t)n_views * (kBuckets + 1) * sizeof(int), stream);
-  if (e == hipSuccess) e = ocrf::zero_async(acc, (size_t)n_views * P * 9 * sizeof(float), stream);
-  if (e != hipSuccess) return (int)e;
-  const int n_chunks = (P + kChunk - 1) / kChunk, n_pre = (P + kPreChunk - 1) / kPreChunk;
-  const dim3 pgrid(n_chunks, n_views);
-  const dim3 xgrid((unsigned)((n_pre + 7) / 8 * 8 * n_views));
-  hipLaunchKernelGGL(raster_preprocess_kernel, xgrid, dim3(kBlock), 0, stream, P, n_views, n_pre, W, H, gx, gy,
-                     means3D, opacities, scales, scale_modifier, rotations, cov3D_precomp, cams, vis_rec,
-                     vis_count, rects, xy, conic_o, radii, (unsigned*)nullptr, hist, n_views, (const int*)nullptr,
-                     (const int*)nullptr, P, 0);
-  hipLaunchKernelGGL(raster_bucket_scan_kernel, dim3(n_views), dim3(kBlock), 0, stream, static_cast<const int*>(hist),
-                     starts, cursor, st, (const int*)nullptr);
-  hipLaunchKernelGGL(raster_scatter_kernel, pgrid, dim3(kBlock), 0, stream, P, static_cast<const uint4*>(vis_rec),
-                     static_cast<const int*>(vis_count), cursor, b_rect, b_comp, (const int*)nullptr);
-  e = hipGetLastError();
+  hipError_t e = ocrf::zero_async(b.acc, (size_t)n_views * P * 9 * sizeof(float), stream);
+  // the forward's lists again: one set of n_views views, no selection, no gate, its radii into the workspace
+  if (e == hipSuccess)
+    e = raster_front_end(b, Lists::kReference, P, n_views, n_views, W, H, gx, gy, means3D, opacities, scales,
+                         scale_modifier, rotations, cov3D_precomp, cams, nullptr, nullptr, false, b.radii, nullptr,
+                         b.status, false, stream);
   if (e != hipSuccess) return (int)e;
   BwdArgs bw;
   bw.dL_dcolor = dL_dcolor; bw.fwd_color = fwd_color; bw.fwd_final_T = fwd_final_T;
-  bw.fwd_n_contrib = fwd_n_contrib; bw.acc = acc;
+  bw.fwd_n_contrib = fwd_n_contrib; bw.acc = b.acc;
   const size_t lds = (size_t)kCapRec * 8 + (size_t)kStage * (16 + 16 + 16 + 4 + 36);
   ocrf::launch(OCRF_K_RASTER_BLEND_BWD, raster_blend_kernel<false, true, true>, dim3(gx, (gy + 1) / 2, n_views),
-               dim3(kBlock), lds, stream, (unsigned long long*)nullptr, P, W, H, gy, static_cast<const int*>(starts),
-               static_cast<const Rect*>(rects), static_cast<const Rect*>(b_rect),
-               static_cast<const unsigned long long*>(b_comp),
-               static_cast<const float2*>(xy), static_cast<const float4*>(conic_o), colors, bg, (float*)nullptr,
-               (float*)nullptr, (float*)nullptr, (unsigned*)nullptr, st, bw, n_views, (int*)nullptr);
+               dim3(kBlock), lds, stream, (unsigned long long*)nullptr, P, W, H, gy, static_cast<const int*>(b.starts),
+               static_cast<const Rect*>(b.rects), static_cast<const Rect*>(b.b_rect),
+               static_cast<const unsigned long long*>(b.b_comp),
+               static_cast<const float2*>(b.xy), static_cast<const float4*>(b.conic_o), colors, bg, (float*)nullptr,
+               (float*)nullptr, (float*)nullptr, (unsigned*)nullptr, b.status, bw, n_views, (int*)nullptr);
   e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
   ocrf::launch(OCRF_K_RASTER_PRE_BWD, raster_preprocess_backward_kernel, dim3((P + kBlock - 1) / kBlock), dim3(kBlock),
                0, stream, P, n_views, W, H, means3D, scales, scale_modifier, rotations, cov3D_precomp, cams,
-               static_cast<const int*>(radii), static_cast<const float*>(acc), dL_dmeans3D, dL_dcolors, dL_dopacity,
+               static_cast<const int*>(b.radii), static_cast<const float*>(b.acc), dL_dmeans3D, dL_dcolors, dL_dopacity,
                dL_dscales, dL_drotations, dL_dcov3D, dL_dmeans2D);
   return (int)hipGetLastError();
 }

@@ -109,6 +109,13 @@ def sh_to_rgb_backward(means3D, campos, shs, degree, clamped, dL_dcolors, dL_dme
     return dL_dmeans3D, d_sh
 
 
+def _camera_rows(packed_cameras, viewmatrices, projmatrices, tanfovx, tanfovy, H, W, dev):
+    """The (V,36) camera rows of a call: the packed ones if given, else ``pack_cameras`` of the matrices."""
+    if packed_cameras is not None:
+        return packed_cameras
+    return pack_cameras(viewmatrices, projmatrices, tanfovx, tanfovy, H, W, dev)
+
+
 def rasterize_views_backward(grad_color, fwd, means3D, colors, opacities, scales, rotations, viewmatrices,
                              projmatrices, tanfovx, tanfovy, image_height, image_width, bg, scale_modifier=1.0,
                              want_means2D=False, packed_cameras=None, cov3D_precomp=None):
@@ -117,36 +124,58 @@ def rasterize_views_backward(grad_color, fwd, means3D, colors, opacities, scales
     (P,3), ``opacities`` (P,1), ``scales`` (P,3), ``rotations`` (P,4) [, ``means2D`` (V,P,3)]; with
     ``cov3D_precomp`` (P,6) (``scales`` / ``rotations`` None) ``cov3D`` (P,6) instead of the last two
     (backward.cu:346-396 without computeCov3D's backward)."""
-    if cov3D_precomp is not None:
-        return _backward_cov3d(grad_color, fwd, means3D, colors, opacities, cov3D_precomp, viewmatrices, projmatrices,
-                               tanfovx, tanfovy, image_height, image_width, bg, want_means2D, packed_cameras)
-    _lib.require_cuda(means3D, colors, opacities, scales, rotations, grad_color)
+    has_cov = cov3D_precomp is not None
+    _lib.require_cuda(means3D, colors, opacities, *((cov3D_precomp,) if has_cov else (scales, rotations)), grad_color)
     dev = means3D.device
     P = means3D.size(0)
     H, W = int(image_height), int(image_width)
-    cams = packed_cameras if packed_cameras is not None else \
-        pack_cameras(viewmatrices, projmatrices, tanfovx, tanfovy, H, W, dev)
+    cams = _camera_rows(packed_cameras, viewmatrices, projmatrices, tanfovx, tanfovy, H, W, dev)
     V = cams.size(0)
     g = _f32c(grad_color).reshape(V, 3, H, W)
-    means3D, colors, opac = _f32c(means3D), _f32c(colors), _f32c(opacities).reshape(-1)
-    sc, rot, bg = _f32c(scales), _f32c(rotations), _f32c(bg).reshape(3)
+    means3D, colors, opac, bg = _f32c(means3D), _f32c(colors), _f32c(opacities).reshape(-1), _f32c(bg).reshape(3)
     fc, ft, fn = fwd['color'].contiguous(), fwd['final_T'].contiguous(), fwd['n_contrib'].contiguous()
     if tuple(fc.shape) != (V, 3, H, W) or tuple(ft.shape) != (V, H, W) or tuple(fn.shape) != (V, H, W):
         raise RuntimeError('rasterize_views_backward: forward outputs do not match the view batch')
     out = dict(means3D=torch.empty(P, 3, device=dev), colors=torch.empty(P, 3, device=dev),
-               opacities=torch.empty(P, 1, device=dev), scales=torch.empty(P, 3, device=dev),
-               rotations=torch.empty(P, 4, device=dev))
+               opacities=torch.empty(P, 1, device=dev))
+    if has_cov:
+        out['cov3D'] = torch.empty(P, 6, device=dev)
+    else:
+        out['scales'], out['rotations'] = torch.empty(P, 3, device=dev), torch.empty(P, 4, device=dev)
     m2d = torch.empty(V, P, 3, device=dev) if want_means2D else None
-    if P == 0:
-        if m2d is not None:
-            out['means2D'] = m2d
-        return out
-    ws = _lib.workspace.get(dev, _lib.lib().ocrf_rasterize_backward_workspace_bytes(P, V), 'raster')
-    _lib.launch('ocrf_rasterize_backward', dev, P, V, H, W, means3D, colors, opac, sc, float(scale_modifier), rot, cams, bg,
-                fc, ft, fn, g, out['means3D'], out['colors'], out['opacities'], out['scales'], out['rotations'], m2d,
-                ws, ws.numel())
     if m2d is not None:
         out['means2D'] = m2d
+    if P == 0:
+        return out
+    ws = _lib.workspace.get(dev, _lib.lib().ocrf_rasterize_backward_workspace_bytes(P, V), 'raster')
+    shared = (cams, bg, fc, ft, fn, g, out['means3D'], out['colors'], out['opacities'])
+    if has_cov:
+        _lib.launch('ocrf_rasterize_backward_cov3d', dev, P, V, H, W, means3D, colors, opac,
+                    _f32c(cov3D_precomp).reshape(P, 6), *shared, out['cov3D'], m2d, ws, ws.numel())
+    else:
+        _lib.launch('ocrf_rasterize_backward', dev, P, V, H, W, means3D, colors, opac, _f32c(scales), float(scale_modifier),
+                    _f32c(rotations), *shared, out['scales'], out['rotations'], m2d, ws, ws.numel())
+    return out
+
+
+def _forward(entry, dims, means3D, colors, opac, sc, scale_modifier, rot, cov, cams, bg, H, W, depth_mode, want_n_contrib,
+             want_tiles_touched, workspace_tag):
+    """Outputs, status word, workspace and launch of a forward entry point whose leading arguments are ``dims`` =
+    (P, [sets,] views): fresh tensors over the ``cams.size(0)`` rendered views."""
+    dev, P, NV = means3D.device, dims[0], cams.size(0)
+    out = dict(color=torch.empty(NV, 3, H, W, device=dev), depth=torch.empty(NV, 1, H, W, device=dev),
+               final_T=torch.empty(NV, H, W, device=dev), radii=torch.empty(NV, P, dtype=torch.int32, device=dev))
+    if want_n_contrib:
+        out['n_contrib'] = torch.empty(NV, H, W, dtype=torch.int32, device=dev)
+    tt = torch.empty(NV, P, dtype=torch.int32, device=dev) if want_tiles_touched else None
+    status = torch.empty(1, dtype=torch.int32, device=dev)      # zeroed on the device by the bucket scan kernel
+    ws = _lib.workspace.get(dev, _lib.lib().ocrf_rasterize_workspace_bytes(P, NV), workspace_tag)
+    _lib.launch(entry, dev, *dims, H, W, means3D, colors, opac, sc, float(scale_modifier), rot, cov, cams, bg,
+                {'median': 0, 'mean': 1}[depth_mode], out['color'], out['depth'], out['final_T'], out.get('n_contrib'),
+                out['radii'], tt, status, ws, ws.numel())
+    if tt is not None:
+        out['tiles_touched'] = tt
+    out['status'] = status     # device int, informational: 2 = the exact streaming path ran for some tile
     return out
 
 
@@ -166,34 +195,16 @@ def rasterize_views(means3D, colors, opacities, scales, rotations, viewmatrices,
     _lib.require_cuda(means3D, colors, opacities, bg)
     if means3D.dim() != 2 or means3D.size(1) != 3:
         raise RuntimeError('means3D must have dimensions (num_points, 3)')     # rasterize_points.cu:57-59
-    dev = means3D.device
-    P = means3D.size(0)
     H, W = int(image_height), int(image_width)
-    cams = packed_cameras if packed_cameras is not None else \
-        pack_cameras(viewmatrices, projmatrices, tanfovx, tanfovy, H, W, dev)              # (V,36)
+    cams = _camera_rows(packed_cameras, viewmatrices, projmatrices, tanfovx, tanfovy, H, W, means3D.device)   # (V,36)
     _lib.require_cuda(cams)
-    V = cams.size(0)
-    means3D, colors, opac = _f32c(means3D), _f32c(colors), _f32c(opacities).reshape(-1)
     if cov3D_precomp is not None and cov3D_precomp.numel() > 0:
         cov, sc, rot = _f32c(cov3D_precomp), None, None
     else:
         cov, sc, rot = None, _f32c(scales), _f32c(rotations)
-    bg = _f32c(bg).reshape(3)
-    out = dict(color=torch.empty(V, 3, H, W, device=dev), depth=torch.empty(V, 1, H, W, device=dev),
-               final_T=torch.empty(V, H, W, device=dev),
-               radii=torch.empty(V, max(P, 0), dtype=torch.int32, device=dev))
-    if want_n_contrib:
-        out['n_contrib'] = torch.empty(V, H, W, dtype=torch.int32, device=dev)
-    tt = torch.empty(V, P, dtype=torch.int32, device=dev) if want_tiles_touched else None
-    status = torch.empty(1, dtype=torch.int32, device=dev)      # zeroed on the device by the bucket scan kernel
-    ws = _lib.workspace.get(dev, _lib.lib().ocrf_rasterize_workspace_bytes(P, V), workspace_tag)
-    _lib.launch('ocrf_rasterize_forward', dev, P, V, H, W, means3D, colors, opac, sc, float(scale_modifier), rot, cov, cams,
-                bg, {'median': 0, 'mean': 1}[depth_mode], out['color'], out['depth'], out['final_T'], out.get('n_contrib'),
-                out['radii'], tt, status, ws, ws.numel())
-    if tt is not None:
-        out['tiles_touched'] = tt
-    out['status'] = status     # device int, informational: 2 = the exact streaming path ran for some tile
-    return out
+    return _forward('ocrf_rasterize_forward', (means3D.size(0), cams.size(0)), _f32c(means3D), _f32c(colors),
+                    _f32c(opacities).reshape(-1), sc, scale_modifier, rot, cov, cams, _f32c(bg).reshape(3), H, W, depth_mode,
+                    want_n_contrib, want_tiles_touched, workspace_tag)
 
 
 def rasterize_sets(means3D, colors, opacities, scales, rotations, packed_cameras, image_height, image_width, bg,
@@ -206,52 +217,14 @@ def rasterize_sets(means3D, colors, opacities, scales, rotations, packed_cameras
     _lib.require_cuda(means3D, colors, opacities, scales, rotations, packed_cameras, bg)
     if means3D.dim() != 3 or means3D.size(2) != 3:
         raise RuntimeError('means3D must have dimensions (num_sets, num_points, 3)')
-    dev = means3D.device
     S, P = means3D.size(0), means3D.size(1)
     NV = packed_cameras.size(0)
     if NV % S:
         raise RuntimeError('packed_cameras rows must be a multiple of the number of sets')
-    H, W = int(image_height), int(image_width)
-    means3D, colors, opac = _f32c(means3D), _f32c(colors), _f32c(opacities).reshape(S, P)
-    sc, rot, bg, cams = _f32c(scales), _f32c(rotations), _f32c(bg).reshape(3), _f32c(packed_cameras)
-    out = dict(color=torch.empty(NV, 3, H, W, device=dev), depth=torch.empty(NV, 1, H, W, device=dev),
-               final_T=torch.empty(NV, H, W, device=dev), radii=torch.empty(NV, P, dtype=torch.int32, device=dev))
-    if want_n_contrib:
-        out['n_contrib'] = torch.empty(NV, H, W, dtype=torch.int32, device=dev)
-    status = torch.empty(1, dtype=torch.int32, device=dev)
-    ws = _lib.workspace.get(dev, _lib.lib().ocrf_rasterize_workspace_bytes(P, NV), workspace_tag)
-    _lib.launch('ocrf_rasterize_forward_sets', dev, P, S, NV // S, H, W, means3D, colors, opac, sc, float(scale_modifier),
-                rot, None, cams, bg, {'median': 0, 'mean': 1}[depth_mode], out['color'], out['depth'], out['final_T'],
-                out.get('n_contrib'), out['radii'], None, status, ws, ws.numel())
-    out['status'] = status
-    return out
-
-
-def _backward_cov3d(grad_color, fwd, means3D, colors, opacities, cov3D, viewmatrices, projmatrices, tanfovx, tanfovy,
-                    image_height, image_width, bg, want_means2D, packed_cameras):
-    _lib.require_cuda(means3D, colors, opacities, cov3D, grad_color)
-    dev = means3D.device
-    P = means3D.size(0)
-    H, W = int(image_height), int(image_width)
-    cams = packed_cameras if packed_cameras is not None else \
-        pack_cameras(viewmatrices, projmatrices, tanfovx, tanfovy, H, W, dev)
-    V = cams.size(0)
-    g = _f32c(grad_color).reshape(V, 3, H, W)
-    means3D, colors, opac = _f32c(means3D), _f32c(colors), _f32c(opacities).reshape(-1)
-    cov, bg = _f32c(cov3D).reshape(P, 6), _f32c(bg).reshape(3)
-    fc, ft, fn = fwd['color'].contiguous(), fwd['final_T'].contiguous(), fwd['n_contrib'].contiguous()
-    if tuple(fc.shape) != (V, 3, H, W) or tuple(ft.shape) != (V, H, W) or tuple(fn.shape) != (V, H, W):
-        raise RuntimeError('rasterize_views_backward: forward outputs do not match the view batch')
-    out = dict(means3D=torch.empty(P, 3, device=dev), colors=torch.empty(P, 3, device=dev),
-               opacities=torch.empty(P, 1, device=dev), cov3D=torch.empty(P, 6, device=dev))
-    m2d = torch.empty(V, P, 3, device=dev) if want_means2D else None
-    if P:
-        ws = _lib.workspace.get(dev, _lib.lib().ocrf_rasterize_backward_workspace_bytes(P, V), 'raster')
-        _lib.launch('ocrf_rasterize_backward_cov3d', dev, P, V, H, W, means3D, colors, opac, cov, cams, bg, fc, ft, fn, g,
-                    out['means3D'], out['colors'], out['opacities'], out['cov3D'], m2d, ws, ws.numel())
-    if m2d is not None:
-        out['means2D'] = m2d
-    return out
+    return _forward('ocrf_rasterize_forward_sets', (P, S, NV // S), _f32c(means3D), _f32c(colors),
+                    _f32c(opacities).reshape(S, P), _f32c(scales), scale_modifier, _f32c(rotations), None,
+                    _f32c(packed_cameras), _f32c(bg).reshape(3), int(image_height), int(image_width), depth_mode,
+                    want_n_contrib, False, workspace_tag)
 
 
 class _RasterizeGaussians(torch.autograd.Function):
@@ -263,27 +236,24 @@ class _RasterizeGaussians(torch.autograd.Function):
         if ctx.has_sh:
             # colours of THIS view from the SH coefficients (forward.cu:240-247); everything after is the ordinary pipeline
             colors_precomp, sh_clamped = sh_to_rgb(means3D, rs.campos, sh, rs.sh_degree)
+        ctx.has_cov = cov3Ds_precomp is not None and cov3Ds_precomp.numel() > 0
         out = rasterize_views(means3D, colors_precomp, opacities, scales, rotations,
                               rs.viewmatrix.reshape(1, 4, 4), rs.projmatrix.reshape(1, 4, 4),
                               float(rs.tanfovx), float(rs.tanfovy), rs.image_height, rs.image_width,
-                              rs.bg, float(rs.scale_modifier),
-                              cov3Ds_precomp if cov3Ds_precomp is not None and cov3Ds_precomp.numel() else None,
+                              rs.bg, float(rs.scale_modifier), cov3Ds_precomp if ctx.has_cov else None,
                               want_n_contrib=any(ctx.needs_input_grad))      # only the backward reads it
         color, radii, depth = out['color'][0], out['radii'][0], out['depth'][0]
         ctx.mark_non_differentiable(radii, depth)
         ctx.raster_settings = rs
-        ctx.has_cov = cov3Ds_precomp is not None and cov3Ds_precomp.numel() > 0
         # the forward's outputs are saved through autograd (not as plain attributes): the backward
         # rebuilds S = C_out - T_final * bg from them, so an in-place edit of the rendered image
         # (clamp_, mul_) must raise instead of silently changing the gradients.  The same holds for the SH
-        # coefficients and their clamp mask, which the backward of the colours reads: last in the tuple
+        # coefficients and their clamp mask, which the backward of the colours reads: last in the tuple.
+        # The covariance is saved in the shape it came in: (cov3D,) or (scales, rotations)
+        shape = (cov3Ds_precomp,) if ctx.has_cov else (scales, rotations)
         sh_saved = (sh, sh_clamped) if ctx.has_sh else ()
-        if ctx.has_cov:
-            ctx.save_for_backward(means3D, colors_precomp, opacities, cov3Ds_precomp, color, out['final_T'],
-                                  out.get('n_contrib'), *sh_saved)
-        else:
-            ctx.save_for_backward(means3D, colors_precomp, opacities, scales, rotations, color, out['final_T'],
-                                  out.get('n_contrib'), *sh_saved)
+        ctx.save_for_backward(means3D, colors_precomp, opacities, *shape, color, out['final_T'], out.get('n_contrib'),
+                              *sh_saved)
         return color, radii, depth
 
     @staticmethod
@@ -301,38 +271,32 @@ class _RasterizeGaussians(torch.autograd.Function):
         """Gradient tuple in the reference's order (diff_gaussian_rasterization/__init__.py:96-149):
         means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings."""
         rs = ctx.raster_settings
-        if ctx.has_cov:
-            means3D, colors, opacities, cov, fwd_color, fwd_T, fwd_n = ctx.saved_tensors[:7]
-            fwd = dict(color=fwd_color.unsqueeze(0), final_T=fwd_T, n_contrib=fwd_n)
-            g = rasterize_views_backward(grad_color.unsqueeze(0), fwd, means3D, colors, opacities, None, None,
-                                         rs.viewmatrix.reshape(1, 4, 4), rs.projmatrix.reshape(1, 4, 4),
-                                         float(rs.tanfovx), float(rs.tanfovy), rs.image_height, rs.image_width, rs.bg,
-                                         want_means2D=True, cov3D_precomp=cov)
-            d_means, d_sh, d_col = _RasterizeGaussians._sh_grads(ctx, means3D, g)
-            grads = (d_means, g['means2D'][0], d_sh, d_col, g['opacities'].reshape(opacities.shape),
-                     None, None, g['cov3D'].reshape(cov.shape), None)
-            return tuple(v if need else None for v, need in zip(grads, ctx.needs_input_grad))
-        means3D, colors, opacities, scales, rotations, fwd_color, fwd_T, fwd_n = ctx.saved_tensors[:8]
+        n = 4 if ctx.has_cov else 5
+        means3D, colors, opacities, *shape = ctx.saved_tensors[:n]
+        scales, rotations, cov = (None, None, *shape) if ctx.has_cov else (*shape, None)
+        fwd_color, fwd_T, fwd_n = ctx.saved_tensors[n:n + 3]
         fwd = dict(color=fwd_color.unsqueeze(0), final_T=fwd_T, n_contrib=fwd_n)
         g = rasterize_views_backward(grad_color.unsqueeze(0), fwd, means3D, colors, opacities, scales, rotations,
                                      rs.viewmatrix.reshape(1, 4, 4), rs.projmatrix.reshape(1, 4, 4),
                                      float(rs.tanfovx), float(rs.tanfovy), rs.image_height, rs.image_width, rs.bg,
-                                     float(rs.scale_modifier), want_means2D=True)
+                                     float(rs.scale_modifier), want_means2D=True, cov3D_precomp=cov)
         d_means, d_sh, d_col = _RasterizeGaussians._sh_grads(ctx, means3D, g)
         grads = (d_means, g['means2D'][0], d_sh, d_col, g['opacities'].reshape(opacities.shape),
-                 g['scales'], g['rotations'], None, None)
+                 g.get('scales'), g.get('rotations'), g['cov3D'].reshape(cov.shape) if ctx.has_cov else None, None)
         # inputs that were not tensors needing a gradient (means2D=None from render()) must get None
         return tuple(v if need else None for v, need in zip(grads, ctx.needs_input_grad))
 
 
 class _RasterizeViews(torch.autograd.Function):
-    """Differentiable batched render: colour (V,3,H,W) w.r.t. the Gaussian parameters, gradients
-    summed over the views in one backward launch sequence."""
+    """Differentiable batched render over packed camera rows ((V,36) of ``pack_cameras``, on the device: nothing of the
+    call or its backward touches the host's copy of the calibration): colour (V,3,H,W) w.r.t. the Gaussian
+    parameters, gradients summed over the views in one backward launch sequence."""
 
     @staticmethod
-    def forward(ctx, means3D, colors, opacities, scales, rotations, cam):
-        out = rasterize_views(means3D, colors, opacities, scales, rotations, *cam)
-        ctx.cam = cam
+    def forward(ctx, means3D, colors, opacities, scales, rotations, packed, H, W, bg, scale_modifier):
+        out = rasterize_views(means3D, colors, opacities, scales, rotations, None, None, None, None, H, W, bg,
+                              scale_modifier, packed_cameras=packed)
+        ctx.cam = (packed, H, W, bg, scale_modifier)
         ctx.save_for_backward(means3D, colors, opacities, scales, rotations, out['color'], out['final_T'], out['n_contrib'])
         ctx.mark_non_differentiable(out['depth'], out['radii'], out['final_T'])
         return out['color'], out['depth'], out['final_T'], out['radii']
@@ -340,49 +304,28 @@ class _RasterizeViews(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_color, _d, _t, _r):
         means3D, colors, opacities, scales, rotations, fwd_color, fwd_T, fwd_n = ctx.saved_tensors
+        packed, H, W, bg, scale_modifier = ctx.cam
         fwd = dict(color=fwd_color, final_T=fwd_T, n_contrib=fwd_n)
-        g = rasterize_views_backward(grad_color, fwd, means3D, colors, opacities, scales, rotations, *ctx.cam)
-        return g['means3D'], g['colors'], g['opacities'].reshape(opacities.shape), g['scales'], g['rotations'], None
+        g = rasterize_views_backward(grad_color, fwd, means3D, colors, opacities, scales, rotations, None, None, None, None,
+                                     H, W, bg, scale_modifier, packed_cameras=packed)
+        grads = (g['means3D'], g['colors'], g['opacities'].reshape(opacities.shape), g['scales'], g['rotations'])
+        return tuple(v if n else None for v, n in zip(grads, ctx.needs_input_grad)) + (None,) * 5
 
 
 def rasterize_views_autograd(means3D, colors, opacities, scales, rotations, viewmatrices, projmatrices, tanfovx,
                              tanfovy, image_height, image_width, bg, scale_modifier=1.0):
     """``rasterize_views`` with autograd through the colour output: returns (color (V,3,H,W),
     depth (V,1,H,W), final_T (V,H,W), radii (V,P))."""
-    cam = (viewmatrices, projmatrices, tanfovx, tanfovy, image_height, image_width, bg, scale_modifier)
-    return _RasterizeViews.apply(means3D, colors, opacities, scales, rotations, cam)
-
-
-class _RasterizePacked(torch.autograd.Function):
-    """``_RasterizeViews`` for cameras already packed on the device ((V,36) rows of ``pack_cameras``): nothing of the call
-    touches the host's copy of the calibration (no matrix uploads, no focal arithmetic per call)."""
-
-    @staticmethod
-    def forward(ctx, means3D, colors, opacities, scales, rotations, packed, H, W, bg):
-        out = rasterize_views(means3D, colors, opacities, scales, rotations, None, None, None, None, H, W, bg,
-                              packed_cameras=packed)
-        ctx.cam = (packed, H, W, bg)
-        ctx.save_for_backward(means3D, colors, opacities, scales, rotations, out['color'], out['final_T'], out['n_contrib'])
-        ctx.mark_non_differentiable(out['depth'], out['radii'], out['final_T'])
-        return out['color'], out['depth'], out['final_T'], out['radii']
-
-    @staticmethod
-    def backward(ctx, grad_color, _d, _t, _r):
-        means3D, colors, opacities, scales, rotations, fwd_color, fwd_T, fwd_n = ctx.saved_tensors
-        packed, H, W, bg = ctx.cam
-        fwd = dict(color=fwd_color, final_T=fwd_T, n_contrib=fwd_n)
-        g = rasterize_views_backward(grad_color, fwd, means3D, colors, opacities, scales, rotations, None, None, None, None,
-                                     H, W, bg, packed_cameras=packed)
-        need = ctx.needs_input_grad
-        grads = (g['means3D'], g['colors'], g['opacities'].reshape(opacities.shape), g['scales'], g['rotations'])
-        return tuple(v if n else None for v, n in zip(grads, need)) + (None, None, None, None)
+    H, W = int(image_height), int(image_width)
+    packed = pack_cameras(viewmatrices, projmatrices, tanfovx, tanfovy, H, W, means3D.device)
+    return _RasterizeViews.apply(means3D, colors, opacities, scales, rotations, packed, H, W, bg, scale_modifier)
 
 
 def rasterize_packed_autograd(means3D, colors, opacities, scales, rotations, packed_cameras, image_height, image_width, bg):
     """``rasterize_views_autograd`` with the cameras given as packed device rows (V,36):
     -> (color (V,3,H,W), depth (V,1,H,W), final_T (V,H,W), radii (V,P)), autograd through the colour."""
-    return _RasterizePacked.apply(means3D, colors, opacities, scales, rotations, packed_cameras, int(image_height),
-                                  int(image_width), bg)
+    return _RasterizeViews.apply(means3D, colors, opacities, scales, rotations, packed_cameras, int(image_height),
+                                 int(image_width), bg, 1.0)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,

@@ -263,3 +263,58 @@ def test_candidate_list_size_queries_are_host_only():
     assert lib.ocrf_raster_plan_bins_bytes(33, 256, 704, 4, 2, ctypes.c_long(1000)) == 0                # > 32 views
     assert lib.ocrf_raster_plan_bins_workspace_bytes(520000, 12, 256, 704, 4, 2, ctypes.c_long(1_500_000)) > 4 * 1_500_000
     assert lib.ocrf_raster_plan_bins_workspace_bytes(520000, 12, 256, 704, 0, 2, ctypes.c_long(1_500_000)) == 0
+
+
+def _raster_entry(name, **change):
+    """Call one rasteriser entry point with arguments that pass every check except what ``change`` replaces.  Pointers are
+    small integers: a refused call dereferences none of them."""
+    L = _lib.lib()
+    P, V, H, W = 100, 2, 32, 48
+    p = ctypes.c_void_p(4096)
+    backward = 'backward' in name
+    size = (L.ocrf_rasterize_backward_workspace_bytes if backward else L.ocrf_rasterize_workspace_bytes)(P, V)
+    a = dict(P=P, n_sets=1, n_views=V, H=H, W=W, scales=p, rotations=p, cov3D=None, depth_mode=0, dL_dcov3D=p, workspace=p,
+             workspace_bytes=size)
+    a.update(change)
+    ws = (a['workspace'], ctypes.c_size_t(a['workspace_bytes']), None)
+    mod = ctypes.c_float(1.0)
+    if name == 'ocrf_rasterize_backward':
+        return L.ocrf_rasterize_backward(a['P'], a['n_views'], a['H'], a['W'], p, p, p, a['scales'], mod, a['rotations'],
+                                         p, p, p, p, p, p, p, p, p, p, p, None, *ws)
+    if name == 'ocrf_rasterize_backward_cov3d':
+        return L.ocrf_rasterize_backward_cov3d(a['P'], a['n_views'], a['H'], a['W'], p, p, p, p, p, p, p, p, p, p, p, p, p,
+                                               a['dL_dcov3D'], None, *ws)
+    dims = (a['P'], a['n_sets'], a['n_views']) if name == 'ocrf_rasterize_forward_sets' else (a['P'], a['n_views'])
+    return getattr(L, name)(*dims, a['H'], a['W'], p, p, p, a['scales'], mod, a['rotations'], a['cov3D'], p, p,
+                            a['depth_mode'], p, p, p, p, p, None, p, *ws)
+
+
+def test_rasteriser_entry_points_refuse_bad_arguments_at_the_c_boundary():
+    """Every case is refused by the argument checks, before anything is enqueued: hipErrorInvalidValue even on a machine
+    with no device.  (P = 0 is not among them: the forward answers it with zero-fills.)"""
+    L = _lib.lib()
+    invalid = 1
+    forwards = ('ocrf_rasterize_forward', 'ocrf_rasterize_forward_sets')
+    every = forwards + ('ocrf_rasterize_backward', 'ocrf_rasterize_backward_cov3d')
+    for name in every:
+        size = (L.ocrf_rasterize_backward_workspace_bytes if 'backward' in name else L.ocrf_rasterize_workspace_bytes)(100, 2)
+        assert _raster_entry(name, workspace=None) == invalid, name
+        assert _raster_entry(name, workspace_bytes=size - 1) == invalid, name
+        assert _raster_entry(name, W=16 * 65535 + 1, H=16) == invalid, name         # 65536 tiles wide
+    for name in forwards + ('ocrf_rasterize_backward',):
+        assert _raster_entry(name, rotations=None) == invalid, name                 # scales without rotations
+    assert _raster_entry('ocrf_rasterize_backward_cov3d', dL_dcov3D=None) == invalid
+    for name in forwards:
+        assert _raster_entry(name, depth_mode=2) == invalid, name
+    assert _raster_entry('ocrf_rasterize_forward_sets', n_sets=0) == invalid
+
+
+def test_rasteriser_workspace_sizes_are_those_of_the_layout():
+    """The two size queries at (P, V).  The literals are measurements of the build before the front end was stated once
+    (one carve for forward, backward and the armed chain): the layout's offsets and both totals must not move."""
+    L = _lib.lib()
+    measured = {(1, 1): (100608, 101120), (1025, 2): (329984, 412416), (2049, 3): (690432, 936704),
+                (100000, 12): (77980416, 125980416)}
+    for (P, V), (forward, backward) in measured.items():
+        assert L.ocrf_rasterize_workspace_bytes(P, V) == forward, (P, V)
+        assert L.ocrf_rasterize_backward_workspace_bytes(P, V) == backward, (P, V)
