@@ -13,7 +13,6 @@
 
 #include <algorithm>
 
-#include "hoa_gate.h"
 #include "launch.h"
 #include "ocrf_hip.h"
 
@@ -64,20 +63,11 @@ __global__ __launch_bounds__(kBlock) void hoa_channel_stats_kernel(const float* 
 // FAST (VEC = 4, X <= 256): the statistic rows are staged as 16-byte words, one row = 64 word slots (no index
 // divisions: the generic staging spends ~ 80 integer divisions per thread, more than the convolution), at clamped
 // addresses without a branch; a staged row carries 4 zero columns on the left (3 would do: 4 keeps the words aligned).
-// D1 (with FAST): opacity_bev does not exist yet — it is HOA-2's output conv (view_transformer_ocrf.py:516) of the gated
-// decoder1 activations, folded in here: `d1` (B,4,Y,X) + decoder1's per-tile channel maxima `d1_pm` -> the
-// HeightAttention gate in the prologue (hoa_gate.h), opacity = out_b + sum_c fma(d1_c g_c, out_w_c, .) per pixel in the
-// arithmetic of hoa_v2b_out_kernel; channel group 0 also writes it to `opacity_out`.  One launch (and its ~ 4.5 us floor
-// plus the gap in front of it) less on the step's main chain; same bits.  d1_w: out_w[4], out_b, gate w1[4], w2[4].
-struct MaskGateD1 {
-  const float* d1; const float* pm; const float* out_w; const float* out_b; const float* g_w1; const float* g_w2;
-  float* opacity_out; int tiles;
-};
-template <int VEC, int KT, bool FAST = false, bool D1 = false>
+template <int VEC, int KT, bool FAST = false>
 __global__ __launch_bounds__(kBlock) void hoa_mask_gate_kernel(
     const float* __restrict__ x, const float* __restrict__ stats, const float* __restrict__ opacity_bev,
     const float* __restrict__ conv_w, int k_rt, int C, int Y, int X, int groups, int n_rows,
-    float* __restrict__ mask, float* __restrict__ gated, MaskGateD1 dd) {
+    float* __restrict__ mask, float* __restrict__ gated) {
   OCRF_MAIN_CHAIN_PRIO();
   const int k = KT ? KT : k_rt;
   const int nt = (int)blockDim.x;              // 256, or fewer for more and shorter workgroups (ocrf_hoa_opacity_mask_gate)
@@ -106,21 +96,6 @@ __global__ __launch_bounds__(kBlock) void hoa_mask_gate_kernel(
 #pragma unroll
       for (int u = 0; u < 5; ++u) first[u] = *reinterpret_cast<const float4*>(pe + (long)(c0_e + u) * plane);
     }
-  }
-  // D1: decoder1's activations of this thread's four pixels, its per-tile maxima and the 13 weights, all in flight now
-  __shared__ __attribute__((aligned(16))) float s_red[16 * 4];
-  __shared__ float s_g[4], s_ow[16];
-  float4 d1v[D1 ? 4 : 1];
-  float4 pmv[hoa_gate::kPmRounds];
-  float owv = 0.f;
-  if constexpr (D1) {
-    const long pc = pix_e < plane ? pix_e : plane - VEC;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) d1v[c] = *reinterpret_cast<const float4*>(dd.d1 + ((long)b * 4 + c) * plane + pc);
-    hoa_gate::pm_issue<4>(dd.pm, b, dd.tiles, (int)threadIdx.x, pmv);
-    const int t = (int)threadIdx.x & 15;                       // out_w[0..3] | out_b | w1[0..3] | w2[0..3]
-    const float* src = t < 4 ? dd.out_w + t : (t == 4 ? dd.out_b : (t < 9 ? dd.g_w1 + (t - 5) : dd.g_w2 + (min(t, 12) - 9)));
-    owv = *src;
   }
   if constexpr (FAST) {
     const int n_items = 2 * n_rows * 64, x4 = X >> 2;
@@ -166,18 +141,7 @@ __global__ __launch_bounds__(kBlock) void hoa_mask_gate_kernel(
     }
   }
   }
-  if constexpr (D1) {
-    if (threadIdx.x < 16) s_ow[threadIdx.x] = owv;
-    hoa_gate::pm_reduce_rows<4>(dd.pm, b, dd.tiles, (int)threadIdx.x, pmv, s_red);
-  }
   __syncthreads();
-  if constexpr (D1) {
-    if (threadIdx.x < 64) {                                   // decoder1's HeightAttention gate (q = hid = 1)
-      const float gt = hoa_gate::gate_of_lane<4>(s_red, s_ow + 5, s_ow + 9, (int)threadIdx.x);
-      if (threadIdx.x < 4) s_g[threadIdx.x] = gt;
-    }
-    __syncthreads();
-  }
   const long pix = p0 + (long)threadIdx.x * VEC;
   if (pix >= plane) return;
   const int yy = (int)(pix / X), xx = (int)(pix % X);
@@ -225,21 +189,8 @@ __global__ __launch_bounds__(kBlock) void hoa_mask_gate_kernel(
       }
   }
   float m[VEC];
-  if constexpr (D1) {
-    const float dv[4][4] = {{d1v[0].x, d1v[0].y, d1v[0].z, d1v[0].w}, {d1v[1].x, d1v[1].y, d1v[1].z, d1v[1].w},
-                            {d1v[2].x, d1v[2].y, d1v[2].z, d1v[2].w}, {d1v[3].x, d1v[3].y, d1v[3].z, d1v[3].w}};
 #pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-      float o = s_ow[4];                                       // hoa_v2b_out_kernel's arithmetic
-#pragma unroll
-      for (int c = 0; c < 4; ++c) o = fmaf(dv[c][e] * s_g[c], s_ow[c], o);
-      if (g == 0) dd.opacity_out[(long)b * plane + pix + e] = o;
-      m[e] = sigmoidf_(acc[e] + o);
-    }
-  } else {
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) m[e] = sigmoidf_(acc[e] + opacity_bev[(long)b * plane + pix + e]);
-  }
+  for (int e = 0; e < VEC; ++e) m[e] = sigmoidf_(acc[e] + opacity_bev[(long)b * plane + pix + e]);
   if (g == 0) {
 #pragma unroll
     for (int e = 0; e < VEC; ++e) mask[(long)b * plane + pix + e] = m[e];
@@ -481,8 +432,8 @@ int ocrf_hoa_opacity_mask_gate(const float* x, const float* stats, const float* 
   if (gated && g_mg_groups > 0) groups = std::min(g_mg_groups, C);
   const dim3 grid((unsigned)((plane + per_wg - 1) / per_wg), 1, (unsigned)(B * groups));
 #define OCRF_MASK_GATE(V, K, F)                                                                                       \
-  ocrf::launch(OCRF_K_HOA_MASK_GATE, hoa_mask_gate_kernel<V, K, F, false>, grid, dim3(threads), lds, stream, x, stats, opacity_bev, \
-               conv_w, k, C, Y, X, groups, n_rows, mask, gated, MaskGateD1{})
+  ocrf::launch(OCRF_K_HOA_MASK_GATE, hoa_mask_gate_kernel<V, K, F>, grid, dim3(threads), lds, stream, x, stats, opacity_bev, \
+               conv_w, k, C, Y, X, groups, n_rows, mask, gated)
   if (fast) OCRF_MASK_GATE(4, 7, true);
   else if (vec4 && k == 7) OCRF_MASK_GATE(4, 7, false);
   else if (vec4) OCRF_MASK_GATE(4, 0, false);
@@ -491,10 +442,6 @@ int ocrf_hoa_opacity_mask_gate(const float* x, const float* stats, const float* 
 #undef OCRF_MASK_GATE
   return (int)hipGetLastError();
 }
-
-// (Rounds 4-5 also exported ocrf_hoa_opacity_mask_gate_v2b: HOA-2's output conv folded into this gate through the kernel's
-// D1 form — one launch less on the chain, but 288 VGPRs and not faster (DESIGN, round 4); nothing selected it, so the entry
-// point and its instantiation are gone.  The D1 branches of hoa_mask_gate_kernel are not instantiated.)
 
 size_t ocrf_hoa_height_attention_workspace_bytes(int B, int C) {
   return (size_t)B * C * 64 * sizeof(float);
@@ -550,55 +497,12 @@ struct UnetBlockArgs {
   const float* pw_w; const float* pw_b; int Cout;                     // BN-folded (Cout,Cin), (Cout)
   const float* addend;                                                // (B,Cout,H,W) or null
   float* out; float* partial_max; int H, W, tiles_x, tiles_y;         // partial_max (B*Cout, tiles) or null
-  // gate of src0 / src1 computed IN this kernel from the producer's per-tile channel maxima (pm != null; else the
-  // gate0 / gate1 vectors above, else 1): HeightAttention = sigmoid(w2 relu(w1 maxpool)) per channel quarter
-  const float* pm0; const float* g0w1; const float* g0w2; int g0hid, g0tiles;
-  const float* pm1; const float* g1w1; const float* g1w2; int g1hid, g1tiles;
 };
 
-// HeightAttention gate of one batch entry from per-tile maxima, by the whole workgroup, into s_gate[C]
-// (view_transformer_ocrf.py:421-461: global max-pool per channel, per quarter q -> hid -> q, sigmoid).  Every
-// consumer workgroup redoes this tiny reduction (C <= 16 channels x <= a few hundred tiles from L2) instead of
-// waiting for a separate launch between every two blocks of the UNet.  Contains barriers: call uniformly.
-__device__ __forceinline__ void gate_from_tiles_dev(int b, int C, int hid, int n_tiles, const float* __restrict__ partial,
-                                                     const float* __restrict__ w1, const float* __restrict__ w2,
-                                                     float* s_gate, float* s_max, float* s_hid) {
-  const int tid = threadIdx.x;
-  const int wave = tid >> 6, lane = tid & 63;
-  const int q = C / 4;
-  for (int c = wave; c < C; c += kBlock / 64) {
-    float m = -INFINITY;
-    for (int t = lane; t < n_tiles; t += 64) m = fmaxf(m, partial[((long)b * C + c) * n_tiles + t]);
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_down(m, off));
-    if (lane == 0) s_max[c] = m;
-  }
+// s_gate[C] = the gate the kernel multiplies a source with: the producer's gate vector, or 1.  Contains a barrier.
+__device__ __forceinline__ void load_gate_dev(int b, int C, const float* gate_vec, float* s_gate) {
+  if ((int)threadIdx.x < C) s_gate[threadIdx.x] = gate_vec ? gate_vec[b * C + threadIdx.x] : 1.f;
   __syncthreads();
-  if (tid < 4 * hid) {
-    const int g = tid / hid, h = tid % hid;
-    float acc = 0.f;
-    for (int i = 0; i < q; ++i) acc = fmaf(w1[(g * hid + h) * q + i], s_max[g * q + i], acc);
-    s_hid[tid] = fmaxf(acc, 0.f);
-  }
-  __syncthreads();
-  if (tid < C) {
-    const int g = tid / q, o = tid % q;
-    float acc = 0.f;
-    for (int h = 0; h < hid; ++h) acc = fmaf(w2[(g * q + o) * hid + h], s_hid[g * hid + h], acc);
-    s_gate[tid] = sigmoidf_(acc);
-  }
-  __syncthreads();
-}
-
-// s_gate[C] = the gate the kernel multiplies a source with: from tiles, from a vector, or 1
-__device__ __forceinline__ void load_gate_dev(int b, int C, const float* gate_vec, const float* pm, const float* w1,
-                                              const float* w2, int hid, int n_tiles, float* s_gate, float* s_max,
-                                              float* s_hid) {
-  if (pm) {
-    gate_from_tiles_dev(b, C, hid, n_tiles, pm, w1, w2, s_gate, s_max, s_hid);
-  } else {
-    if ((int)threadIdx.x < C) s_gate[threadIdx.x] = gate_vec ? gate_vec[b * C + threadIdx.x] : 1.f;
-    __syncthreads();
-  }
 }
 
 __global__ __launch_bounds__(kBlock) void hoa_unet_block_kernel(UnetBlockArgs a) {
@@ -619,11 +523,8 @@ __global__ __launch_bounds__(kBlock) void hoa_unet_block_kernel(UnetBlockArgs a)
     if (tid < a.Cout) s_pwb[tid] = a.pw_b[tid];
   }
   __syncthreads();
-  {
-    __shared__ float s_gm[64], s_gh[64];
-    load_gate_dev(blockIdx.z, a.C0, a.gate0, a.pm0, a.g0w1, a.g0w2, a.g0hid, a.g0tiles, s_g0, s_gm, s_gh);
-    if (a.C1 > 0) load_gate_dev(blockIdx.z, a.C1, a.gate1, a.pm1, a.g1w1, a.g1w2, a.g1hid, a.g1tiles, s_g1, s_gm, s_gh);
-  }
+  load_gate_dev(blockIdx.z, a.C0, a.gate0, s_g0);
+  if (a.C1 > 0) load_gate_dev(blockIdx.z, a.C1, a.gate1, s_g1);
   const int b = blockIdx.z;
   const int ty0 = blockIdx.y * kUT, tx0 = blockIdx.x * kUT;
   const int Cfirst = (a.mode == 2) ? a.Cup : a.C0;
@@ -741,131 +642,6 @@ __global__ __launch_bounds__(kBlock) void hoa_unet_block_kernel(UnetBlockArgs a)
   }
 }
 
-// Compile-time-shaped variant of hoa_unet_block_kernel for the five blocks of the reference UNet:
-// channel loops unroll completely, so every weight index is a constant and the weights arrive through
-// the scalar cache into SGPRs (no LDS traffic, no per-channel LDS latency chain) — the generic
-// kernel above spends its time waiting on serialized LDS reads inside runtime-bounded loops.
-template <int MODE, int C0, int CUP, int C1, int COUT>
-__global__ __launch_bounds__(kBlock) void hoa_unet_block_fixed_kernel(UnetBlockArgs a) {
-  constexpr int CF = (MODE == 2) ? CUP : C0;
-  constexpr int CIN = CF + C1;
-  __shared__ float s_v[CIN][kUH][kUH + 1];
-  __shared__ float s_red[kBlock / 64][COUT];
-  __shared__ float s_upw[(MODE == 2) ? C0 * CUP * 4 : 1];   // the 2x2 tap is per lane: vector (LDS) reads
-  __shared__ float s_g0[C0], s_g1[C1 > 0 ? C1 : 1], s_gm[64], s_gh[64];
-  const int tid = threadIdx.x;
-  const int b = blockIdx.z;
-  const int ty0 = blockIdx.y * kUT, tx0 = blockIdx.x * kUT;
-  const int H = a.H, W = a.W;
-  if (MODE == 2) {
-    for (int i = tid; i < C0 * CUP * 4; i += kBlock) s_upw[i] = a.up_w[i];
-  }
-  // The raw values of this thread's (at most two) halo pixels are requested BEFORE the producers' gates are rebuilt
-  // from their per-tile maxima: both are global round trips and a block is a latency chain (16-338 workgroups).
-  constexpr int kIt = (kUH * kUH + kBlock - 1) / kBlock;
-  float raw0[kIt][C0], raw1[kIt][C1 > 0 ? C1 : 1];
-#pragma unroll
-  for (int it = 0; it < kIt; ++it) {
-    const int i = tid + it * kBlock;
-    const int hy = i / kUH, hx = i % kUH;
-    const int y = ty0 + hy - 1, x = tx0 + hx - 1;
-    const bool in = (i < kUH * kUH) && (y >= 0) && (y < H) && (x >= 0) && (x < W);
-#pragma unroll
-    for (int c = 0; c < C0; ++c) {
-      float v = 0.f;
-      if (in) {
-        const float* p = a.src0 + ((long)b * C0 + c) * a.H0 * a.W0;
-        if (MODE == 2) {
-          v = p[(long)(y >> 1) * a.W0 + (x >> 1)];
-        } else if (MODE == 1) {
-          const float* q = p + (long)(2 * y) * a.W0 + 2 * x;
-          v = fmaxf(fmaxf(q[0], q[1]), fmaxf(q[a.W0], q[a.W0 + 1]));
-        } else {
-          v = p[(long)y * a.W0 + x];
-        }
-      }
-      raw0[it][c] = v;
-    }
-#pragma unroll
-    for (int c = 0; c < C1; ++c) raw1[it][c] = in ? a.src1[(((long)b * C1 + c) * H + y) * W + x] : 0.f;
-  }
-  load_gate_dev(b, C0, a.gate0, a.pm0, a.g0w1, a.g0w2, a.g0hid, a.g0tiles, s_g0, s_gm, s_gh);
-  if (C1 > 0) load_gate_dev(b, C1, a.gate1, a.pm1, a.g1w1, a.g1w2, a.g1hid, a.g1tiles, s_g1, s_gm, s_gh);
-
-#pragma unroll
-  for (int it = 0; it < kIt; ++it) {
-    const int i = tid + it * kBlock;
-    if (i >= kUH * kUH) continue;
-    const int hy = i / kUH, hx = i % kUH;
-    const int y = ty0 + hy - 1, x = tx0 + hx - 1;
-    const bool in = (y >= 0) && (y < H) && (x >= 0) && (x < W);
-    if (MODE == 2) {
-      const int ki = (y & 1) * 2 + (x & 1);
-      float sv[C0];
-#pragma unroll
-      for (int ci = 0; ci < C0; ++ci) sv[ci] = raw0[it][ci] * s_g0[ci];
-#pragma unroll
-      for (int co = 0; co < CUP; ++co) {
-        float acc = a.up_b[co];
-#pragma unroll
-        for (int ci = 0; ci < C0; ++ci) acc = fmaf(sv[ci], s_upw[(ci * CUP + co) * 4 + ki], acc);
-        s_v[co][hy][hx] = in ? acc : 0.f;
-      }
-    } else {
-#pragma unroll
-      for (int c = 0; c < C0; ++c) s_v[c][hy][hx] = in ? raw0[it][c] * s_g0[c] : 0.f;      // gates > 0: commute with the max-pool
-    }
-#pragma unroll
-    for (int c = 0; c < C1; ++c) s_v[CF + c][hy][hx] = in ? raw1[it][c] * s_g1[c] : 0.f;
-  }
-  __syncthreads();
-
-  const int ly = tid / kUT, lx = tid % kUT;
-  const int y = ty0 + ly, x = tx0 + lx;
-  const bool valid = (y < H) && (x < W);
-  float outv[COUT];
-#pragma unroll
-  for (int co = 0; co < COUT; ++co) outv[co] = a.pw_b[co];
-#pragma unroll
-  for (int c = 0; c < CIN; ++c) {
-    float d = a.dw_b[c];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) d = fmaf(s_v[c][ly + i][lx + j], a.dw_w[c * 9 + i * 3 + j], d);
-#pragma unroll
-    for (int co = 0; co < COUT; ++co) outv[co] = fmaf(d, a.pw_w[co * CIN + c], outv[co]);
-  }
-  const long plane = (long)H * W;
-  const long pix = (long)y * W + x;
-#pragma unroll
-  for (int co = 0; co < COUT; ++co) {
-    float v = fmaxf(outv[co], 0.f);
-    if (valid) {
-      if (a.addend) v += a.addend[((long)b * COUT + co) * plane + pix];
-      a.out[((long)b * COUT + co) * plane + pix] = v;
-    } else {
-      v = -INFINITY;
-    }
-    outv[co] = v;
-  }
-  if (a.partial_max) {
-#pragma unroll
-    for (int co = 0; co < COUT; ++co) {
-      float m = outv[co];
-      for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_down(m, off));
-      if ((tid & 63) == 0) s_red[tid >> 6][co] = m;
-    }
-    __syncthreads();
-    if (tid < COUT) {
-      float m = s_red[0][tid];
-      for (int w = 1; w < kBlock / 64; ++w) m = fmaxf(m, s_red[w][tid]);
-      const int n_tiles = a.tiles_x * a.tiles_y;
-      a.partial_max[((long)b * COUT + tid) * n_tiles + blockIdx.y * a.tiles_x + blockIdx.x] = m;
-    }
-  }
-}
-
 // HeightAttention gate from per-tile maxima (any number of tiles): one workgroup per batch entry,
 // one wave per channel for the max (no barrier per channel).
 __global__ __launch_bounds__(kBlock) void hoa_height_gate_from_tiles_kernel(
@@ -898,25 +674,21 @@ __global__ __launch_bounds__(kBlock) void hoa_height_gate_from_tiles_kernel(
   }
 }
 
-// Final 1x1 output conv (:516) over the gated decoder output; the gate as a vector or from per-tile maxima.
+// Final 1x1 output conv (:516) over the gated decoder output.
 __global__ __launch_bounds__(kBlock) void hoa_gated_conv1x1_kernel(const float* __restrict__ x,
                                                                    const float* __restrict__ gate, int C,
                                                                    long plane, const float* __restrict__ w,
                                                                    const float* __restrict__ bias,
-                                                                   float* __restrict__ out, const float* pm,
-                                                                   const float* gw1, const float* gw2, int ghid,
-                                                                   int gtiles) {
-  __shared__ float s_g[64], s_gm[64], s_gh[64];
+                                                                   float* __restrict__ out) {
+  __shared__ float s_g[64];
   const int b = blockIdx.y;
-  load_gate_dev(b, C, gate, pm, gw1, gw2, ghid, gtiles, s_g, s_gm, s_gh);
+  load_gate_dev(b, C, gate, s_g);
   const long pix = (long)blockIdx.x * kBlock + threadIdx.x;
   if (pix >= plane) return;
   float acc = bias[0];
   for (int c = 0; c < C; ++c) acc = fmaf(x[((long)b * C + c) * plane + pix] * s_g[c], w[c], acc);
   out[(long)b * plane + pix] = acc;
 }
-
-int launch_unet_block(const UnetBlockArgs& a, int B, hipStream_t stream);
 
 }  // namespace
 
@@ -942,36 +714,9 @@ int ocrf_hoa_unet_block(const float* src0, const float* gate0, int C0, int H0, i
   a.dw_w = dw_w; a.dw_b = dw_b; a.pw_w = pw_w; a.pw_b = pw_b; a.Cout = Cout; a.addend = addend;
   a.out = out; a.partial_max = partial_max; a.H = H; a.W = W;
   a.tiles_x = (W + kUT - 1) / kUT; a.tiles_y = (H + kUT - 1) / kUT;
-  a.pm0 = a.g0w1 = a.g0w2 = a.pm1 = a.g1w1 = a.g1w2 = nullptr;
-  a.g0hid = a.g0tiles = a.g1hid = a.g1tiles = 0;
-  return launch_unet_block(a, B, stream);
-}
-
-}  // extern "C"
-
-namespace {
-int launch_unet_block(const UnetBlockArgs& a, int B, hipStream_t stream) {
-  const int mode = a.mode, C0 = a.C0, Cup = a.Cup, C1 = a.C1, Cout = a.Cout;
-  const dim3 grid(a.tiles_x, a.tiles_y, B);
-#define OCRF_UNET_FIXED(M, c0, cup, c1, co)                                                                   \
-  if (mode == M && C0 == c0 && (M != 2 || Cup == cup) && C1 == c1 && Cout == co) {                            \
-    ocrf::launch(OCRF_K_HOA_UNET_BLOCK, hoa_unet_block_fixed_kernel<M, c0, cup, c1, co>, grid, dim3(kBlock), 0, \
-                 stream, a);                                                                                    \
-    return (int)hipGetLastError();                                                                              \
-  }
-  OCRF_UNET_FIXED(0, 13, 0, 0, 4)     // encoder1   (:498)
-  OCRF_UNET_FIXED(1, 4, 0, 0, 8)      // encoder2   (:501)
-  OCRF_UNET_FIXED(1, 8, 0, 0, 16)     // bottleneck (:504)
-  OCRF_UNET_FIXED(2, 16, 8, 8, 8)     // decoder2   (:507-509)
-  OCRF_UNET_FIXED(2, 8, 4, 4, 4)      // decoder1   (:512-514)
-#undef OCRF_UNET_FIXED
-  ocrf::launch(OCRF_K_HOA_UNET_BLOCK, hoa_unet_block_kernel, grid, dim3(kBlock), 0, stream, a);
+  ocrf::launch(OCRF_K_HOA_UNET_BLOCK, hoa_unet_block_kernel, dim3(a.tiles_x, a.tiles_y, B), dim3(kBlock), 0, stream, a);
   return (int)hipGetLastError();
 }
-
-}  // namespace
-
-extern "C" {
 
 // ocrf_hoa_v2b_weights_len / _workspace_bytes / _forward (the whole converter as six launches): csrc/hoa_v2b.hip
 
@@ -994,8 +739,7 @@ int ocrf_hoa_gated_conv1x1(const float* x, const float* gate, int B, int C, int 
   if (!x || !gate || !w || !bias || !out || B <= 0 || C <= 0 || H <= 0 || W <= 0) return (int)hipErrorInvalidValue;
   const long plane = (long)H * W;
   ocrf::launch(OCRF_K_HOA_OUT_CONV, hoa_gated_conv1x1_kernel, dim3((unsigned)((plane + kBlock - 1) / kBlock), B),
-               dim3(kBlock), 0, stream, x, gate, C, plane, w, bias, out, (const float*)nullptr, (const float*)nullptr,
-               (const float*)nullptr, 0, 0);
+               dim3(kBlock), 0, stream, x, gate, C, plane, w, bias, out);
   return (int)hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
-// Shared by hoa_v2b.hip (HOA-2 block kernels) and hoa.hip (the HOA-3 gate kernel that folds HOA-2's output conv in):
-// the HeightAttention gate of a producer rebuilt from its per-tile channel maxima, with DPP row reductions.
+// For hoa_v2b.hip (HOA-2 block kernels and output conv): the HeightAttention gate of a producer rebuilt by its
+// consumer from the producer's per-tile channel maxima, with DPP row reductions.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -348,21 +348,6 @@ inline int tiles_of(int h, int w) { return ((w + kTW - 1) / kTW) * ((h + kTH - 1
 
 }  // namespace
 
-namespace ocrf {
-void v2b_deferred_pointers(const void* workspace, const float* weights, int B, int H, int W, const float** d1,
-                           const float** pm, int* tiles, const float** out_w, const float** out_b, const float** g_w1,
-                           const float** g_w2) {
-  const int hs[5] = {H, H / 2, H / 4, H / 2, H}, wsz[5] = {W, W / 2, W / 4, W / 2, W};
-  const float* p = static_cast<const float*>(workspace);
-  for (int k = 0; k < 4; ++k) p += (size_t)B * kCout[k] * hs[k] * wsz[k] + (size_t)B * kCout[k] * tiles_of(hs[k], wsz[k]);
-  *d1 = p;
-  *pm = p + (size_t)B * kCout[4] * H * W;
-  *tiles = tiles_of(H, W);
-  *out_w = weights + kOff.out_w; *out_b = weights + kOff.out_b;
-  *g_w1 = weights + kOff.g_w1[4]; *g_w2 = weights + kOff.g_w2[4];
-}
-}  // namespace ocrf
-
 extern "C" {
 
 // length of the packed weight vector ocrf_hoa_v2b_forward reads: the converter's weights in v2b_offsets() order,
@@ -379,13 +364,12 @@ size_t ocrf_hoa_v2b_workspace_bytes(int B, int H, int W) {
 }
 
 // The whole OpacityVoxelToBEVConverter.forward (view_transformer_ocrf.py:497-518) of the architecture OcRFDet
-// instantiates as SIX launches in one call (FIVE with out == NULL: the output conv is then left to
-// ocrf_hoa_opacity_mask_gate_v2b).  x (B,13,H,W), position (B,4,H,W), out (B,1,H,W); H, W multiples of 4;
+// instantiates as SIX launches in one call.  x (B,13,H,W), position (B,4,H,W), out (B,1,H,W); H, W multiples of 4;
 // weights: ocrf_hoa_v2b_weights_len() floats, 16-byte aligned; workspace 16-byte aligned.
 int ocrf_hoa_v2b_forward(const float* x, const float* position, const float* weights, int B, int H, int W,
                          void* workspace, size_t workspace_bytes, float* out, ocrf_stream_t stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (!x || !position || !weights || !workspace || B <= 0 || B > 65535 || H < 4 || W < 4 || (H % 4) || (W % 4) ||
+  if (!x || !position || !weights || !workspace || !out || B <= 0 || B > 65535 || H < 4 || W < 4 || (H % 4) || (W % 4) ||
       workspace_bytes < ocrf_hoa_v2b_workspace_bytes(B, H, W) ||
       ((reinterpret_cast<uintptr_t>(weights) | reinterpret_cast<uintptr_t>(workspace)) & 15u))
     return (int)hipErrorInvalidValue;
@@ -424,7 +408,6 @@ int ocrf_hoa_v2b_forward(const float* x, const float* position, const float* wei
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
   }
-  if (!out) return 0;        // deferred: the output conv runs inside ocrf_hoa_opacity_mask_gate_v2b (csrc/hoa.hip)
   const long plane = (long)H * W;
   ocrf::launch(OCRF_K_HOA_OUT_CONV, hoa_v2b_out_kernel, dim3((unsigned)((plane + kBlock - 1) / kBlock), B), dim3(kBlock), 0,
                stream, static_cast<const float*>(act[4]), static_cast<const float*>(pm[4]), tiles[4], weights, plane, out);

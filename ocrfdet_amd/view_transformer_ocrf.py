@@ -16,7 +16,7 @@ configs/ocrfdet/ocrfdet.py:259-337), assembled MI355X-first:
                                                     cameras, then ocrf_nerf_alpha / ocrf_nerf_render on
                                                     composed maps (no (80,H,W) feature images)
     Gaussian render ............................... ocrf_rasterize_forward
-    HOA-1 / HOA-2 / HOA-3, geometry attention ..... ocrf_hoa1_forward, ocrf_hoa_unet_block, ...,
+    HOA-1 / HOA-2 / HOA-3, geometry attention ..... ocrf_hoa1_forward, ocrf_hoa_v2b_forward,
                                                     ocrf_hoa_opacity_mask_gate
     DualFeatFusion / ProbNet convolutions ......... PyTorch-ROCm (MIOpen), SURVEY 8a row a27
   training mode: the reference's op sequence as differentiable torch ops around the differentiable

@@ -109,6 +109,16 @@ def test_opacity_voxel_to_bev_gpu(cuda, g):
     np.testing.assert_allclose(out.cpu().numpy(), g['v2b_out'], rtol=1e-4, atol=3e-5)
 
 
+def _torch_block_by_block(m, xt, pt):
+    """The converter block by block: torch convolutions, eval-mode BatchNorm, the HeightAttention gate kernels."""
+    enc1 = m.ca1.gate_apply(m.encoder1(xt) + pt)
+    enc2 = m.ca2.gate_apply(m.encoder2(m.pool(enc1)))
+    mid = m.ca_bottleneck.gate_apply(m.bottleneck(m.pool(enc2)))
+    dec2 = m.ca_dec2.gate_apply(m.decoder2(torch.cat((m.upconv2(mid), enc2), dim=1)))
+    dec1 = m.ca_dec1.gate_apply(m.decoder1(torch.cat((m.upconv1(dec2), enc1), dim=1)))
+    return m.output_conv(dec1)
+
+
 @pytest.mark.gpu
 def test_opacity_voxel_to_bev_fused_vs_blockwise_and_oracle(cuda, g):
     """Eval-mode fused path (5 block kernels) == training-style block-by-block path == numpy oracle,
@@ -122,12 +132,7 @@ def test_opacity_voxel_to_bev_fused_vs_blockwise_and_oracle(cuda, g):
     xt, pt = torch.from_numpy(x).to(cuda), torch.from_numpy(pos).to(cuda)
     with torch.no_grad():
         fused = m(xt, pt)
-        enc1 = m.ca1.gate_apply(m.encoder1(xt) + pt)                       # block-by-block (torch convs)
-        enc2 = m.ca2.gate_apply(m.encoder2(m.pool(enc1)))
-        mid = m.ca_bottleneck.gate_apply(m.bottleneck(m.pool(enc2)))
-        dec2 = m.ca_dec2.gate_apply(m.decoder2(torch.cat((m.upconv2(mid), enc2), dim=1)))
-        dec1 = m.ca_dec1.gate_apply(m.decoder1(torch.cat((m.upconv1(dec2), enc1), dim=1)))
-        blockwise = m.output_conv(dec1)
+        blockwise = _torch_block_by_block(m, xt, pt)
     np.testing.assert_allclose(fused.cpu().numpy(), blockwise.cpu().numpy(), rtol=1e-4, atol=3e-5)
     want = ohoa.opacity_voxel_to_bev(x, pos, g, 'v2b')
     np.testing.assert_allclose(fused.cpu().numpy(), want, rtol=1e-4, atol=3e-5)
@@ -155,6 +160,47 @@ def test_opacity_voxel_to_bev_six_launch_form_on_other_map_sizes(cuda, g, B, H, 
         six = m(xt, pt)
         eleven = m._forward_blocks(xt, pt)
     assert torch.equal(six, eleven)
+
+
+@pytest.mark.gpu
+def test_opacity_voxel_to_bev_other_channel_count_takes_the_blockwise_kernels(cuda):
+    """A converter that is not the reference's (8 input channels) runs ``_forward_blocks`` in eval mode — the generic
+    block kernel with C0 = 8 — and agrees with the torch block-by-block sequence; 36 x 52: ragged 16 x 16 tiles at all
+    three levels (36 x 52, 18 x 26, 9 x 13), BatchNorm with running statistics and an affine that fold to something."""
+    torch.manual_seed(8)
+    m = hoa.OpacityVoxelToBEVConverter(8).to(cuda).eval()
+    with torch.no_grad():
+        for bn in (mod for mod in m.modules() if isinstance(mod, torch.nn.BatchNorm2d)):
+            bn.running_mean.copy_(torch.randn_like(bn.running_mean) * 0.2)
+            bn.running_var.copy_(torch.rand_like(bn.running_var) + 0.5)
+            bn.weight.copy_(torch.rand_like(bn.weight) + 0.5)
+            bn.bias.copy_(torch.randn_like(bn.bias) * 0.1)
+    assert not m._is_reference_architecture()
+    xt = torch.rand(2, 8, 36, 52, device=cuda)
+    pt = torch.randn(2, 4, 36, 52, device=cuda) * 0.1
+    with torch.no_grad():
+        got = m(xt, pt)
+        want = _torch_block_by_block(m, xt, pt)
+    assert got.shape == (2, 1, 36, 52)
+    np.testing.assert_allclose(got.cpu().numpy(), want.cpu().numpy(), rtol=1e-4, atol=3e-5)
+
+
+@pytest.mark.gpu
+def test_v2b_forward_refuses_a_null_output_before_any_launch(cuda):
+    """``ocrf_hoa_v2b_forward`` with ``out = NULL`` is hipErrorInvalidValue from the argument check, like every other
+    missing pointer: no block kernel has run, the workspace still holds what was in it."""
+    from ocrfdet_amd import _lib
+    L, p = _lib.lib(), _lib.ptr
+    B, H, W = 1, 16, 16
+    x, pos = torch.rand(B, 13, H, W, device=cuda), torch.zeros(B, 4, H, W, device=cuda)
+    w = torch.zeros(L.ocrf_hoa_v2b_weights_len(), device=cuda)
+    nbytes = L.ocrf_hoa_v2b_workspace_bytes(B, H, W)
+    assert nbytes > 0 and nbytes % 4 == 0
+    ws = torch.full((nbytes // 4,), 12345.0, device=cuda)
+    torch.cuda.synchronize()
+    assert L.ocrf_hoa_v2b_forward(p(x), p(pos), p(w), B, H, W, p(ws), nbytes, None, _lib.stream_ptr(cuda)) == 1
+    torch.cuda.synchronize()
+    assert bool((ws == 12345.0).all())
 
 
 @pytest.mark.gpu

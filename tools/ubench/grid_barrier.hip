@@ -2,7 +2,7 @@
 //   (a) a dependent launch on one stream (what the six-launch HOA-2 pays five times), against
 //   (b) a grid-wide barrier inside one persistent kernel (what a fused HOA-2 would pay five times),
 // both with the payload of a U-Net block's boundary: every workgroup publishes 16 per-tile maxima before the boundary
-// and reads all tiles' maxima after it (gate_from_tiles_dev in csrc/hoa.hip).  Grids are those of the blocks at cfg2
+// and reads all tiles' maxima after it (the gate rebuild of csrc/hoa_gate.h).  Grids are those of the blocks at cfg2
 // (B = 2): 32, 98 and 338 workgroups of 256 threads.
 //   hipcc --offload-arch=gfx950 -O3 grid_barrier.hip -o grid_barrier && ./grid_barrier
 #include <hip/hip_runtime.h>
