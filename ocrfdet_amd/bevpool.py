@@ -14,7 +14,15 @@ interval_lengths)``  -> ``(B, C, Z, Y, X)`` contiguous fp32                     
                       pybind module's argument order — ``interval_lengths`` BEFORE
                       ``interval_starts``                               [src/bev_pool.cpp:30-39,74-85]
 
-All compute is in ``csrc/bev_pool.hip`` behind the C ABI of ``include/ocrf_hip.h``.  There is no
+Beyond the reference's surface: ``bev_pool_v2_collapsed`` and ``bev_pool_v2_device_counts[_autograd]`` (the fused tile
+kernel, the latter on rank vectors whose lengths stay on the device), ``DevicePoolPlan`` / ``MfmaPoolPlan`` with
+``bev_pool_v2_planned`` / ``bev_pool_v2_mfma`` / ``bev_pool_v2_panel`` for cached rank vectors, and ``PoolPlan``, which owns
+cached rank vectors and is the one place that says which of those pools them (``PoolPlan.pool``).  Stated once for all
+of them: the operand prologue with the 2 GiB refusal (``_fp32_operands``), the ``out=`` contract (``_out_tensor``), the
+panel channel counts (``PANEL_CHANNELS``) and the backward (``_pool_backward``, behind ``QuickCumsumCuda`` and
+``_FusedPool``).
+
+All compute is in ``csrc/bev_pool*.hip`` behind the C ABI of ``include/ocrf_hip.h``.  There is no
 CPU path: CPU tensors raise ``OcrfHipError``.
 """
 import os
@@ -104,20 +112,82 @@ class _ExtensionAPI:
 bev_pool_v2_ext = _ExtensionAPI()
 
 
+PANEL_CHANNELS = (64, 80, 96, 128)      # channel counts csrc/bev_pool_mfma.hip / bev_pool_panel.hip are instantiated for
+
+
+def _fusable(channels):
+    return channels % 4 == 0 and 32 <= channels <= 256
+
+
+def _panel_channels(channels):
+    return channels in PANEL_CHANNELS
+
+
+def _check_32bit_offsets(*tensors):
+    """The tile / MFMA / panel pooling kernels address their operands, as fp32, with 32-bit byte offsets (raw buffer loads
+    whose resource covers 2^31 - 1 bytes: a load beyond returns 0 silently).  An operand of 2 GiB or more is refused here,
+    on its size alone."""
+    for t in tensors:
+        if t is not None and t.numel() * 4 >= (1 << 31):
+            raise _lib.OcrfHipError(f'a pooling operand of {t.numel() * 4} bytes exceeds the 2 GiB the '
+                                    'kernels\' 32-bit offsets cover: split the batch')
+
+
+def _fp32_operands(*tensors, channels=None, said_by='the plan was built for'):
+    """The operand prologue of every wrapper of those kernels: 2 GiB refused (before anything asks for the device),
+    contiguous fp32, on the GPU, and — with ``channels`` — the last one a ``feat`` of that many channels."""
+    _check_32bit_offsets(*tensors)
+    ops = [t.float().contiguous() for t in tensors]
+    _lib.require_cuda(*ops)
+    if channels is not None and ops[-1].size(-1) != channels:
+        raise _lib.OcrfHipError(f'feat has {ops[-1].size(-1)} channels, {said_by} {channels}')
+    return ops
+
+
+def _int32(*ranks):
+    """dtype / contiguity normalisation of rank and interval vectors as bev_pool.py:19-25."""
+    return tuple(t.int().contiguous() for t in ranks)
+
+
+def _out_tensor(out, shape, layout, dev):
+    """The ``out=`` contract: a new (B,C,Z,Y,X) (layout 0) / (B,Z*C,Y,X) tensor, or the caller's once it is contiguous fp32
+    of that many elements on ``dev`` (e.g. a slice of a fused multi-frame buffer)."""
+    B, Z, Y, X, C = shape
+    if out is None:
+        return torch.empty((B, C, Z, Y, X) if layout == 0 else (B, Z * C, Y, X), dtype=torch.float32, device=dev)
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * C * Z * Y * X or out.device != dev:
+        raise _lib.OcrfHipError('out must be a contiguous fp32 tensor of B*C*Z*Y*X elements on the inputs\' device')
+    return out
+
+
+def _pool_backward(grad_rows, d32, f32, rd, rf, rb, n_live=None):
+    """The backward of every autograd surface -> (depth_grad, feat_grad).  ``grad_rows``: the upstream gradient as contiguous
+    fp32 (B,Z,Y,X,C) rows.  The point list is regrouped by feature pixel (bev_pool.py:47-57), stably, so that runs of
+    equal ranks_feat keep their forward order.  ``n_live``: device-side point count of rank vectors at their capacity; the
+    entries past it (uninitialised) get a feature index past the last pixel first, so the stable sort puts them behind
+    every run and no run covers them — and nothing is read back from the device."""
+    n_pixels = f32.numel() // f32.size(-1)
+    if n_live is not None:
+        live = torch.arange(rf.numel(), device=rf.device, dtype=torch.int32) < n_live
+        rf = torch.where(live, rf, torch.full_like(rf, n_pixels))
+    rf_sorted, perm = torch.sort(rf, stable=True)
+    starts_bp, lengths_bp = dense_runs(rf_sorted, n_pixels)
+    g_depth = torch.zeros_like(d32)
+    g_feat = torch.zeros_like(f32)
+    bev_pool_v2_ext.bev_pool_v2_backward(grad_rows, g_depth, g_feat, d32, f32, rd[perm].contiguous(), rf_sorted.contiguous(),
+                                         rb[perm].contiguous(), lengths_bp, starts_bp)
+    return g_depth, g_feat
+
+
 class QuickCumsumCuda(torch.autograd.Function):
     """Autograd wrapper with the reference's name and call signature (bev_pool.py:11-83)."""
 
     @staticmethod
     def forward(ctx, depth, feat, ranks_depth, ranks_feat, ranks_bev,
                 bev_feat_shape, interval_starts, interval_lengths):
-        # dtype/contiguity normalisation as bev_pool.py:19-25
-        rb = ranks_bev.int().contiguous()
-        rd = ranks_depth.int().contiguous()
-        rf = ranks_feat.int().contiguous()
+        rb, rd, rf, starts, lengths = _int32(ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths)
         d32 = depth.float().contiguous()
         f32 = feat.float().contiguous()
-        starts = interval_starts.int().contiguous()
-        lengths = interval_lengths.int().contiguous()
         pooled = f32.new_zeros(tuple(int(s) for s in bev_feat_shape))    # bev_pool.py:27
         bev_pool_v2_ext.bev_pool_v2_forward(d32, f32, pooled, rd, rf, rb, lengths, starts)
         ctx.save_for_backward(rb, d32, f32, rf, rd)
@@ -126,82 +196,7 @@ class QuickCumsumCuda(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_pooled):
         rb, d32, f32, rf, rd = ctx.saved_tensors
-        # regroup the point list by feature pixel (bev_pool.py:47-57); stable so that runs of
-        # equal ranks_feat keep their forward order
-        rf_sorted, perm = torch.sort(rf, stable=True)
-        starts_bp, lengths_bp = dense_runs(rf_sorted, f32.numel() // f32.size(-1))
-        g_depth = torch.zeros_like(d32)
-        g_feat = torch.zeros_like(f32)
-        bev_pool_v2_ext.bev_pool_v2_backward(
-            grad_pooled.contiguous(), g_depth, g_feat, d32, f32, rd[perm].contiguous(),
-            rf_sorted.contiguous(), rb[perm].contiguous(), lengths_bp, starts_bp)
-        return g_depth, g_feat, None, None, None, None, None, None
-
-
-def _fusable(channels):
-    return channels % 4 == 0 and 32 <= channels <= 256
-
-
-class _FusedPool(torch.autograd.Function):
-    """bev_pool_v2 + the reference's layout passes in one go (C ABI ``ocrf_bev_pool_v2_nchw``):
-    ``layout`` 0 -> (B,C,Z,Y,X) (bev_pool.py:91), 1 -> (B,Z*C,Y,X) (view_transformer.py:194).
-    The output is written exactly once (no zero-fill, no permute, no cat)."""
-
-    @staticmethod
-    def forward(ctx, depth, feat, ranks_depth, ranks_feat, ranks_bev, bev_feat_shape,
-                interval_starts, interval_lengths, layout):
-        rb = ranks_bev.int().contiguous()
-        rd = ranks_depth.int().contiguous()
-        rf = ranks_feat.int().contiguous()
-        d32 = depth.float().contiguous()
-        f32 = feat.float().contiguous()
-        starts = interval_starts.int().contiguous()
-        lengths = interval_lengths.int().contiguous()
-        _lib.require_cuda(d32, f32, rb, rd, rf, starts, lengths)
-        B, Z, Y, X, C = (int(v) for v in bev_feat_shape)
-        if f32.size(-1) != C:
-            raise _lib.OcrfHipError(f'feat has {f32.size(-1)} channels, bev_feat_shape says {C}')
-        n_iv, n_pts = starts.numel(), rd.numel()
-        if rf.numel() != n_pts or rb.numel() != n_pts or lengths.numel() != n_iv:
-            raise _lib.OcrfHipError('rank / interval vectors disagree in length')
-        dev = d32.device
-        out = torch.empty((B, C, Z, Y, X) if layout == 0 else (B, Z * C, Y, X),
-                          dtype=torch.float32, device=dev)
-        need = _lib.lib().ocrf_bev_pool_v2_nchw_workspace_bytes(C, n_iv, n_pts, B, Z, Y, X)
-        scratch = _lib.workspace.get(dev, need, 'bev_pool_nchw')
-        _lib.launch('ocrf_bev_pool_v2_nchw', dev, C, n_iv, n_pts, d32, f32, rd, rf, rb, starts, lengths, out, B, Z, Y, X,
-                    int(layout), scratch, scratch.numel())
-        ctx.save_for_backward(rb, d32, f32, rf, rd)
-        ctx.geom = (B, Z, Y, X, C, int(layout))
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        rb, d32, f32, rf, rd = ctx.saved_tensors
-        B, Z, Y, X, C, layout = ctx.geom
-        if layout == 0:
-            g = grad_out.permute(0, 2, 3, 4, 1)                       # (B,Z,Y,X,C)
-        else:
-            g = grad_out.view(B, Z, C, Y, X).permute(0, 1, 3, 4, 2)
-        rf_sorted, perm = torch.sort(rf, stable=True)
-        starts_bp, lengths_bp = dense_runs(rf_sorted, f32.numel() // f32.size(-1))
-        g_depth = torch.zeros_like(d32)
-        g_feat = torch.zeros_like(f32)
-        bev_pool_v2_ext.bev_pool_v2_backward(
-            g.contiguous().float(), g_depth, g_feat, d32, f32, rd[perm].contiguous(),
-            rf_sorted.contiguous(), rb[perm].contiguous(), lengths_bp, starts_bp)
-        return g_depth, g_feat, None, None, None, None, None, None, None
-
-
-def bev_pool_v2(depth, feat, ranks_depth, ranks_feat, ranks_bev,
-                bev_feat_shape, interval_starts, interval_lengths):
-    """The reference's op: -> (B, C, Z, Y, X) contiguous fp32 (bev_pool.py:86-92)."""
-    if _fusable(int(bev_feat_shape[-1])):
-        return _FusedPool.apply(depth, feat, ranks_depth, ranks_feat, ranks_bev, bev_feat_shape,
-                                interval_starts, interval_lengths, 0)
-    pooled = QuickCumsumCuda.apply(depth, feat, ranks_depth, ranks_feat, ranks_bev,
-                                   bev_feat_shape, interval_starts, interval_lengths)
-    return pooled.permute(0, 4, 1, 2, 3).contiguous()        # (B,Z,Y,X,C) -> (B,C,Z,Y,X)
+        return _pool_backward(grad_pooled.contiguous(), d32, f32, rd, rf, rb) + (None,) * 6
 
 
 @torch.no_grad()
@@ -216,14 +211,14 @@ def bev_pool_v2_device_counts(depth, feat, ranks_depth, ranks_feat, ranks_bev, b
     B, Z, Y, X, C = (int(v) for v in bev_feat_shape)
     if not _fusable(C):
         raise _lib.OcrfHipError(f'bev_pool_v2_device_counts needs C % 4 == 0 and C <= 256, got {C}')
-    d32, f32 = depth.float().contiguous(), feat.float().contiguous()
-    _lib.require_cuda(d32, f32, ranks_depth, ranks_feat, ranks_bev, interval_starts, interval_lengths, counts)
+    d32, f32 = _fp32_operands(depth, feat)
+    _lib.require_cuda(ranks_depth, ranks_feat, ranks_bev, interval_starts, interval_lengths, counts)
     for t in (ranks_depth, ranks_feat, ranks_bev, interval_starts, interval_lengths, counts):
         if t.dtype != torch.int32 or not t.is_contiguous():
             raise _lib.OcrfHipError('rank / interval / count vectors must be contiguous int32')
     cap_pts, cap_iv = ranks_depth.numel(), interval_starts.numel()
     dev = d32.device
-    out = torch.empty((B, C, Z, Y, X) if layout == 0 else (B, Z * C, Y, X), dtype=torch.float32, device=dev)
+    out = _out_tensor(None, (B, Z, Y, X, C), layout, dev)
     need = _lib.lib().ocrf_bev_pool_v2_nchw_workspace_bytes(C, cap_iv, cap_pts, B, Z, Y, X)
     scratch = _lib.workspace.get(dev, need, scratch_tag)
     _lib.launch('ocrf_bev_pool_v2_nchw_dyn', dev, C, cap_iv, cap_pts, counts, d32, f32, ranks_depth, ranks_feat, ranks_bev,
@@ -231,22 +226,36 @@ def bev_pool_v2_device_counts(depth, feat, ranks_depth, ranks_feat, ranks_bev, b
     return out
 
 
-class _FusedPoolCounts(torch.autograd.Function):
-    """``_FusedPool`` on rank vectors whose LENGTHS LIVE ON THE DEVICE (``index_prep.*_hip(sync=False)``: five vectors at
-    their capacity + ``counts`` = int32 [n_points, n_intervals]): forward by ``ocrf_bev_pool_v2_nchw_dyn``, backward by the
-    same kernel as ``_FusedPool`` — so a training forward reads nothing back from the device.  The backward regroups the
-    points by feature pixel like the reference (bev_pool.py:47-57); the entries past ``n_points`` (uninitialised) are given
-    a feature index past the last pixel first, so the stable sort puts them behind every run and no run covers them."""
+class _FusedPool(torch.autograd.Function):
+    """bev_pool_v2 + the reference's layout passes in one go: ``layout`` 0 -> (B,C,Z,Y,X) (bev_pool.py:91), 1 ->
+    (B,Z*C,Y,X) (view_transformer.py:194).  The output is written exactly once (no zero-fill, no permute, no cat).
+    ``counts`` None: exact rank vectors (C ABI ``ocrf_bev_pool_v2_nchw``); otherwise rank vectors whose LENGTHS LIVE ON THE
+    DEVICE (``bev_pool_v2_device_counts``), so that a training forward reads nothing back.  One backward for both."""
 
     @staticmethod
     def forward(ctx, depth, feat, ranks_depth, ranks_feat, ranks_bev, bev_feat_shape, interval_starts, interval_lengths,
-                counts, layout, scratch_tag):
-        d32, f32 = depth.float().contiguous(), feat.float().contiguous()
-        with torch.no_grad():
-            out = bev_pool_v2_device_counts(d32, f32, ranks_depth, ranks_feat, ranks_bev, bev_feat_shape, interval_starts,
-                                            interval_lengths, counts, layout=layout, scratch_tag=scratch_tag)
-        ctx.save_for_backward(ranks_bev, d32, f32, ranks_feat, ranks_depth, counts)
-        ctx.geom = tuple(int(v) for v in bev_feat_shape) + (int(layout),)
+                layout, counts, scratch_tag):
+        B, Z, Y, X, C = shape = tuple(int(v) for v in bev_feat_shape)
+        if counts is None:
+            d32, f32 = _fp32_operands(depth, feat, channels=C, said_by='bev_feat_shape says')
+            rb, rd, rf, starts, lengths = _int32(ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths)
+            _lib.require_cuda(rb, rd, rf, starts, lengths)
+            n_iv, n_pts = starts.numel(), rd.numel()
+            if rf.numel() != n_pts or rb.numel() != n_pts or lengths.numel() != n_iv:
+                raise _lib.OcrfHipError('rank / interval vectors disagree in length')
+            dev = d32.device
+            out = _out_tensor(None, shape, layout, dev)
+            need = _lib.lib().ocrf_bev_pool_v2_nchw_workspace_bytes(C, n_iv, n_pts, B, Z, Y, X)
+            scratch = _lib.workspace.get(dev, need, scratch_tag)
+            _lib.launch('ocrf_bev_pool_v2_nchw', dev, C, n_iv, n_pts, d32, f32, rd, rf, rb, starts, lengths, out, B, Z, Y, X,
+                        int(layout), scratch, scratch.numel())
+        else:
+            d32, f32 = _fp32_operands(depth, feat)
+            rb, rd, rf = ranks_bev, ranks_depth, ranks_feat
+            out = bev_pool_v2_device_counts(d32, f32, rd, rf, rb, shape, interval_starts, interval_lengths, counts,
+                                            layout=layout, scratch_tag=scratch_tag)
+        ctx.save_for_backward(rb, d32, f32, rf, rd, counts)
+        ctx.geom = shape + (int(layout),)
         return out
 
     @staticmethod
@@ -257,23 +266,26 @@ class _FusedPoolCounts(torch.autograd.Function):
             g = grad_out.permute(0, 2, 3, 4, 1)                       # (B,Z,Y,X,C)
         else:
             g = grad_out.view(B, Z, C, Y, X).permute(0, 1, 3, 4, 2)
-        n_pixels = f32.numel() // f32.size(-1)
-        live = torch.arange(rf.numel(), device=rf.device, dtype=torch.int32) < counts[0]
-        rf_sorted, perm = torch.sort(torch.where(live, rf, torch.full_like(rf, n_pixels)), stable=True)
-        starts_bp, lengths_bp = dense_runs(rf_sorted, n_pixels)
-        g_depth = torch.zeros_like(d32)
-        g_feat = torch.zeros_like(f32)
-        bev_pool_v2_ext.bev_pool_v2_backward(
-            g.contiguous().float(), g_depth, g_feat, d32, f32, rd[perm].contiguous(),
-            rf_sorted.contiguous(), rb[perm].contiguous(), lengths_bp, starts_bp)
-        return (g_depth, g_feat) + (None,) * 9
+        return _pool_backward(g.contiguous().float(), d32, f32, rd, rf, rb,
+                              n_live=None if counts is None else counts[0]) + (None,) * 9
+
+
+def bev_pool_v2(depth, feat, ranks_depth, ranks_feat, ranks_bev,
+                bev_feat_shape, interval_starts, interval_lengths):
+    """The reference's op: -> (B, C, Z, Y, X) contiguous fp32 (bev_pool.py:86-92)."""
+    if _fusable(int(bev_feat_shape[-1])):
+        return _FusedPool.apply(depth, feat, ranks_depth, ranks_feat, ranks_bev, bev_feat_shape,
+                                interval_starts, interval_lengths, 0, None, 'bev_pool_nchw')
+    pooled = QuickCumsumCuda.apply(depth, feat, ranks_depth, ranks_feat, ranks_bev,
+                                   bev_feat_shape, interval_starts, interval_lengths)
+    return pooled.permute(0, 4, 1, 2, 3).contiguous()        # (B,Z,Y,X,C) -> (B,C,Z,Y,X)
 
 
 def bev_pool_v2_device_counts_autograd(depth, feat, ranks_depth, ranks_feat, ranks_bev, bev_feat_shape, interval_starts,
                                        interval_lengths, counts, layout=1, scratch_tag='bev_pool_nchw'):
-    """``bev_pool_v2_device_counts`` with autograd for ``depth`` and ``feat`` (``_FusedPoolCounts``)."""
-    return _FusedPoolCounts.apply(depth, feat, ranks_depth, ranks_feat, ranks_bev, bev_feat_shape, interval_starts,
-                                  interval_lengths, counts, int(layout), scratch_tag)
+    """``bev_pool_v2_device_counts`` with autograd for ``depth`` and ``feat`` (``_FusedPool`` with ``counts``)."""
+    return _FusedPool.apply(depth, feat, ranks_depth, ranks_feat, ranks_bev, bev_feat_shape, interval_starts,
+                            interval_lengths, int(layout), counts, scratch_tag)
 
 
 class DevicePoolPlan:
@@ -289,9 +301,8 @@ class DevicePoolPlan:
         if not _fusable(C):
             raise _lib.OcrfHipError(f'pool plans need C % 4 == 0 and C <= 256, got {C}')
         self.shape = (B, Z, Y, X, C)
-        self.ranks_depth = ranks_depth.int().contiguous()
-        self.ranks_feat = ranks_feat.int().contiguous()
-        rb, st, ln = ranks_bev.int().contiguous(), interval_starts.int().contiguous(), interval_lengths.int().contiguous()
+        self.ranks_depth, self.ranks_feat, rb, st, ln = _int32(ranks_depth, ranks_feat, ranks_bev, interval_starts,
+                                                               interval_lengths)
         self.n_points, self.n_intervals = self.ranks_depth.numel(), st.numel()
         dev = rb.device
         L = _lib.lib()
@@ -307,33 +318,15 @@ class DevicePoolPlan:
 @torch.no_grad()
 def bev_pool_v2_planned(depth, feat, plan, layout=1, out=None):
     """``bev_pool_v2_collapsed`` (layout 1: (B, Z*C, Y, X)) or ``bev_pool_v2`` (layout 0: (B,C,Z,Y,X)) for the
-    rank vectors a ``DevicePoolPlan`` was built from; bit-identical results.  ``out``: optional contiguous fp32
-    tensor of that many elements to write into (e.g. a slice of a fused multi-frame buffer)."""
+    rank vectors a ``DevicePoolPlan`` was built from; bit-identical results.  ``out``: see ``_out_tensor``."""
     B, Z, Y, X, C = plan.shape
-    d32, f32 = depth.float().contiguous(), feat.float().contiguous()
-    _check_32bit_offsets(d32, f32)
-    _lib.require_cuda(d32, f32)
-    if f32.size(-1) != C:
-        raise _lib.OcrfHipError(f'feat has {f32.size(-1)} channels, the plan was built for {C}')
+    d32, f32 = _fp32_operands(depth, feat, channels=C)
     dev = d32.device
-    shape = (B, C, Z, Y, X) if layout == 0 else (B, Z * C, Y, X)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=dev)
-    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * C * Z * Y * X or out.device != dev:
-        raise _lib.OcrfHipError('out must be a contiguous fp32 tensor of B*C*Z*Y*X elements on the inputs\' device')
+    out = _out_tensor(out, plan.shape, layout, dev)
     _lib.launch('ocrf_bev_pool_v2_nchw_planned', dev, C, plan.n_points, d32, f32, plan.ranks_depth, plan.ranks_feat,
                 plan.plan, out, B, Z, Y, X, int(layout), plan.scratch, plan.scratch.numel(), d32.numel() * 4,
                 f32.numel() * 4)
     return out
-
-
-def _check_32bit_offsets(*tensors):
-    """The tile / MFMA / panel pooling kernels address their operands with 32-bit byte offsets (raw buffer loads whose
-    resource covers 2^31 - 1 bytes: a load beyond returns 0 silently).  A tensor of 2 GiB or more is refused here."""
-    for t in tensors:
-        if t is not None and t.numel() * t.element_size() >= (1 << 31):
-            raise _lib.OcrfHipError(f'a pooling operand of {t.numel() * t.element_size()} bytes exceeds the 2 GiB the '
-                                    'kernels\' 32-bit offsets cover: split the batch')
 
 
 class MfmaPoolPlan:
@@ -347,8 +340,8 @@ class MfmaPoolPlan:
     def __init__(self, ranks_depth, ranks_feat, ranks_bev, bev_feat_shape, group=4, unit_cost=None):
         _lib.require_cuda(ranks_depth, ranks_feat, ranks_bev)
         B, Z, Y, X, C = (int(v) for v in bev_feat_shape)
-        if C not in (64, 80, 96, 128):
-            raise _lib.OcrfHipError(f'the MFMA pooling takes C in (64, 80, 96, 128), got {C}')
+        if not _panel_channels(C):
+            raise _lib.OcrfHipError(f'the MFMA pooling takes C in {PANEL_CHANNELS}, got {C}')
         self.shape = (B, Z, Y, X, C)
         dev = ranks_bev.device
         L = _lib.lib()
@@ -489,17 +482,9 @@ def bev_pool_v2_mfma(depth, feat, plan, layout=1, out=None):
     """The pooling of ``plan``'s rank vectors on the matrix cores: (B, Z*C, Y, X) (layout 1) or (B,C,Z,Y,X)
     (layout 0); same result as ``bev_pool_v2_planned`` up to the summation order."""
     B, Z, Y, X, C = plan.shape
-    d32, f32 = depth.float().contiguous(), feat.float().contiguous()
-    _check_32bit_offsets(d32, f32)
-    _lib.require_cuda(d32, f32)
-    if f32.size(-1) != C:
-        raise _lib.OcrfHipError(f'feat has {f32.size(-1)} channels, the plan was built for {C}')
+    d32, f32 = _fp32_operands(depth, feat, channels=C)
     dev = d32.device
-    shape = (B, C, Z, Y, X) if layout == 0 else (B, Z * C, Y, X)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=dev)
-    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * C * Z * Y * X or out.device != dev:
-        raise _lib.OcrfHipError('out must be a contiguous fp32 tensor of B*C*Z*Y*X elements on the inputs\' device')
+    out = _out_tensor(out, plan.shape, layout, dev)
     _lib.launch('ocrf_bev_pool_v2_nchw_mfma', dev, C, plan.n_units, plan.units, plan.unit_slab, plan.panel_rows,
                 plan.panel_nrows, plan.panel_cell_off, plan.cells, plan.rd_sorted, d32, f32, out, B, Z, Y, X, int(layout),
                 plan.arrive, plan.slabs)
@@ -510,10 +495,8 @@ def bev_pool_v2_mfma(depth, feat, plan, layout=1, out=None):
 def bev_pool_cell_weights(depth, plan, plan2=None):
     """Pre-pass of ``bev_pool_v2_panel``: the summed depth weight of every cell of ``plan`` (and of ``plan2`` — the LSS
     and the height-sampling plan of a step read the same depth tensor) in ONE launch -> ``plan.cw`` (``plan2.cw``)."""
-    d32 = depth.float().contiguous()
-    _check_32bit_offsets(d32)
-    _lib.require_cuda(d32)
-    n2 = plan2.n_cells if (plan2 is not None and plan2.n_points) else 0
+    d32, = _fp32_operands(depth)
+    n2 =plan2.n_cells if (plan2 is not None and plan2.n_points) else 0
     n1 = plan.n_cells if plan.n_points else 0
     _lib.launch('ocrf_bev_pool_cell_weights', d32.device, n1, plan.cells, plan.rd_sorted, plan.cw,
                 n2, plan2.cells if n2 else None, plan2.rd_sorted if n2 else None, plan2.cw if n2 else None, d32)
@@ -529,20 +512,12 @@ def bev_pool_v2_panel(depth, feat, plan, layout=1, out=None, weights_ready=False
     pixel of it — the bits of ``hoa.channel_stats(out)`` without its pass over the BEV
     (``ocrf_bev_pool_v2_nchw_panel_stats``)."""
     B, Z, Y, X, C = plan.shape
-    f32 = feat.float().contiguous()
-    _check_32bit_offsets(f32)
-    _lib.require_cuda(f32)
-    if f32.size(-1) != C:
-        raise _lib.OcrfHipError(f'feat has {f32.size(-1)} channels, the plan was built for {C}')
+    f32, = _fp32_operands(feat, channels=C)
     if not weights_ready:
         bev_pool_cell_weights(depth, plan)
     dev = f32.device
-    shape = (B, C, Z, Y, X) if layout == 0 else (B, Z * C, Y, X)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=dev)
-    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * C * Z * Y * X or out.device != dev:
-        raise _lib.OcrfHipError('out must be a contiguous fp32 tensor of B*C*Z*Y*X elements on the inputs\' device')
-    args = (C, plan.n_units, plan.units, plan.unit_slab, plan.panel_rows, plan.panel_nrows, plan.panel_cell_off,
+    out = _out_tensor(out, plan.shape, layout, dev)
+    args =(C, plan.n_units, plan.units, plan.unit_slab, plan.panel_rows, plan.panel_nrows, plan.panel_cell_off,
             plan.panel_voff, plan.cell_code, plan.cw, f32, out, B, Z, Y, X, int(layout), plan.arrive, plan.slabs, f32.numel() * 4)
     if stats is None:
         _lib.launch('ocrf_bev_pool_v2_nchw_panel', dev, *args)
@@ -563,10 +538,89 @@ def bev_pool_v2_collapsed(depth, feat, ranks_depth, ranks_feat, ranks_bev,
     view_transformer_ocrf.py:776-782), produced without the intermediate copies."""
     if _fusable(int(bev_feat_shape[-1])):
         return _FusedPool.apply(depth, feat, ranks_depth, ranks_feat, ranks_bev, bev_feat_shape,
-                                interval_starts, interval_lengths, 1)
+                                interval_starts, interval_lengths, 1, None, 'bev_pool_nchw')
     x = bev_pool_v2(depth, feat, ranks_depth, ranks_feat, ranks_bev, bev_feat_shape,
                     interval_starts, interval_lengths)
     return torch.cat(x.unbind(dim=2), 1)
+
+
+def panel_plan_args(which, backend, lss_mfma_group=2):
+    """``MfmaPoolPlan``'s unit arguments for the rank vectors of branch ``which`` ('lss' | 'ht').  The height-sampling ranks have
+    no heavy tiles (11 points per feature row and 8 x 8 tile): units of up to 8 panels.  The LSS ranks do (the block
+    beside the rig): units cut by estimated cost for the panel kernel, short units for the MFMA kernel, more slabs."""
+    if which == 'ht':
+        return dict(group=8)
+    return dict(group=8, unit_cost=8.0) if backend == 'panel' else dict(group=lss_mfma_group)
+
+
+class PoolPlan:
+    """Rank vectors of one bev_pool_v2 call, cached on the device, and the one statement of how such vectors are pooled
+    (``pool``): the rank-only half of the pooling is cached with them, built on first use."""
+
+    def __init__(self, ranks_bev, ranks_depth, ranks_feat, starts, lengths, bev_shape):
+        self.ranks_bev, self.ranks_depth, self.ranks_feat = ranks_bev, ranks_depth, ranks_feat
+        self.starts, self.lengths = starts, lengths
+        self.bev_shape = tuple(int(v) for v in bev_shape)      # (B, Z, Y, X, C)
+        self.device_plan = None                                # DevicePoolPlan, built on first use
+        self.mfma_plan = None                                  # MfmaPoolPlan, built on first use
+
+    @property
+    def n_points(self):
+        return int(self.ranks_bev.numel())
+
+    @property
+    def n_intervals(self):
+        return int(self.starts.numel())
+
+    def algorithmic_bytes(self, depth_numel, feat_numel):
+        """4*(depth + feat + 3*Np + 2*Nv + B*Z*Y*X*C)."""
+        out = 1
+        for v in self.bev_shape:
+            out *= v
+        return 4 * (depth_numel + feat_numel + 3 * self.n_points + 2 * self.n_intervals + out)
+
+    def route(self, backend):
+        """The kernel that pools these vectors when ``backend`` ('tile' | 'mfma' | 'panel') is asked for: 'unplanned'
+        without points, the tile kernel where the channel count is not a panel count."""
+        if not self.ranks_bev.numel():
+            return 'unplanned'
+        return backend if backend != 'tile' and _panel_channels(self.bev_shape[-1]) else 'tile'
+
+    def writes_stats(self, backend, layout=1):
+        """Whether that pooling can write the channel statistics (``bev_pool_v2_panel(..., stats=...)``)."""
+        return self.route(backend) == 'panel' and self.bev_shape[1] == 1 and layout in (0, 1)
+
+    def panel_plan(self, which, backend, lss_mfma_group=2):
+        """The ``MfmaPoolPlan`` of the MFMA / panel kernels: built once, with the arguments in force at its first use."""
+        if self.mfma_plan is None:
+            self.mfma_plan = MfmaPoolPlan(self.ranks_depth, self.ranks_feat, self.ranks_bev, self.bev_shape,
+                                          **panel_plan_args(which, backend, lss_mfma_group))
+        return self.mfma_plan
+
+    def pool(self, depth, feat, backend, which=None, lss_mfma_group=2, out=None, weights_ready=False, stats=None):
+        """-> (B, Z*C, Y, X): pooled BEV with Z collapsed into channels (view_transformer.py:194).  ``which`` /
+        ``lss_mfma_group``: see ``panel_plan_args``; ``out`` / ``weights_ready`` / ``stats`` as in ``bev_pool_v2_panel``.
+        The panel plan: unique feature rows of an 8 x 8 tile in panels of 48, cells = (voxel, row) pairs.  'panel': cells
+        walked out of LDS after a weight pre-pass (csrc/bev_pool_panel.hip); 'mfma': dense W . F panels on the matrix
+        cores (csrc/bev_pool_mfma.hip)."""
+        route = self.route(backend)
+        if stats is not None and not self.writes_stats(backend):
+            raise _lib.OcrfHipError('only the panel pooling (of Z == 1) writes channel statistics')
+        if route == 'unplanned':
+            res = bev_pool_v2_collapsed(depth, feat, self.ranks_depth, self.ranks_feat, self.ranks_bev, self.bev_shape,
+                                        self.starts, self.lengths)
+            if out is not None:
+                out.view_as(res).copy_(res)
+            return res
+        if route == 'tile':
+            if self.device_plan is None:
+                self.device_plan = DevicePoolPlan(self.ranks_depth, self.ranks_feat, self.ranks_bev, self.bev_shape,
+                                                  self.starts, self.lengths)
+            return bev_pool_v2_planned(depth, feat, self.device_plan, out=out)
+        plan = self.panel_plan(which, backend, lss_mfma_group)
+        if route == 'mfma':
+            return bev_pool_v2_mfma(depth, feat, plan, out=out)
+        return bev_pool_v2_panel(depth, feat, plan, out=out, weights_ready=weights_ready, stats=stats)
 
 
 class TRTBEVPoolv2(torch.autograd.Function):

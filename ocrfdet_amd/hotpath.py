@@ -17,30 +17,7 @@ from . import _lib, bevpool, gaussian_renderer, hoa, index_prep, raster_plan, sy
 from .diff_gaussian_rasterization import pack_cameras, rasterize_sets, rasterize_views
 
 
-class PoolPlan:
-    """Rank vectors of one bev_pool_v2 call, resident on the device."""
-
-    def __init__(self, ranks_bev, ranks_depth, ranks_feat, starts, lengths, bev_shape):
-        self.ranks_bev, self.ranks_depth, self.ranks_feat = ranks_bev, ranks_depth, ranks_feat
-        self.starts, self.lengths = starts, lengths
-        self.bev_shape = tuple(int(v) for v in bev_shape)      # (B, Z, Y, X, C)
-        self.device_plan = None                                # bevpool.DevicePoolPlan, built on first use
-        self.mfma_plan = None                                  # bevpool.MfmaPoolPlan, built on first use
-
-    @property
-    def n_points(self):
-        return int(self.ranks_bev.numel())
-
-    @property
-    def n_intervals(self):
-        return int(self.starts.numel())
-
-    def algorithmic_bytes(self, depth_numel, feat_numel):
-        """4*(depth + feat + 3*Np + 2*Nv + B*Z*Y*X*C)."""
-        out = 1
-        for v in self.bev_shape:
-            out *= v
-        return 4 * (depth_numel + feat_numel + 3 * self.n_points + 2 * self.n_intervals + out)
+PoolPlan = bevpool.PoolPlan
 
 
 _STREAMS = {}
@@ -114,7 +91,6 @@ class HotPath:
         if ht_pool_backend is None:
             ht_pool_backend = 'panel'
         assert ht_pool_backend in ('mfma', 'tile', 'panel') and lss_pool_backend in ('mfma', 'tile', 'panel')
-        self.lss_panel_unit_cost = 8.0
         self.ht_pool_backend = ht_pool_backend
         self.lss_pool_backend, self.lss_mfma_group = lss_pool_backend, int(lss_mfma_group)
         self.hoa_first = hoa_first
@@ -239,9 +215,8 @@ class HotPath:
     def _fused_stats(self):
         """The buffer the HT pooling fills with HOA-3's channel statistics, or None where they are a launch of their own:
         without HOA, with the per-step index preparation (``bev_pool_v2_nchw_dyn``) and with the tile / MFMA backends."""
-        C = self.ht.bev_shape[-1]
-        if (self.fuse_hoa_stats and self.cfg.hoa and self.index_prep_mode == 'cached' and self.ht_pool_backend == 'panel'
-                and C in (64, 80, 96, 128) and self.ht.n_points and self._hoa_stats is not None):
+        if (self.fuse_hoa_stats and self.cfg.hoa and self.index_prep_mode == 'cached' and self._hoa_stats is not None
+                and self.ht.writes_stats(self.ht_pool_backend)):
             return self._hoa_stats
         return None
 
@@ -483,48 +458,16 @@ class HotPath:
         feat = feat.permute(0, 1, 3, 4, 2).contiguous()
         return depth.to(self.device), feat.to(self.device)
 
-    def _panel_plan(self, plan):
-        if plan.mfma_plan is None:
-            backend = self.ht_pool_backend if plan is self.ht else self.lss_pool_backend
-            if plan is self.ht:
-                kw = dict(group=8)
-            elif backend == 'panel':
-                kw = dict(group=8, unit_cost=self.lss_panel_unit_cost)
-            else:
-                kw = dict(group=self.lss_mfma_group)
-            plan.mfma_plan = bevpool.MfmaPoolPlan(plan.ranks_depth, plan.ranks_feat, plan.ranks_bev, plan.bev_shape, **kw)
-        return plan.mfma_plan
+    def _branch(self, plan):
+        """(backend, branch) of ``plan``, read at call time; a plan object that is neither ``self.lss`` nor ``self.ht``
+        pools with the tile kernel."""
+        if plan is self.ht:
+            return self.ht_pool_backend, 'ht'
+        return (self.lss_pool_backend, 'lss') if plan is self.lss else ('tile', None)
 
     def pool(self, plan, depth, feat, out=None, weights_ready=False, stats=None):
-        """-> (B, Z*C, Y, X): pooled BEV with Z collapsed into channels (view_transformer.py:194).  The
-        rank vectors are cached, so the rank-only half of the pooling is too (bevpool.DevicePoolPlan).
-        ``out``: contiguous fp32 tensor to write into (a slice of a fused buffer).  ``stats``: panel backend only, see
-        ``bevpool.bev_pool_v2_panel``."""
-        if stats is not None and not (plan.n_points and plan.bev_shape[-1] in (64, 80, 96, 128) and
-                                      (self.ht_pool_backend if plan is self.ht else
-                                       self.lss_pool_backend if plan is self.lss else 'tile') == 'panel'):
-            raise _lib.OcrfHipError('only the panel pooling writes channel statistics')
-        if plan.n_points == 0:
-            res = bevpool.bev_pool_v2_collapsed(depth, feat, plan.ranks_depth, plan.ranks_feat,
-                                                plan.ranks_bev, plan.bev_shape, plan.starts, plan.lengths)
-            if out is not None:
-                out.view_as(res).copy_(res)
-            return res
-        backend = self.ht_pool_backend if plan is self.ht else (self.lss_pool_backend if plan is self.lss else 'tile')
-        if backend in ('mfma', 'panel') and plan.bev_shape[-1] in (64, 80, 96, 128):
-            # the panel plan (unique feature rows of an 8 x 8 tile in panels of 48; cells = (voxel, row) pairs).  'panel':
-            # cells walked out of LDS after a weight pre-pass (csrc/bev_pool_panel.hip); 'mfma': dense W . F panels on the
-            # matrix cores (csrc/bev_pool_mfma.hip).  The height-sampling ranks have no heavy tiles (11 points per feature
-            # row and 8x8 tile): units of up to 8 panels; the LSS ranks do (the block beside the rig): units cut by
-            # estimated cost ('panel') / short units ('mfma'), more slabs
-            self._panel_plan(plan)
-            if backend == 'mfma':
-                return bevpool.bev_pool_v2_mfma(depth, feat, plan.mfma_plan, out=out)
-            return bevpool.bev_pool_v2_panel(depth, feat, plan.mfma_plan, out=out, weights_ready=weights_ready, stats=stats)
-        if plan.device_plan is None:
-            plan.device_plan = bevpool.DevicePoolPlan(plan.ranks_depth, plan.ranks_feat, plan.ranks_bev, plan.bev_shape,
-                                                      plan.starts, plan.lengths)
-        return bevpool.bev_pool_v2_planned(depth, feat, plan.device_plan, out=out)
+        """``bevpool.PoolPlan.pool`` with this path's backend for ``plan`` -> (B, Z*C, Y, X)."""
+        return plan.pool(depth, feat, *self._branch(plan), self.lss_mfma_group, out, weights_ready, stats)
 
     def _camera_blocks(self):
         cfg, dev, args = self.cfg, self.device, self._calib_host
@@ -576,11 +519,9 @@ class HotPath:
             lss = bevpool.bev_pool_v2_device_counts(depth, feat, lv[1], lv[2], lv[0], self.lss.bev_shape, lv[3], lv[4], lc)
             ht = bevpool.bev_pool_v2_device_counts(depth, feat, hv[1], hv[2], hv[0], self.ht.bev_shape, hv[3], hv[4], hc)
             return lss, ht
-        C = self.lss.bev_shape[-1]
-        if (self.lss_pool_backend == 'panel' and self.ht_pool_backend == 'panel' and C in (64, 80, 96, 128)
-                and self.lss.n_points and self.ht.n_points):
+        if self.lss.route(self.lss_pool_backend) == 'panel' == self.ht.route(self.ht_pool_backend):
             # both poolings read the same depth tensor: ONE launch sums the cell weights of both plans
-            bevpool.bev_pool_cell_weights(depth, self._panel_plan(self.lss), self._panel_plan(self.ht))
+            bevpool.bev_pool_cell_weights(depth, self.lss.panel_plan('lss', 'panel'), self.ht.panel_plan('ht', 'panel'))
             return (self.pool(self.lss, depth, feat, weights_ready=True),
                     self.pool(self.ht, depth, feat, weights_ready=True, stats=ht_stats))
         return self.pool(self.lss, depth, feat), self.pool(self.ht, depth, feat, stats=ht_stats)

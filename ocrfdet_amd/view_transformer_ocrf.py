@@ -818,19 +818,12 @@ class OcRFViewTransformerFull(nn.Module):
         if (geo is self._geo and len(ranks) == 5 and ranks[0] is not None and not torch.is_grad_enabled()
                 and bevpool._fusable(bev_shape[-1])):
             plan = geo.plans.get(which)
-            panel = bev_shape[-1] in (64, 80, 96, 128)
-            if plan is None or plan.shape != tuple(int(v) for v in bev_shape):
-                rb, rd, rf, st, ln = ranks
-                if panel:
-                    # the same back end as HotPath's default: the panel latency kernel (csrc/bev_pool_panel.hip), 13-30 %
-                    # faster than the tile kernel; heavy LSS tiles cut by estimated cost
-                    plan = bevpool.MfmaPoolPlan(rd, rf, rb, bev_shape, group=8, unit_cost=8.0 if which == 'lss' else None)
-                else:
-                    plan = bevpool.DevicePoolPlan(rd, rf, rb, bev_shape, st, ln)
-                geo.plans[which] = plan
-            if panel:
-                return bevpool.bev_pool_v2_panel(depth, feat_cl, plan)
-            return bevpool.bev_pool_v2_planned(depth, feat_cl, plan)
+            if plan is None or plan.bev_shape != tuple(int(v) for v in bev_shape):
+                plan = geo.plans[which] = bevpool.PoolPlan(*ranks, bev_shape)
+            # HotPath's default back end through the same front end and plan arguments (the panel latency kernel, the tile
+            # kernel where the channel count is no panel count); here each pooling runs its own weight pre-pass and HOA-3's
+            # statistics stay a launch of their own
+            return plan.pool(depth, feat_cl, 'panel', which)
         return self._pool(ranks, depth, feat_cl, bev_shape)
 
     def get_lss_bev_feat(self, geo, depth, feat_cl):
@@ -865,7 +858,7 @@ class OcRFViewTransformerFull(nn.Module):
         fused = not self.training and not self._recording(depth, tran_feat, feat_channels_last)
         # Under autograd too the geometry stays on the device when the calibration is there (``device_geometry`` not False):
         # the rank vectors at their capacity with device-side lengths, in tensors of THIS forward (an autograd Function saves
-        # them), the poolings differentiated by ``_FusedPoolCounts``, the cameras staged from the device rows — a training
+        # them), the poolings differentiated by ``_FusedPool`` with counts, the cameras staged from the device rows — a training
         # forward then reads nothing back (the reference synchronises at :1086-1088, and this module did, once per forward,
         # until round 6: the GPU's tail of every iteration was exposed, ~1.5-2.4 ms at cfg2)
         on_dev = all(torch.is_tensor(t) and t.is_cuda for t in list(input[1:7]) + [input[11]])

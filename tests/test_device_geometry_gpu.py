@@ -151,7 +151,7 @@ def _setup(cuda):
 def test_training_forward_and_backward_read_nothing_back(cuda):
     """``module.train()`` with the calibration on the GPU (``device_geometry`` auto): the geometry stays on the device
     under autograd too — rank vectors at their capacity with device-side lengths in tensors of this forward, poolings
-    differentiated by ``_FusedPoolCounts``, cameras staged from the device rows — so forward + backward run without a single
+    differentiated by ``_FusedPool`` with counts, cameras staged from the device rows — so forward + backward run without a single
     synchronising call (the reference reads the calibration to the host once per forward, view_transformer_ocrf.py:1086-1088).
     Against the opted-out host formulation: same loss and gradients up to the handful of border samples that change cell."""
     cfg, m, inp, depth0, feat0 = _setup(cuda)
