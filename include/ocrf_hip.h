@@ -1330,6 +1330,55 @@ int ocrf_deform_taps(int H, int W, int base_h, int base_w, float off_h, float of
                      float *frac);
 
 /* ------------------------------------------------------------------------------------------
+ * Geometry distillation of OcRFDet4DVGGT (csrc/group_corr.hip): the group-wise correlation volume over a camera pair
+ * (mmdet3d/models/detectors/ocrfdet_vggt.py:205-216, build_cost_volume(method='group_corr')) and the two losses between
+ * two volumes (:476-480).  f32, no atomics, no memset, no host reads; repeated runs are bit-identical.
+ *
+ * Volume.  left, right: the two views, each B blocks of (C, H, W) contiguous floats, `batch_stride` floats from one
+ *   sample to the next: feats[:, 0] and feats[:, 1] of a contiguous (B, 2, C, H, W) tensor are left = feats,
+ *   right = feats + C * H * W, batch_stride = 2 * C * H * W, without a copy.  Cg = C / G.
+ *     out[b][g][d][h][w] = sum_{c < Cg} left[b][g Cg + c][h][w] * right[b][g Cg + c][h][max(w - d, 0)],  0 <= d < D;
+ *   out (B, G, D, H, W) contiguous.  The clamp is the only border rule (the reference's torch.clamp(idx - d, min=0)).
+ *   The sum runs over c ascending, one fmaf per term.
+ * ocrf_group_corr_forward: ONE launch; every element of out is written once.
+ * ocrf_group_corr_backward: two launches, both gathers:
+ *     grad_left[b][c][h][w]   = sum_d grad_out[b][g][d][h][w] * right[b][c][h][max(w - d, 0)]             (d ascending)
+ *     grad_right[b][c][h][w'] = sum over the (w, d) with max(w - d, 0) = w' of grad_out[b][g][d][h][w] * left[b][c][h][w]
+ *       (w' > 0: w = w' + d < W, d ascending; w' = 0: every w <= min(d, W - 1), d ascending, w ascending inside a d),
+ *   grad_left / grad_right laid out like left / right with `grad_batch_stride` (the two halves of a (B, 2, C, H, W)
+ *   gradient); every element written once.
+ * Limits: every size positive, C a multiple of G, 1 <= D <= 16, a stride no smaller than C * H * W, and both views, the
+ *   volume and the farthest element a stride reaches below 2^31 elements (the kernels index a sample with int); anything
+ *   else, a NULL pointer included, returns hipErrorInvalidValue and launches nothing.
+ *
+ * Losses, for s, t (B, n) contiguous:
+ *     *loss_smooth = 0.1 * mean(smooth_l1(s - t, beta = 1))
+ *     *loss_cos    = 1 - mean_b(s_b . t_b / (max(|s_b|, 1e-8) * max(|t_b|, 1e-8)))     (torch's cosine_similarity)
+ * ocrf_kd_losses_forward: two launches.  The sums (smooth-L1 and, per sample, s.t, s.s, t.t) are accumulated in double in
+ *   a fixed two-stage order: per-workgroup partials in `workspace` (ocrf_kd_losses_workspace_bytes, 8-byte aligned),
+ *   then one workgroup adds them and rounds each result to float32 once.  sums (B, 3) doubles receives (s.t, s.s, t.t)
+ *   per sample, for the backward.
+ * ocrf_kd_losses_backward: one elementwise launch.  grad_smooth, grad_cos: device floats, the gradients of the two
+ *   results.  With ns = |s_b|, hs = max(ns, 1e-8), ht alike:
+ *     grad_s = 0.1 clamp(s - t, -1, 1) / (B n) * grad_smooth
+ *              - grad_cos / B * (t / (hs ht) - [ns > 1e-8] (s_b . t_b) s / (hs^2 ht ns)),
+ *   what torch's autograd gives through the clamp (a sample with s_b = 0 gets -t / (1e-8 ht) / B); evaluated in double,
+ *   rounded once.  t gets no gradient.
+ * Limits: B in [1, 65535], n >= 1, B * n < 2^31, no NULL pointer, a workspace of the queried size; anything else
+ *   returns hipErrorInvalidValue (the size query: 0) and launches nothing.
+ */
+int ocrf_group_corr_forward(int B, int C, int H, int W, int G, int D, const float *left, const float *right,
+                            long long batch_stride, float *out, ocrf_stream_t stream);
+int ocrf_group_corr_backward(int B, int C, int H, int W, int G, int D, const float *grad_out, const float *left,
+                             const float *right, long long batch_stride, float *grad_left, float *grad_right,
+                             long long grad_batch_stride, ocrf_stream_t stream);
+size_t ocrf_kd_losses_workspace_bytes(int B, long long n);
+int ocrf_kd_losses_forward(int B, long long n, const float *s, const float *t, float *loss_smooth, float *loss_cos,
+                           double *sums, void *workspace, size_t workspace_bytes, ocrf_stream_t stream);
+int ocrf_kd_losses_backward(int B, long long n, const float *s, const float *t, const double *sums,
+                            const float *grad_smooth, const float *grad_cos, float *grad_s, ocrf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-kernel device timer (measurement aid for bench.py; not part of the reference's surface)
  * ------------------------------------------------------------------------------------------
  * While a timer is armed for kernel id K, every launch of K inside the library is bracketed by
@@ -1448,7 +1497,13 @@ enum {
   OCRF_K_POINT_LABELS_MARK = 136,     /* point_labels_mark_kernel */
   OCRF_K_POINT_LABELS_RESOLVE = 137,  /* point_labels_resolve_kernel */
   OCRF_K_DEFORM_IM2COL = 138,         /* deform_im2col_kernel */
-  OCRF_K_DEFORM_COL2IM = 139          /* deform_col2im_kernel */
+  OCRF_K_DEFORM_COL2IM = 139,         /* deform_col2im_kernel */
+  OCRF_K_GROUP_CORR = 140,            /* group_corr_forward_kernel<DT> */
+  OCRF_K_GROUP_CORR_GRAD_LEFT = 141,  /* group_corr_grad_left_kernel<DT> */
+  OCRF_K_GROUP_CORR_GRAD_RIGHT = 142, /* group_corr_grad_right_kernel<DT> */
+  OCRF_K_KD_PARTIAL = 143,            /* kd_partial_kernel */
+  OCRF_K_KD_FINAL = 144,              /* kd_final_kernel */
+  OCRF_K_KD_BWD = 145                 /* kd_backward_kernel */
 };
 const char *ocrf_kernel_name(int kernel_id);           /* symbol as rocprofv3 prints it */
 /* Diagnostic: a one-thread kernel that stores the device's constant-rate clock (wall_clock64, 100 MHz)

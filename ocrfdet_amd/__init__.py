@@ -37,6 +37,10 @@ Drop-in mirrors of the reference's Python surface for that path (and nothing els
   mmcv.ops DeformConv2d, DeformConv2dPack         ocrfdet_amd.deform_conv (deform_conv2d, deform_conv2d_torch,
   (type 'DCN'), deform_conv2d                     DeformConv2d, DeformConv2dPack, build_dcn; opt-in in depthnet
                                                   through NATIVE_DCN, in center_head through DCNSeparateHead)
+  ...detectors.ocrfdet_vggt.OcRFDet4DVGGT,        ocrfdet_amd.detector.OcRFDet4DVGGT and ocrfdet_amd.distill
+  ...detectors.bevdet_vggt.CrossAttentionAlign    (build_cost_volume, group_corr_volume, group_corr_volume_torch,
+                                                  kd_losses, kd_losses_torch, CrossAttentionAlign, resize_img,
+                                                  get_pair_indices; the VGGT teacher itself is passed in)
   ==============================================  =================================================
 
 Every op calls the C ABI of ``csrc/libocrf_hip.so`` (``include/ocrf_hip.h``) through ctypes with
@@ -49,7 +53,9 @@ _LAZY = ('ResNet', 'CustomFPN', 'ImageEncoder')
 _LAZY_TEMPORAL = ('feature_transform', 'shift_feature', 'shift_feature_torch', 'align_and_cat', 'gen_grid',
                   'shift_feature_method')
 _LAZY_OPTIM = ('FusedAdamW', 'ModelEMA', 'paramwise_groups')
-_LAZY_DETECTOR = ('OcRFDet4D', 'prepare_inputs', 'frame_poses', 'frame_poses_torch')
+_LAZY_DETECTOR = ('OcRFDet4D', 'OcRFDet4DVGGT', 'prepare_inputs', 'frame_poses', 'frame_poses_torch')
+_LAZY_DISTILL = ('build_cost_volume', 'group_corr_volume', 'group_corr_volume_torch', 'kd_losses', 'kd_losses_torch',
+                 'CrossAttentionAlign')
 _LAZY_INPUTS = ('sample_augmentation', 'post_homography', 'sample_bda_augmentation', 'bev_transform',
                 'assemble_img_inputs', 'prepare_images', 'prepare_images_torch', 'point_label_maps',
                 'point_label_maps_torch')
@@ -71,6 +77,9 @@ def __getattr__(name):
     if name in _LAZY_DETECTOR:
         from . import detector
         return getattr(detector, name)
+    if name in _LAZY_DISTILL:
+        from . import distill
+        return getattr(distill, name)
     if name in _LAZY_INPUTS:
         from . import inputs
         return getattr(inputs, name)

@@ -188,6 +188,12 @@ const char* ocrf_kernel_name(int kernel_id) {
     case OCRF_K_POINT_LABELS_RESOLVE: return "point_labels_resolve_kernel";
     case OCRF_K_DEFORM_IM2COL: return "deform_im2col_kernel";
     case OCRF_K_DEFORM_COL2IM: return "deform_col2im_kernel";
+    case OCRF_K_GROUP_CORR: return "group_corr_forward_kernel<*>";
+    case OCRF_K_GROUP_CORR_GRAD_LEFT: return "group_corr_grad_left_kernel<*>";
+    case OCRF_K_GROUP_CORR_GRAD_RIGHT: return "group_corr_grad_right_kernel<*>";
+    case OCRF_K_KD_PARTIAL: return "kd_partial_kernel";
+    case OCRF_K_KD_FINAL: return "kd_final_kernel";
+    case OCRF_K_KD_BWD: return "kd_backward_kernel";
     default: return "";
   }
 }

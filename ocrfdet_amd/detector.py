@@ -382,3 +382,171 @@ class OcRFDet4D(nn.Module):
         if return_loss:
             return self.forward_train(**kwargs)
         return self.simple_test(**kwargs)
+
+
+# ------------------------------------------------------------------------------------------------ geometry distillation
+LOSS_KEYS_KD = ('loss_Smoothl1_KD', 'loss_cos_KD')
+
+
+class OcRFDet4DVGGT(OcRFDet4D):
+    """``OcRFDet4DVGGT`` of configs/ocrfdet/ocrfdet_vggt.py (mmdet3d/models/detectors/ocrfdet_vggt.py:148-498):
+    ``OcRFDet4D`` plus a geometry-distillation branch on the key frame, in training only.  A frozen teacher
+    (``aggregator``) turns the images of a camera pair into patch tokens, the trainable ``aligner``
+    (``distill.CrossAttentionAlign``) maps the student's image feature of that pair onto the teacher's grid, a group-wise
+    correlation volume is built from each, and ``loss_Smoothl1_KD`` / ``loss_cos_KD`` compare the two volumes.
+
+    On top of ``OcRFDet4D``'s constructor keys:
+
+    * ``aggregator``: the teacher, any ``nn.Module`` called as VGGT's ``Aggregator`` is: ``aggregator(images (B, 2, 3,
+      h, w)) -> (list of token tensors, patch_start_idx)``, the last list entry (B, 2, patch_start_idx + (h // 14) *
+      (w // 14), vit_dim).  VGGT itself is not part of this package.  It is registered as ``self.aggregator`` (so
+      ``aggregator.*`` keys of a checkpoint line up), its parameters get ``requires_grad=False`` and it stays in
+      ``eval()`` through ``train()``.  ``None``: the detector builds and tests, and a training forward raises.
+    * ``aligner``: a dict for ``CrossAttentionAlign`` or the module.
+    * ``distill``: ``max_disp`` and ``groups`` of the volumes, ``resize`` (h, w) of the teacher's images and its
+      ``patch_size``.
+
+    As in the reference, the student's pair feature is formed under ``no_grad``: the two losses train the aligner, not
+    the image encoder.  ``fused_distill`` (class attribute, default ``distill.FUSED_DISTILL_DEFAULT``) selects the HIP
+    kernels for the volumes and the losses; False takes the torch formulations."""
+
+    fused_distill = None
+
+    def __init__(self, *args, aggregator=None, aligner=None, distill=None, type=None, **kwargs):
+        if type not in (None, 'OcRFDet4DVGGT'):
+            raise NotImplementedError(f'type {type}: only OcRFDet4DVGGT')
+        super().__init__(*args, **kwargs)
+        from .distill import CrossAttentionAlign
+        if aggregator is not None and not isinstance(aggregator, nn.Module):
+            raise NotImplementedError('aggregator: pass the teacher as an nn.Module (VGGT is not part of this package)')
+        self.aggregator = aggregator
+        if aggregator is not None:
+            aggregator.requires_grad_(False).eval()
+        self.aligner = _build(dict(res_dim=512, vit_dim=2048, num_heads=8) if aligner is None else aligner,
+                              'CrossAttentionAlign', CrossAttentionAlign)
+        self.distill = dict(max_disp=4, groups=64, resize=(294, 518), patch_size=14)
+        self.distill.update(distill or {})
+
+    def train(self, mode=True):
+        super().train(mode)
+        if self.aggregator is not None:
+            self.aggregator.eval()                   # the teacher is frozen: no batch statistics, no dropout
+        return self
+
+    def distill_volumes(self, img, x):
+        """ocrfdet_vggt.py:243-268: ``[cost_volume_t, cost_volume_s]`` for a drawn camera pair, from the key frame's
+        images ``img`` (B, N, 3, H, W) and image feature ``x`` (B, N, C, h, w)."""
+        from . import distill as D
+        if self.aggregator is None:
+            raise RuntimeError('OcRFDet4DVGGT was built with aggregator=None: a training forward needs the teacher '
+                               '(pass VGGT\'s Aggregator, or any module with its call, as `aggregator`)')
+        cfg = self.distill
+        i1, i2 = D.get_pair_indices()
+        with torch.no_grad():
+            x_s = torch.stack([x[:, i1], x[:, i2]], dim=1)
+            # the reference resizes all six images and takes two; resizing works image by image
+            x_t = D.resize_img(torch.stack([img[:, i1], img[:, i2]], dim=1).detach(), *cfg['resize'])
+            B, _, _, H, W = x_t.shape
+            tokens, patch_start_idx = self.aggregator(x_t)
+            token_img = tokens[-1][:, :, patch_start_idx:]
+            vit_dim = token_img.shape[-1]
+            # channel-major in memory (the permuted tokens are a view): the volume and the aligner read (h, w) planes
+            token_img = token_img.reshape(B * 2, -1, vit_dim).permute(0, 2, 1).reshape(
+                B, 2, vit_dim, H // cfg['patch_size'], W // cfg['patch_size']).contiguous()
+        aligned = self.aligner(x_s, token_img)
+        return [D.build_cost_volume(f, max_disp=cfg['max_disp'], method='group_corr', groups=cfg['groups'],
+                                    fused=self.fused_distill) for f in (token_img, aligned)]
+
+    # ---------------------------------------------------------------- ocrfdet_vggt.py:232-295
+    def prepare_bev_feat(self, img, rot, tran, sensor2keyego, ego2global, intrin, post_rot, post_tran, bda, mlp_input,
+                         feat_prev_iv, k2s_sensor, extra_ref_frame, imgs_wo_norm, imgs_wo_aug, c2w, key_frame=False):
+        """``OcRFDet4D.prepare_bev_feat`` with a sixth result: the two volumes for the key frame in training, else
+        None."""
+        if extra_ref_frame:
+            return None, None, None, self.extract_stereo_ref_feat(img), None, None
+        x, stereo_feat = self.image_encoder(img, stereo=True)
+        F_ts = self.distill_volumes(img, x) if self.training and key_frame else None
+        vt = self.img_view_transformer
+        metas = dict(k2s_sensor=k2s_sensor, intrins=intrin, post_rots=post_rot, post_trans=post_tran,
+                     frustum=vt.cv_frustum.to(x), cv_downsample=4, downsample=vt.downsample,
+                     grid_config=vt.grid_config, cv_feat_list=[feat_prev_iv, stereo_feat])
+        bev_feat, depth, bev_mask, extras = vt(
+            [x, rot, tran, intrin, post_rot, post_tran, bda, mlp_input, img, imgs_wo_norm, imgs_wo_aug, c2w], metas)
+        if self.pre_process:
+            bev_feat = self.pre_process_net(bev_feat)[0]
+        return bev_feat, depth, bev_mask, stereo_feat, extras, F_ts
+
+    # ---------------------------------------------------------------- ocrfdet_vggt.py:328-401
+    def extract_img_feat(self, img, img_metas=None, pred_prev=False, sequential=False, **kwargs):
+        """``OcRFDet4D.extract_img_feat`` with the key frame marked for ``prepare_bev_feat``; in training the result
+        carries ``F_ts = [cost_volume_t, cost_volume_s]`` as a last element."""
+        if sequential:
+            return self.extract_img_feat_sequential(img, **kwargs)
+        if pred_prev:
+            raise NotImplementedError('pred_prev: the reference asserts False here')
+        (imgs, rots, trans, intrins, post_rots, post_trans, bda, sensor2keyegos, ego2globals, curr2adjsensor,
+         imgs_wo_norm, imgs_wo_aug, c2ws), mlp_inputs = self.prepare_inputs(img, stereo=True)
+        bev_feat_list = []
+        depth_key_frame = bev_mask_key_frame = extras = F_ts = None
+        feat_prev_iv = None
+        for fid in range(self.num_frame - 1, -1, -1):
+            key_frame = fid == 0
+            extra_ref_frame = fid == self.num_frame - self.extra_ref_frames
+            if not (key_frame or self.with_prev):
+                continue
+            sensor2keyego, ego2global = sensor2keyegos[fid], ego2globals[fid]
+            if self.align_after_view_transfromation:
+                sensor2keyego, ego2global = sensor2keyegos[0], ego2globals[0]
+            inputs_curr = (imgs[fid], rots[fid], trans[fid], sensor2keyego, ego2global, intrins[fid], post_rots[fid],
+                           post_trans[fid], bda, mlp_inputs[fid], feat_prev_iv, curr2adjsensor[fid], extra_ref_frame,
+                           imgs_wo_norm[fid], imgs_wo_aug[fid], c2ws[fid], key_frame)
+            if key_frame:
+                bev_feat, depth_key_frame, bev_mask_key_frame, feat_curr_iv, extras, F_ts = \
+                    self.prepare_bev_feat(*inputs_curr)
+            else:
+                with torch.no_grad():
+                    bev_feat, _, _, feat_curr_iv, _, _ = self.prepare_bev_feat(*inputs_curr)
+            if not extra_ref_frame:
+                bev_feat_list.append(bev_feat)
+            feat_prev_iv = feat_curr_iv
+        n_adj = self.num_frame - self.extra_ref_frames - 1
+        if not self.with_prev:
+            key = bev_feat_list[0]
+            zeros = key.new_zeros((key.shape[0], key.shape[1] * n_adj) + tuple(key.shape[2:]))
+            bev_feat = torch.cat([zeros, key], dim=1)
+        elif self.align_after_view_transfromation:
+            vt = self.img_view_transformer
+            frame_ids = [self.num_frame - 2 - k for k in range(self.num_frame - 2)] + [0]
+            bev_feat = temporal.align_and_cat(bev_feat_list, frame_ids, sensor2keyegos, bda, vt.grid_interval,
+                                              vt.grid_lower_bound, fused=self.fused_align)
+        else:
+            bev_feat = torch.cat(bev_feat_list, dim=1)
+        x = self.bev_encoder(bev_feat)
+        if self.training:
+            return [x], depth_key_frame, bev_mask_key_frame, extras, F_ts
+        return [x], depth_key_frame, bev_mask_key_frame
+
+    # ---------------------------------------------------------------- ocrfdet_vggt.py:436-498
+    def forward_train(self, points=None, img_metas=None, gt_bboxes_3d=None, gt_labels_3d=None, gt_labels=None,
+                      gt_bboxes=None, img_inputs=None, proposals=None, gt_bboxes_ignore=None, **kwargs):
+        """``OcRFDet4D.forward_train``'s dict with ``loss_Smoothl1_KD`` and ``loss_cos_KD`` after the neck's five, where
+        the reference puts them."""
+        from .distill import kd_losses
+        gt_depth, gt_semantic, gt_bev_mask = kwargs.pop('gt_depth'), kwargs.pop('gt_semantic'), kwargs.pop('gt_bev_mask')
+        img_feats, _, depth, bev_mask, extras, F_ts = self.extract_feat(points, img=img_inputs, img_metas=img_metas,
+                                                                        **kwargs)
+        (render_imgs, gt_images, render_image_G_all, render_image_N_all, opacity_alpha_view, cam_idx_list, render_depth,
+         render_depth_G_all, render_depth_N_all) = extras
+        vt = self.img_view_transformer
+        values = vt.get_loss(depth, bev_mask[1], gt_depth, gt_semantic, gt_bboxes, cam_idx_list, render_imgs, gt_images,
+                             render_image_G_all, render_image_N_all, render_depth, render_depth_G_all,
+                             render_depth_N_all)
+        losses = dict(zip(LOSS_KEYS_NECK, values))
+        # the reference calls smooth_l1_loss(F_ts[0], F_ts[1]): both losses are symmetric in their operands, and the
+        # student's volume, F_ts[1], is the one a gradient flows into
+        losses.update(zip(LOSS_KEYS_KD, kd_losses(F_ts[1], F_ts[0], fused=self.fused_distill)))
+        if opacity_alpha_view is not None:
+            losses.update(vt.prob.get_bev_opacity_loss(gt_bev_mask, opacity_alpha_view.squeeze(1)))
+        losses.update(vt.prob.get_bev_mask_loss(gt_bev_mask, bev_mask[0]))
+        losses.update(self.forward_pts_train(img_feats, gt_bboxes_3d, gt_labels_3d, img_metas, gt_bboxes_ignore))
+        return losses
