@@ -993,9 +993,9 @@ int ocrf_bn_act_backward_bf16(int N, int C, int H, int W, const unsigned short *
  *   grid_config['depth'][0:2]; Wf, Hf, D: feature-map size and depth bins
  * outputs as above with ranks_bev = b*n_pillars + pillar; inside a pillar the order is (camera,
  * height) ascending = the reference's flattening order under a stable sort.
-  * The workspace holds the look-back states of the single-launch prefix sums: one call at a time per workspace
- * (two calls that share it on different streams overwrite each other's states; a wave that waits ~a second for a
- * predecessor traps instead of spinning for ever).
+ * The workspace holds the look-back states of the single-launch prefix sums: one call at a time per workspace
+ * (two calls that share it on different streams overwrite each other's states; a tile that waits ~a second for a
+ * predecessor gives up instead of spinning for ever, and the call leaves counts = -1).
  */
 int ocrf_lss_prepare(int B, int N, int D, int H, int W, const float *frustum, const float *cams,
                      const float *grid_lower_host, const float *grid_interval_host, int gx, int gy, int gz,
@@ -1519,6 +1519,16 @@ int ocrf_diag_stamp(unsigned long long *slot, void *stream);
 int ocrf_diag_plan_stats(unsigned long long *buf);
 int ocrf_diag_plan_resident(void); /* workgroups the persistent sorted blend launches (occupancy API x CUs) */
 int ocrf_diag_where(int n_blocks, unsigned *out, int spin_ticks, void *stream);
+/* Diagnostic: the library's stable radix sort (csrc/radix_sort.hip) on its own.  n device keys below 2^key_bits
+ * (key_bits 1 .. 32; `keys` is clobbered) leave as out_keys ascending and out_ids = their original positions, ascending
+ * among equal keys.  ocrf_diag_radix_sort_states (host pointers for the three results): where in the workspace the call
+ * leaves the look-back state blocks of its n_states passes, stride_words 64-bit words apart; bit 63 of a block's first
+ * word says that pass's scan gave up. */
+int ocrf_diag_radix_sort(unsigned *keys, int n, int key_bits, unsigned *out_keys, int *out_ids, void *workspace,
+                         size_t workspace_bytes, ocrf_stream_t stream);
+size_t ocrf_diag_radix_sort_workspace_bytes(int n);
+int ocrf_diag_radix_sort_states(void *workspace, int n, int key_bits, size_t *offset_bytes, int *n_states,
+                                long *stride_words);
 /* HIP streams for the hot path's chains (host pointers): cu_mask (n_words x 32 bits, NULL = every CU) restricts the
  * stream's kernels to those compute units (hipExtStreamCreateWithCUMask); without a mask `priority` is the HIP stream
  * priority (lower = more urgent).  The stream is non-blocking w.r.t. the legacy default stream. */

@@ -11,30 +11,28 @@
 // forward.  Here one kernel evaluates the per-point arithmetic — written as the same separate
 // float32 multiplies and adds, k ascending, fp-contract off, IEEE division, so the voxel indices
 // are bit-exact against vectors dumped from the reference — and
-//   * LSS: the points are ordered by voxel with an LSD radix sort written for this key shape
-//     (keys are voxel ids: 17-20 bits -> 2 passes of 9 bits up to 262 144 voxels, 3 beyond; stable,
-//     so the order inside an interval is ascending point index — deterministic where the
-//     reference's argsort is not); interval starts / lengths come from one binary search per voxel;
+//   * LSS: the points are ordered by voxel with the library's LSD radix sort (radix_sort.hip; keys are
+//     voxel ids: 17-20 bits -> 2 passes of 9 bits up to 262 144 voxels, 3 beyond; stable, so the order
+//     inside an interval is ascending point index — deterministic where the reference's argsort is
+//     not); interval starts / lengths come from one binary search per voxel;
 //   * HT: the key is the pillar itself and a pillar's candidates are its (camera, height) pairs, so
 //     no sort is needed at all: validity bits per (camera, pillar), totals per pillar, one scan
 //     over the pillars, emit in (camera, height) order.
-// Every prefix sum is a single launch (decoupled look-back over ticket-ordered tiles): 18 launches per LSS
-// preparation became 10, 7 per HT preparation 5.
+// Every prefix sum is a single launch (decoupled look-back over ticket-ordered tiles, lookback_scan.h): 18
+// launches per LSS preparation became 10, 7 per HT preparation 5.
 // Tiny per-camera algebra (3x3 inverses and products) stays on the host, as the same torch calls the
-// reference makes; the kernels take the resulting per-camera blocks.
+// reference makes (or runs in geom_blocks_kernel below); the kernels take the resulting per-camera blocks.
 #include <hip/hip_runtime.h>
 
 #include "launch.h"
+#include "lookback_scan.h"
 #include "ocrf_hip.h"
-#include "radix_emit.h"
+#include "radix_sort.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kItems = 8;                     // keys per thread and radix pass
-constexpr int kChunk = kBlock * kItems;       // 2048 keys per workgroup
-constexpr int kRadixBits = 9;
-constexpr int kBins = 1 << kRadixBits;        // 512
+using ocrf::kBins;
+static_assert(kChunk == ocrf::kSortChunk, "lss_keys_hist_kernel histograms the sort's chunks");
 
 struct LssCam {       // 33 floats per camera-frame, see ocrf_hip.h
   float inv_post[9], combine[9], post_trans[3], trans[3], bda[9];
@@ -118,276 +116,6 @@ __global__ __launch_bounds__(kBlock) void lss_keys_hist_kernel(
   }
   __syncthreads();
   for (int d = threadIdx.x; d < kBins; d += kBlock) table[(long)d * n_wg + blockIdx.x] = s_hist[d];
-}
-
-// ---------------------------------------------------------------------------------------------
-// LSD radix sort, one 9-bit digit per pass: histogram -> exclusive scan of the [digit][workgroup]
-// table -> stable scatter.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void radix_hist_kernel(const unsigned* __restrict__ keys, int n, int shift,
-                                                            int n_wg, int* __restrict__ table) {
-  __shared__ int s_hist[kBins];
-  for (int i = threadIdx.x; i < kBins; i += kBlock) s_hist[i] = 0;
-  __syncthreads();
-  const int base = blockIdx.x * kChunk;
-  // the thread's keys in ONE round trip (clamped addresses; `if (i < n) load` per key was a branch and a wait per key)
-  unsigned key[kItems];
-#pragma unroll
-  for (int it = 0; it < kItems; ++it) key[it] = keys[min(base + it * kBlock + (int)threadIdx.x, n - 1)];
-#pragma unroll
-  for (int it = 0; it < kItems; ++it) {
-    const int i = base + it * kBlock + threadIdx.x;
-    if (i < n) atomicAdd(&s_hist[(key[it] >> shift) & (kBins - 1)], 1);
-  }
-  __syncthreads();
-  for (int d = threadIdx.x; d < kBins; d += kBlock) table[(long)d * n_wg + blockIdx.x] = s_hist[d];
-}
-
-// exclusive prefix of v over the 256 threads of the workgroup (each thread of a scan owns 8 consecutive
-// values, so a wave touches 2 KB of contiguous memory per load)
-template <typename T>
-__device__ __forceinline__ T block_exclusive(T v, T* s_wave, T* block_total) {
-  // exclusive prefix of v over the 256 threads of the workgroup
-  const int lane = threadIdx.x % 64, wave = threadIdx.x / 64;
-  T inc = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const T o = __shfl_up(inc, off);
-    if (lane >= off) inc += o;
-  }
-  if (lane == 63) s_wave[wave] = inc;
-  __syncthreads();
-  T base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < kBlock / 64; ++w) {
-    const T c = s_wave[w];
-    if (w < wave) base += c;
-    tot += c;
-  }
-  if (block_total) *block_total = tot;
-  return base + inc - v;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Single-launch prefix sums: decoupled look-back over TICKET-ordered tiles.  state[0] is the ticket
-// counter, state[1 + t] the 64-bit word of tile t: bits 63:62 = 0 nothing yet | 1 the tile's own sum |
-// 2 its inclusive prefix, bits 61:0 the value — one word, written and read with agent-scope atomics,
-// so a reader never sees a value without its status.  A workgroup takes the next ticket before it
-// does anything else: the tiles it may wait for hold smaller tickets, i.e. are already running —
-// every wave reaches its exit whatever the scheduling order.  `state` must be zero before the launch.
-// ---------------------------------------------------------------------------------------------
-constexpr unsigned long long kLbValue = (1ull << 62) - 1;
-
-__device__ __forceinline__ void lb_publish(unsigned long long* state, int tile, unsigned status, unsigned long long v) {
-  __hip_atomic_store(state + 1 + tile, ((unsigned long long)status << 62) | v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// ticket of this workgroup (uniform); contains a barrier
-__device__ __forceinline__ int lb_ticket(unsigned long long* state, int* s_tile) {
-  if (threadIdx.x == 0) *s_tile = (int)atomicAdd(reinterpret_cast<unsigned*>(state), 1u);
-  __syncthreads();
-  return __builtin_amdgcn_readfirstlane(*s_tile);      // known-uniform: what depends on it stays in SGPRs
-}
-
-template <int NW = kBlock / 64>
-struct LbShared {
-  unsigned long long inc[NW], none[NW], sum[NW], run;
-};
-
-// exclusive prefix of this tile given its own sum `tot` (uniform).  All 64 NW threads call; contains barriers.
-// The look-back reads 64 NW predecessors per round (thread i reads tile hi - i): an agent-scope load is a
-// round trip to memory, and while every tile still holds only its own sum a tile t needs ~t / (2 kBlock) rounds.
-template <int NW>
-__device__ __forceinline__ unsigned long long lb_tile_prefix(unsigned long long* state, int tile, unsigned long long tot,
-                                                             LbShared<NW>* sh) {
-  constexpr int kThreads = NW * 64;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) {
-    lb_publish(state, tile, tile == 0 ? 2u : 1u, tot);
-    sh->run = 0;
-  }
-  int hi = tile - 1;
-  int spins = 0;
-  while (hi >= 0) {                                   // uniform: hi, and the decisions below, are the same everywhere
-    const int j = hi - tid;
-    const unsigned long long w = j >= 0 ? __hip_atomic_load(state + 1 + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                        : (2ull << 62);                 // before tile 0: inclusive prefix 0
-    const unsigned status = (unsigned)(w >> 62);
-    const unsigned long long inc = __ballot(status == 2), none = __ballot(status == 0);
-    if (lane == 0) { sh->inc[wave] = inc; sh->none[wave] = none; }
-    __syncthreads();
-    // nearest predecessor with a full prefix, as a thread index; everything nearer must at least hold its sum
-    int first = kThreads;
-    bool wait = false;
-#pragma unroll
-    for (int k = 0; k < NW; ++k) {
-      if (first < kThreads) break;
-      const unsigned long long i = sh->inc[k], n = sh->none[k];
-      const int f = i ? __ffsll((long long)i) - 1 : 64;
-      const unsigned long long need = f >= 63 ? ~0ull : ((2ull << f) - 1ull);
-      wait = wait || (n & need) != 0;
-      if (f < 64) first = k * 64 + f;
-    }
-    __syncthreads();                                  // sh->inc / none are rewritten by the next round
-    if (wait) {
-      // Every tile this one waits for holds a smaller ticket and is running, so the wait ends within microseconds —
-      // unless the state words are being overwritten, e.g. by a second call sharing this scratch on another stream.
-      // A wave must not spin on a shared GPU for ever: after ~a second the kernel traps (the launch fails loudly).
-      // A wave must not spin on a shared GPU for ever, and a trap would take the whole process down: after ~a second
-      // the tile gives up, raises the error bit of the state block (bit 63 of word 0; the ticket counter is the low
-      // half) and carries on with what it has — the call's last kernel turns the bit into counts = -1, which the
-      // poolings read as "no points" and the host wrappers as an OcrfHipError.
-      if (++spins > (1 << 20)) {
-        if (tid == 0) atomicOr(state, 1ull << 63);
-        break;
-      }
-      __builtin_amdgcn_s_sleep(2);
-      continue;                                       // something nearer than `first` is unpublished: read again
-    }
-    unsigned long long v = tid <= first ? (w & kLbValue) : 0ull;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    if (lane == 0) sh->sum[wave] = v;
-    __syncthreads();
-    if (tid == 0) {
-      unsigned long long r = sh->run;
-#pragma unroll
-      for (int k = 0; k < NW; ++k) r += sh->sum[k];
-      sh->run = r;
-    }
-    if (first < kThreads) break;
-    hi -= kThreads;
-  }
-  __syncthreads();
-  const unsigned long long prefix = sh->run;
-  if (tid == 0 && tile > 0) lb_publish(state, tile, 2u, prefix + tot);
-  return prefix;
-}
-
-inline size_t lb_state_bytes(long n_tiles) { return ((size_t)n_tiles + 1) * 8; }
-
-// in-place exclusive scan of n non-negative values (sums < 2^62), one launch of ceil(n / kChunk) workgroups
-template <typename T>
-__global__ __launch_bounds__(kBlock) void scan_lookback_kernel(T* __restrict__ data, long n, T* __restrict__ total,
-                                                               unsigned long long* __restrict__ state) {
-  __shared__ T s_wave[kBlock / 64];
-  __shared__ int s_tile;
-  __shared__ LbShared<> s_lb;
-  const int tile = lb_ticket(state, &s_tile);
-  const long base = (long)tile * kChunk + (long)threadIdx.x * kItems;
-  T v[kItems];
-  T sum = 0;
-#pragma unroll
-  for (int i = 0; i < kItems; ++i) {
-    v[i] = base + i < n ? data[base + i] : (T)0;
-    sum += v[i];
-  }
-  T tot;
-  const T local = block_exclusive<T>(sum, s_wave, &tot);
-  const unsigned long long prefix = lb_tile_prefix(state, tile, (unsigned long long)tot, &s_lb);
-  T run = (T)prefix + local;
-#pragma unroll
-  for (int i = 0; i < kItems; ++i) {
-    if (base + i < n) data[base + i] = run;
-    run += v[i];
-  }
-  if (total && tile == (int)gridDim.x - 1 && threadIdx.x == 0) *total = (T)prefix + tot;
-}
-
-template <typename T>
-inline void scan_exclusive_lookback(T* data, long n, T* total, unsigned long long* zeroed_state, hipStream_t stream) {
-  const int nb = (int)((n + kChunk - 1) / kChunk);
-  ocrf::launch(OCRF_K_SCAN, scan_lookback_kernel<T>, dim3(nb), dim3(kBlock), 0, stream, data, n, total, zeroed_state);
-}
-
-// Stable scatter of one pass.  A wave owns 512 consecutive keys of the workgroup's chunk and walks
-// them 64 at a time in order; the rank of a key among equal digits of its step is a ballot match,
-// running per-digit positions live in LDS (LDS operations of one wave execute in order).
-// EMIT (the LAST pass of the LSS preparation): the sorted (voxel, point) pairs leave as the three rank vectors at once —
-// ranks_bev = key, ranks_depth = the point's flat index (view_transformer.py:232-236), ranks_feat = (b*N + n)*H*W + h*W + w
-// — instead of as keys / values that one more launch turned into them.
-// EMIT 2 (the last pass of a render-plan build's sort): besides the sorted keys, the plan's per-view list arrays
-// (ocrf::RadixPlanEmit) — the gather launch that read the pairs back to write them is gone.
-struct ScatterExtra {
-  int* ranks_feat;
-  int DHW, HW;
-  ocrf::RadixPlanEmit plan;
-};
-template <bool IMPLICIT_VALS, int EMIT = 0>
-__global__ __launch_bounds__(kBlock) void radix_scatter_kernel(
-    const unsigned* __restrict__ keys_in, const int* __restrict__ vals_in, int n, int shift, int n_wg,
-    const int* __restrict__ table, unsigned* __restrict__ keys_out, int* __restrict__ vals_out, ScatterExtra x) {
-  __shared__ int s_pos[kBlock / 64][kBins];
-  const int tid = threadIdx.x, wave = tid / 64, lane = tid % 64;
-  for (int i = tid; i < (kBlock / 64) * kBins; i += kBlock) (&s_pos[0][0])[i] = 0;
-  __syncthreads();
-  const int wbase = blockIdx.x * kChunk + wave * (kChunk / (kBlock / 64));
-  unsigned key[kItems];
-  int val[kItems];
-  bool ok[kItems];
-  // keys (and values) of the thread in ONE round trip, at clamped addresses
-#pragma unroll
-  for (int s = 0; s < kItems; ++s) {
-    const int i = wbase + s * 64 + lane;
-    ok[s] = i < n;
-    key[s] = keys_in[min(i, n - 1)];
-    val[s] = IMPLICIT_VALS ? i : vals_in[min(i, n - 1)];
-  }
-  // EMIT 2: what the value points at, requested now (a gather per key inside the ordered walk below would be a round
-  // trip per step)
-  int e_id[EMIT == 2 ? kItems : 1];
-  float2 e_pix[EMIT == 2 ? kItems : 1];
-  if constexpr (EMIT == 2) {
-#pragma unroll
-    for (int s = 0; s < kItems; ++s) {
-      const int e = val[s];
-      e_id[s] = x.plan.rec_id[e];
-      const float4 q1 = x.plan.e_q1[e];
-      e_pix[s] = make_float2(q1.z, q1.w);
-    }
-  }
-#pragma unroll
-  for (int s = 0; s < kItems; ++s) {
-    if (!ok[s]) key[s] = 0u;
-    if (ok[s]) atomicAdd(&s_pos[wave][(key[s] >> shift) & (kBins - 1)], 1);
-  }
-  __syncthreads();
-  // per digit: global base of this workgroup, then the waves in order
-  for (int d = tid; d < kBins; d += kBlock) {
-    int run = table[(long)d * n_wg + blockIdx.x];
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w) {
-      const int c = s_pos[w][d];
-      s_pos[w][d] = run;
-      run += c;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int s = 0; s < kItems; ++s) {
-    const int digit = (int)((key[s] >> shift) & (kBins - 1));
-    unsigned long long same = __ballot(ok[s]);
-#pragma unroll
-    for (int b = 0; b < kRadixBits; ++b) {
-      const unsigned long long m = __ballot((digit >> b) & 1);
-      same &= ((digit >> b) & 1) ? m : ~m;
-    }
-    if (ok[s]) {
-      const int rank = __popcll(same & ((1ull << lane) - 1ull));
-      const int pos = s_pos[wave][digit] + rank;
-      keys_out[pos] = key[s];
-      if constexpr (EMIT != 2) vals_out[pos] = val[s];
-      if constexpr (EMIT == 1) x.ranks_feat[pos] = (val[s] / x.DHW) * x.HW + val[s] % x.HW;
-      if constexpr (EMIT == 2) {
-        x.plan.s_e[pos] = (unsigned)val[s];
-        x.plan.s_id[pos] = (unsigned)e_id[s];
-        x.plan.s_key[pos] = (key[s] & x.plan.depth_mask) + x.plan.key_base;
-        x.plan.s_pix[pos] = e_pix[s];
-      }
-      if (rank == 0) s_pos[wave][digit] = pos + __popcll(same);      // leader advances the digit
-    }
-    __builtin_amdgcn_wave_barrier();
-  }
 }
 
 // lower bounds, non-empty flags, their prefix sum and the interval vectors in ONE launch (one voxel per thread,
@@ -596,142 +324,31 @@ __global__ void ht_counts_kernel(const long long* __restrict__ total, int* __res
 
 using ocrf::align_up;
 
-inline int radix_passes(unsigned n_vox_total) {
-  int bits = 1;
-  while (bits < 32 && (1ull << bits) <= (unsigned long long)n_vox_total) ++bits;
-  return (bits + kRadixBits - 1) / kRadixBits;
+// LSS workspace: the sort's, keys A inside; behind its state blocks that of lss_intervals_kernel (kBlock voxels per tile)
+inline ocrf::SortLayout lss_layout(long n_pts, unsigned n_vox_total) {
+  return ocrf::radix_sort_layout(n_pts, true, lb_state_bytes(((long)n_vox_total + 1 + kBlock - 1) / kBlock));
 }
 
-struct LssWs {
-  size_t keys_a, keys_b, vals_a, vals_b, table, state, state_bytes, bytes;
-  long state_tiles_table, state_tiles_iv;
-};
-
-inline void lss_layout(long n_pts, unsigned n_vox_total, LssWs* w) {
-  size_t off = 0;
-  auto take = [&](size_t b) { size_t o = off; off += align_up(b, 256); return o; };
-  const long n_wg = (n_pts + kChunk - 1) / kChunk;
-  w->keys_a = take((size_t)n_pts * 4);
-  w->keys_b = take((size_t)n_pts * 4);
-  w->vals_a = take((size_t)n_pts * 4);
-  w->vals_b = take((size_t)n_pts * 4);
-  w->table = take((size_t)kBins * n_wg * 4);
-  // look-back states: one per radix pass (<= 4) + the interval kernel, zero-filled by ONE launch per call
-  w->state_tiles_table = ((long)kBins * n_wg + kChunk - 1) / kChunk;
-  w->state_tiles_iv = ((long)n_vox_total + 1 + kBlock - 1) / kBlock;
-  w->state = take(4 * lb_state_bytes(w->state_tiles_table) + lb_state_bytes(w->state_tiles_iv));
-  w->state_bytes = off - w->state;
-  w->bytes = off;
-}
-
-struct SortWs {
-  size_t keys_b, vals_a, vals_b, table, state, state_bytes, bytes;
-  long state_tiles;
-};
-
-inline void sort_layout(long n, SortWs* w) {
-  size_t off = 0;
-  auto take = [&](size_t b) { size_t o = off; off += align_up(b, 256); return o; };
-  const long n_wg = (n + kChunk - 1) / kChunk;
-  w->keys_b = take((size_t)n * 4);
-  w->vals_a = take((size_t)n * 4);
-  w->vals_b = take((size_t)n * 4);
-  w->table = take((size_t)kBins * n_wg * 4);
-  w->state_tiles = ((long)kBins * n_wg + kChunk - 1) / kChunk;
-  w->state = take(4 * lb_state_bytes(w->state_tiles));
-  w->state_bytes = off - w->state;
-  w->bytes = off;
+// HT workspace over n = B * n_pillars (batch, pillar) pairs: packed counts (at 0) | their total | look-back state of the
+// one scan | validity bits of up to 64 cameras
+struct HtWs { size_t total, state, state_bytes, valid_bits, bytes; };
+inline HtWs ht_layout(size_t n) {
+  HtWs w;
+  w.state_bytes = lb_state_bytes((long)((n + kChunk - 1) / kChunk));
+  w.total = align_up(n * 8, 256);
+  w.state = w.total + 256;
+  w.valid_bits = w.state + align_up(w.state_bytes, 256);
+  w.bytes = w.valid_bits + align_up(n * 64 * 4, 256);
+  return w;
 }
 
 }  // namespace
-
-namespace ocrf {
-
-// The radix sort of the LSS preparation as a service for the other translation units (raster_plan.hip sorts a
-// view's Gaussians by depth bits once per plan): stable, ids = original positions.
-size_t radix_sort_ids_bytes(int n) {
-  if (n <= 0) return 0;
-  SortWs w;
-  sort_layout(n, &w);
-  return w.bytes;
-}
-
-hipError_t radix_sort_ids(unsigned* keys, int n, int key_bits, void* scratch, size_t scratch_bytes,
-                          const unsigned** sorted_keys, const int** sorted_ids, hipStream_t stream,
-                          const RadixPlanEmit* plan_emit) {
-  if (n <= 0 || key_bits <= 0 || key_bits > 32 || !keys || !scratch) return hipErrorInvalidValue;
-  SortWs w;
-  sort_layout(n, &w);
-  if (scratch_bytes < w.bytes) return hipErrorInvalidValue;
-  char* base = static_cast<char*>(scratch);
-  unsigned* kbuf[2] = {keys, reinterpret_cast<unsigned*>(base + w.keys_b)};
-  int* vbuf[2] = {reinterpret_cast<int*>(base + w.vals_a), reinterpret_cast<int*>(base + w.vals_b)};
-  int* table = reinterpret_cast<int*>(base + w.table);
-  auto* state = reinterpret_cast<unsigned long long*>(base + w.state);
-  const size_t st_words = lb_state_bytes(w.state_tiles) / 8;
-  hipError_t e = zero_async(state, w.state_bytes, stream);
-  if (e != hipSuccess) return e;
-  const int n_wg = (n + kChunk - 1) / kChunk;
-  const int passes = (key_bits + kRadixBits - 1) / kRadixBits;      // <= 4
-  int cur = 0;
-  for (int pass = 0; pass < passes; ++pass) {
-    const int shift = pass * kRadixBits;
-    launch(OCRF_K_RADIX_HIST, radix_hist_kernel, dim3(n_wg), dim3(kBlock), 0, stream,
-           static_cast<const unsigned*>(kbuf[cur]), n, shift, n_wg, table);
-    scan_exclusive_lookback(table, (long)kBins * n_wg, (int*)nullptr, state + pass * st_words, stream);
-    ScatterExtra x{};
-    const bool emit = plan_emit != nullptr && pass == passes - 1 && pass > 0;
-    if (emit) x.plan = *plan_emit;
-    if (pass == 0)
-      launch(OCRF_K_RADIX_SCATTER, radix_scatter_kernel<true>, dim3(n_wg), dim3(kBlock), 0, stream,
-             static_cast<const unsigned*>(kbuf[cur]), static_cast<const int*>(nullptr), n, shift, n_wg,
-             static_cast<const int*>(table), kbuf[cur ^ 1], vbuf[cur ^ 1], x);
-    else if (emit)        // the consumer's arrays instead of the values (the sorted keys are still written)
-      launch(OCRF_K_RADIX_SCATTER, radix_scatter_kernel<false, 2>, dim3(n_wg), dim3(kBlock), 0, stream,
-             static_cast<const unsigned*>(kbuf[cur]), static_cast<const int*>(vbuf[cur]), n, shift, n_wg,
-             static_cast<const int*>(table), kbuf[cur ^ 1], vbuf[cur ^ 1], x);
-    else
-      launch(OCRF_K_RADIX_SCATTER, radix_scatter_kernel<false>, dim3(n_wg), dim3(kBlock), 0, stream,
-             static_cast<const unsigned*>(kbuf[cur]), static_cast<const int*>(vbuf[cur]), n, shift, n_wg,
-             static_cast<const int*>(table), kbuf[cur ^ 1], vbuf[cur ^ 1], x);
-    cur ^= 1;
-  }
-  *sorted_keys = kbuf[cur];
-  *sorted_ids = (plan_emit != nullptr && passes > 1) ? nullptr : vbuf[cur];      // (not written with an emit)
-  return hipGetLastError();
-}
-
-// where a radix_sort_ids(.., n, key_bits, scratch, ..) call leaves the state blocks of its look-back scans (one per
-// pass): bit 63 of a block's first word says that scan gave up (the caller's last kernel checks them on the device)
-void radix_sort_states(void* scratch, int n, int key_bits, const unsigned long long** states, int* n_states,
-                       long* stride_words) {
-  SortWs w;
-  sort_layout(n, &w);
-  *states = reinterpret_cast<const unsigned long long*>(static_cast<char*>(scratch) + w.state);
-  *n_states = (key_bits + kRadixBits - 1) / kRadixBits;
-  *stride_words = (long)(lb_state_bytes(w.state_tiles) / 8);
-}
-
-// in-place exclusive prefix sum of n non-negative ints (one look-back launch + the zero-fill of its state)
-size_t exclusive_scan_bytes(long n) { return n > 0 ? align_up(lb_state_bytes((n + kChunk - 1) / kChunk), 256) : 0; }
-
-hipError_t exclusive_scan_ints(int* data, long n, int* total, void* scratch, size_t scratch_bytes, hipStream_t stream) {
-  if (n <= 0 || !data || !scratch || scratch_bytes < exclusive_scan_bytes(n)) return hipErrorInvalidValue;
-  hipError_t e = zero_async(scratch, exclusive_scan_bytes(n), stream);
-  if (e != hipSuccess) return e;
-  scan_exclusive_lookback<int>(data, n, total, static_cast<unsigned long long*>(scratch), stream);
-  return hipGetLastError();
-}
-
-}  // namespace ocrf
 
 extern "C" {
 
 size_t ocrf_lss_prepare_workspace_bytes(int B, int N, int D, int H, int W, int gx, int gy, int gz) {
   if (B <= 0 || N <= 0 || D <= 0 || H <= 0 || W <= 0 || gx <= 0 || gy <= 0 || gz <= 0) return 0;
-  LssWs w;
-  lss_layout((long)B * N * D * H * W, (unsigned)((long)B * gz * gy * gx), &w);
-  return w.bytes;
+  return lss_layout((long)B * N * D * H * W, (unsigned)((long)B * gz * gy * gx)).bytes;
 }
 
 int ocrf_lss_prepare(int B, int N, int D, int H, int W, const float* frustum, const float* cams,
@@ -749,57 +366,32 @@ int ocrf_lss_prepare(int B, int N, int D, int H, int W, const float* frustum, co
   if (n_pts_l >= (1l << 31) - kChunk || n_vox_l >= (1l << 31) - 1) return (int)hipErrorInvalidValue;
   const int n_pts = (int)n_pts_l;
   const unsigned n_vox_total = (unsigned)n_vox_l;
-  LssWs w;
-  lss_layout(n_pts, n_vox_total, &w);
+  const ocrf::SortLayout w = lss_layout(n_pts, n_vox_total);
   if (!workspace || workspace_bytes < w.bytes) return (int)hipErrorInvalidValue;
   char* base = static_cast<char*>(workspace);
-  unsigned* keys[2] = {reinterpret_cast<unsigned*>(base + w.keys_a), reinterpret_cast<unsigned*>(base + w.keys_b)};
-  int* vals[2] = {reinterpret_cast<int*>(base + w.vals_a), reinterpret_cast<int*>(base + w.vals_b)};
-  int* table = reinterpret_cast<int*>(base + w.table);
-  const int n_wg = (n_pts + kChunk - 1) / kChunk;
-  // the grid constants are read on the host side of the ABI (6 floats); they are host memory
-  const float lx = grid_lower[0], ly = grid_lower[1], lz = grid_lower[2];
-  const float ix = grid_interval[0], iy = grid_interval[1], iz = grid_interval[2];
-
+  unsigned* keys = reinterpret_cast<unsigned*>(base + w.keys_a);
   auto* state = reinterpret_cast<unsigned long long*>(base + w.state);
-  const size_t st_words = lb_state_bytes(w.state_tiles_table) / 8;
-  hipError_t ze = ocrf::zero_async(state, w.state_bytes, stream);
-  if (ze != hipSuccess) return (int)ze;
-  const int passes = radix_passes(n_vox_total);
-  if (passes > 4) return (int)hipErrorInvalidValue;
+  // the grid constants are read on the host side of the ABI (6 floats); they are host memory
+  const LssGrid grid{grid_lower[0], grid_lower[1], grid_lower[2], grid_interval[0], grid_interval[1], grid_interval[2],
+                     gx, gy, gz};
+  hipError_t e = ocrf::zero_async(state, w.state_bytes, stream);
+  if (e != hipSuccess) return (int)e;
   // keys + the first pass's histogram in one launch; the last pass scatters straight into the rank vectors
-  const LssGrid grid{lx, ly, lz, ix, iy, iz, gx, gy, gz};
-  ocrf::launch(OCRF_K_LSS_KEYS, lss_keys_hist_kernel, dim3(n_wg), dim3(kBlock), 0, stream, n_pts, N, D * H * W, frustum,
-               reinterpret_cast<const LssCam*>(cams), grid, n_vox_total, keys[0], n_wg, table);
-  int cur = 0;
-  unsigned* const rb_keys = reinterpret_cast<unsigned*>(ranks_bev);
-  const int DHW = D * H * W, HW = H * W;
-  for (int pass = 0; pass < passes; ++pass) {
-    const int shift = pass * kRadixBits;
-    const bool last = pass == passes - 1;
-    if (pass > 0)
-      ocrf::launch(OCRF_K_RADIX_HIST, radix_hist_kernel, dim3(n_wg), dim3(kBlock), 0, stream,
-                   static_cast<const unsigned*>(keys[cur]), n_pts, shift, n_wg, table);
-    scan_exclusive_lookback(table, (long)kBins * n_wg, (int*)nullptr, state + pass * st_words, stream);
-    ScatterExtra sx{};
-    sx.ranks_feat = ranks_feat; sx.DHW = DHW; sx.HW = HW;
-#define OCRF_LSS_SCATTER(IMPL, EMIT, KOUT, VOUT)                                                                        \
-  ocrf::launch(OCRF_K_RADIX_SCATTER, radix_scatter_kernel<IMPL, EMIT>, dim3(n_wg), dim3(kBlock), 0, stream,             \
-               static_cast<const unsigned*>(keys[cur]), static_cast<const int*>(IMPL ? nullptr : vals[cur]), n_pts,     \
-               shift, n_wg, static_cast<const int*>(table), KOUT, VOUT, sx)
-    if (pass == 0 && last) OCRF_LSS_SCATTER(true, 1, rb_keys, ranks_depth);
-    else if (pass == 0) OCRF_LSS_SCATTER(true, 0, keys[cur ^ 1], vals[cur ^ 1]);
-    else if (last) OCRF_LSS_SCATTER(false, 1, rb_keys, ranks_depth);
-    else OCRF_LSS_SCATTER(false, 0, keys[cur ^ 1], vals[cur ^ 1]);
-#undef OCRF_LSS_SCATTER
-    cur ^= 1;
-  }
+  ocrf::launch(OCRF_K_LSS_KEYS, lss_keys_hist_kernel, dim3(w.n_wg), dim3(kBlock), 0, stream, n_pts, N, D * H * W, frustum,
+               reinterpret_cast<const LssCam*>(cams), grid, n_vox_total, keys, w.n_wg,
+               reinterpret_cast<int*>(base + w.table));
+  const ocrf::RadixRankEmit emit{ranks_feat, D * H * W, H * W};
+  unsigned* rb_keys = reinterpret_cast<unsigned*>(ranks_bev);
+  const int key_bits = 32 - __builtin_clz(n_vox_total);      // of the largest key, n_vox_total: a dropped point's
+  e = ocrf::radix_sort_passes(keys, n_pts, ocrf::radix_passes_of_bits(key_bits), true, workspace, w, &emit, nullptr,
+                              &rb_keys, &ranks_depth, stream);
+  if (e != hipSuccess) return (int)e;
   const int vgrid = (int)((n_vox_total + 1 + kBlock - 1) / kBlock);
   // the interval vectors from the sorted keys (= ranks_bev); its last tile also turns a look-back scan that gave up —
   // any of the sort's or its own — into counts = -1
   ocrf::launch(OCRF_K_LSS_BOUNDS, lss_intervals_kernel, dim3(vgrid), dim3(kBlock), 0, stream,
                static_cast<const unsigned*>(rb_keys), n_pts, n_vox_total, interval_starts, interval_lengths, counts,
-               state + 4 * st_words, static_cast<const unsigned long long*>(state), (int)st_words, 5);
+               state + 4 * w.st_words, static_cast<const unsigned long long*>(state), (int)w.st_words, 5);
   return (int)hipGetLastError();
 }
 
@@ -956,8 +548,7 @@ int ocrf_geometry_blocks(int B, int N, const float* rots, const float* trans, co
 
 size_t ocrf_ht_prepare_workspace_bytes(int B, int n_pillars) {
   if (B <= 0 || n_pillars <= 0) return 0;
-  const size_t n = (size_t)B * n_pillars;
-  return align_up(n * 8, 256) + 256 + align_up(((n + kChunk - 1) / kChunk + 1) * 8, 256) + align_up(n * 64 * 4, 256);   // valid bits: up to 64 cameras
+  return ht_layout((size_t)B * n_pillars).bytes;
 }
 
 int ocrf_ht_prepare(int B, int N, int Z, int n_pillars, int Wf, int Hf, int D, const float* ref_points,
@@ -971,13 +562,14 @@ int ocrf_ht_prepare(int B, int N, int Z, int n_pillars, int Wf, int Hf, int D, c
     return (int)hipErrorInvalidValue;
   if ((long)B * N * Z * n_pillars >= (1l << 31) - 1 || (long)B * N * D * Wf * Hf >= (1l << 31) - 1)
     return (int)hipErrorInvalidValue;
-  const size_t need = ocrf_ht_prepare_workspace_bytes(B, n_pillars);
-  if (!workspace || workspace_bytes < need) return (int)hipErrorInvalidValue;
+  const HtWs w = ht_layout((size_t)B * n_pillars);
+  if (!workspace || workspace_bytes < w.bytes) return (int)hipErrorInvalidValue;
+  char* base = static_cast<char*>(workspace);
   long long* cnt_flag = static_cast<long long*>(workspace);
-  long long* total = reinterpret_cast<long long*>(static_cast<char*>(workspace) + align_up((size_t)B * n_pillars * 8, 256));
-  long long* scratch = total + 32;
-  unsigned* valid_bits = reinterpret_cast<unsigned*>(
-      reinterpret_cast<char*>(scratch) + align_up((((size_t)B * n_pillars + kChunk - 1) / kChunk + 1) * 8, 256));
+  long long* total = reinterpret_cast<long long*>(base + w.total);
+  // the look-back state of the scan: (tiles + 1) words, zero-filled by the first kernel
+  auto* state = reinterpret_cast<unsigned long long*>(base + w.state);
+  unsigned* valid_bits = reinterpret_cast<unsigned*>(base + w.valid_bits);
   HtParams q;
   q.B = B; q.N = N; q.Z = Z; q.Nq = n_pillars; q.Wf = Wf; q.Hf = Hf; q.D = D;
   // scale / offset as float32 scalars of double differences: what `tensor * python_float` does
@@ -988,11 +580,8 @@ int ocrf_ht_prepare(int B, int N, int Z, int n_pillars, int Wf, int Hf, int D, c
   const dim3 cgrid((n_pillars + kBlock - 1) / kBlock, B * N);
   const int pgrid = (B * n_pillars + kBlock - 1) / kBlock;
   const HtCam* hc = reinterpret_cast<const HtCam*>(cams);
-  // scratch holds the look-back state of the scan: (tiles + 1) words, zero-filled by the first kernel
-  auto* state = reinterpret_cast<unsigned long long*>(scratch);
-  const int state_words = (int)(((long)B * n_pillars + kChunk - 1) / kChunk + 1);
   ocrf::launch(OCRF_K_HT_COUNT, ht_valid_kernel, cgrid, dim3(kBlock), 0, stream, q, ref_points, hc, valid_bits, state,
-               state_words);
+               (int)(w.state_bytes / 8));
   hipLaunchKernelGGL(ht_pillar_totals_kernel, dim3(pgrid), dim3(kBlock), 0, stream, q,
                      static_cast<const unsigned*>(valid_bits), cnt_flag);
   scan_exclusive_lookback<long long>(cnt_flag, (long)B * n_pillars, total, state, stream);

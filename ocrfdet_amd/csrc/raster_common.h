@@ -207,23 +207,4 @@ int raster_forward_chain(int P, int n_sets, int views_per_set, int H, int W, con
                          size_t workspace_bytes, int* gate, bool shared_means, bool hist_is_zero, hipStream_t stream);
 int* raster_chain_hist(void* workspace, int P, int n_views, size_t* n_words);
 
-// index_prep.hip: stable LSD radix sort of n 32-bit keys carrying their original index (ids ascending among equal
-// keys).  `keys` is clobbered; the sorted keys / ids are returned through the two pointers (they point into
-// `scratch`, >= radix_sort_ids_bytes(n) bytes, or at `keys`).
-size_t radix_sort_ids_bytes(int n);
-// `plan_emit` (radix_emit.h): the last pass writes the render plan's per-view list arrays itself; *sorted_ids is then
-// null (the values are not written).
-struct RadixPlanEmit;
-hipError_t radix_sort_ids(unsigned* keys, int n, int key_bits, void* scratch, size_t scratch_bytes,
-                          const unsigned** sorted_keys, const int** sorted_ids, hipStream_t stream,
-                          const RadixPlanEmit* plan_emit = nullptr);
-// the state blocks of that call's look-back scans (bit 63 of a block's first word: the scan gave up)
-void radix_sort_states(void* scratch, int n, int key_bits, const unsigned long long** states, int* n_states,
-                       long* stride_words);
-
-
-// index_prep.hip: in-place exclusive prefix sum of n non-negative ints (*total = their sum, may be null)
-size_t exclusive_scan_bytes(long n);
-hipError_t exclusive_scan_ints(int* data, long n, int* total, void* scratch, size_t scratch_bytes, hipStream_t stream);
-
 }  // namespace ocrf

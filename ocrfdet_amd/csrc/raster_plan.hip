@@ -36,7 +36,7 @@
 #include "ocrf_hip.h"
 #include "raster_blend_body.h"
 #include "raster_blend_math.h"
-#include "radix_emit.h"
+#include "radix_sort.h"
 #include "raster_common.h"
 
 namespace {
@@ -130,7 +130,7 @@ inline void dyn_layout(long T, int n_sets, DynLayout* L, long cand_cap = 0, long
 //   3. fill records   per record: the rows of J W and the pixel centre (static per (mean, camera)), its Gaussian id and
 //                     its sort key (view << 27 | depth bits - 0x3E000000): depths in [0.125, 8191) m order by their
 //                     27 low-order-relevant bits, so ONE 32-bit key sorts every view's list at once
-//   4. stable radix sort of the keys (index_prep.hip), 4 passes.  Equal (view, depth) keep their Gaussian-major order
+//   4. stable radix sort of the keys (radix_sort.hip), 4 passes.  Equal (view, depth) keep their Gaussian-major order
 //                     = ascending id: the reference's order (stable sort of duplicateWithKeys' id-ordered output,
 //                     rasterizer_impl.cu:226-267).  Records beyond the total carry the key ~0 and stay at the end.
 //   5. gather         sorted position -> (record, id, depth bits, pixel centre); header: view offsets, magic.
