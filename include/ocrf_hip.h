@@ -433,6 +433,28 @@ int ocrf_rasterize_backward_cov3d(int P, int n_views, int H, int W, const float 
                                   float *dL_dcolors, float *dL_dopacity, float *dL_dcov3D, float *dL_dmeans2D,
                                   void *workspace, size_t workspace_bytes, ocrf_stream_t stream);
 size_t ocrf_rasterize_backward_workspace_bytes(int P, int n_views);
+/* The backward with the gradients of the two outputs the w-depth fork leaves without one: the MEAN depth
+ * D = sum_i alpha_i T_i z_i of depth_mode 1 (unnormalised, 0 where nothing is hit; the median depth is piecewise
+ * constant and has no gradient) and final_T.  D and 1 - final_T are two more colour channels with the constant colours
+ * z_i and 1 over a zero background; z_i = view[:,2] . (mean_i, 1) adds (view[0][2], view[1][2], view[2][2]) * dL/dz_i to
+ * dL_dmeans3D.
+ *   fwd_depth (n_views,H,W): the forward's out_depth at depth_mode 1 for the same inputs
+ *   dL_ddepth / dL_dfinal_T (n_views,H,W): either may be NULL (zeros), not both: that is the case of the two entries
+ *   above.  dL_ddepth without fwd_depth is refused.  dL_dcolor is required (zeros if the colour got no gradient).
+ * Covariance as in the two entries above: cov3D_precomp (then dL_dcov3D is written, scales / rotations and their
+ * gradients are ignored) or (scales, rotations) with scale_modifier.  Every other argument, output and refusal as
+ * there; the workspace is larger (ten sums per (view, Gaussian) instead of nine).  Float atomics per (tile, Gaussian):
+ * reproducible to rounding only, exactly as the colour backward. */
+int ocrf_rasterize_backward_depth(int P, int n_views, int H, int W, const float *means3D, const float *colors,
+                                  const float *opacities, const float *scales, float scale_modifier,
+                                  const float *rotations, const float *cov3D_precomp, const float *cameras,
+                                  const float *bg, const float *fwd_color, const float *fwd_depth,
+                                  const float *fwd_final_T, const uint32_t *fwd_n_contrib, const float *dL_dcolor,
+                                  const float *dL_ddepth, const float *dL_dfinal_T, float *dL_dmeans3D,
+                                  float *dL_dcolors, float *dL_dopacity, float *dL_dscales, float *dL_drotations,
+                                  float *dL_dcov3D, float *dL_dmeans2D, void *workspace, size_t workspace_bytes,
+                                  ocrf_stream_t stream);
+size_t ocrf_rasterize_backward_depth_workspace_bytes(int P, int n_views);
 
 /*
  * Spherical-harmonics colours (the `shs` argument of the reference's rasteriser; computeColorFromSH,
@@ -1401,7 +1423,7 @@ enum {
   OCRF_K_RASTER_GATHER = 12,     /* raster_scatter_kernel */
   OCRF_K_RASTER_SCAN = 13,       /* raster_bucket_scan_kernel */
   OCRF_K_RASTER_BLEND_BWD = 15,  /* raster_blend_kernel<false, true> */
-  OCRF_K_RASTER_PRE_BWD = 16,    /* raster_preprocess_backward_kernel */
+  OCRF_K_RASTER_PRE_BWD = 16,    /* raster_preprocess_backward_kernel<false> */
   OCRF_K_RASTER_PLAN_UPDATE = 17,  /* raster_plan_head_kernel (rounds 3-4: raster_plan_update_kernel) */
   OCRF_K_RASTER_BLEND_SORTED = 18, /* raster_blend_sorted_kernel<*>, first pass */
   OCRF_K_RASTER_BLEND_SECOND = 19, /* raster_blend_sorted_kernel<*>, second pass (tile pairs handed over by the first) */
@@ -1503,7 +1525,9 @@ enum {
   OCRF_K_GROUP_CORR_GRAD_RIGHT = 142, /* group_corr_grad_right_kernel<DT> */
   OCRF_K_KD_PARTIAL = 143,            /* kd_partial_kernel */
   OCRF_K_KD_FINAL = 144,              /* kd_final_kernel */
-  OCRF_K_KD_BWD = 145                 /* kd_backward_kernel */
+  OCRF_K_KD_BWD = 145,                /* kd_backward_kernel */
+  OCRF_K_RASTER_BLEND_BWD_DEPTH = 146, /* raster_blend_kernel<false, true, true, true, true> */
+  OCRF_K_RASTER_PRE_BWD_DEPTH = 147   /* raster_preprocess_backward_kernel<true> */
 };
 const char *ocrf_kernel_name(int kernel_id);           /* symbol as rocprofv3 prints it */
 /* Diagnostic: a one-thread kernel that stores the device's constant-rate clock (wall_clock64, 100 MHz)

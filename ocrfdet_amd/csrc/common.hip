@@ -94,7 +94,7 @@ const char* ocrf_kernel_name(int kernel_id) {
     case OCRF_K_RASTER_PREPROCESS: return "raster_preprocess_kernel";
     case OCRF_K_RASTER_BLEND: return "raster_blend_kernel<false, false, *>";
     case OCRF_K_RASTER_BLEND_BWD: return "raster_blend_kernel<false, true, true>";
-    case OCRF_K_RASTER_PRE_BWD: return "raster_preprocess_backward_kernel";
+    case OCRF_K_RASTER_PRE_BWD: return "raster_preprocess_backward_kernel<false>";
     case OCRF_K_RASTER_GATHER: return "raster_scatter_kernel";
     case OCRF_K_RASTER_PLAN_UPDATE: return "raster_plan_update_kernel";
     case OCRF_K_RASTER_BLEND_SORTED: return "raster_blend_sorted_kernel<*>";
@@ -194,6 +194,8 @@ const char* ocrf_kernel_name(int kernel_id) {
     case OCRF_K_KD_PARTIAL: return "kd_partial_kernel";
     case OCRF_K_KD_FINAL: return "kd_final_kernel";
     case OCRF_K_KD_BWD: return "kd_backward_kernel";
+    case OCRF_K_RASTER_BLEND_BWD_DEPTH: return "raster_blend_kernel<false, true, true, true, true>";
+    case OCRF_K_RASTER_PRE_BWD_DEPTH: return "raster_preprocess_backward_kernel<true>";
     default: return "";
   }
 }

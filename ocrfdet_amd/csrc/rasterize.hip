@@ -498,7 +498,11 @@ struct BwdArgs {
   const float* fwd_color;      // (V,3,H,W) forward output
   const float* fwd_final_T;    // (V,H,W)
   const unsigned* fwd_n_contrib;
-  float* acc;                  // (V,P,9): mean2D x,y | conic x,y,z | opacity | colour r,g,b
+  float* acc;                  // (V,P,9): mean2D x,y | conic x,y,z | opacity | colour r,g,b; DEPTHG: (V,P,10), | depth
+  // DEPTHG only: the gradients of the mean depth D = sum_i alpha_i T_i z_i and of final_T (either may be null: zeros)
+  const float* dL_ddepth;      // (V,H,W)
+  const float* dL_dfinal_T;    // (V,H,W)
+  const float* fwd_depth;      // (V,H,W) forward output, depth_mode 1; may be null with dL_ddepth
 };
 
 // One workgroup = one PAIR of vertically adjacent 16x16 tiles (tile rows 2*by and 2*by+1) of one
@@ -510,7 +514,12 @@ struct BwdArgs {
 // counter of its covered records.
 // (forward: five waves per SIMD asked of the compiler — 28 KB of LDS hold five workgroups per CU; left alone hipcc takes
 // 110 VGPRs for the staging and the record loops keep everything in registers at 96 too)
-template <bool STAMP, bool BWD, bool MEDIAN, bool CONTRIB = true>
+// DEPTHG (backward only): D and 1 - final_T are two more channels whose "colours" are z_i and 1 and whose background is
+// 0.  dL/dalpha_i gains dL/dD * (z_i T_i - (D - prefix_D(i)) / (1 - alpha_i)) and -dL/dT_final * T_final / (1 - alpha_i)
+// (the second has the form of the background term: bgdot + dL/dT_final), and there is a tenth per-record sum,
+// dL/dz_i = sum_pixels dL/dD * alpha_i T_i, which the preprocess backward carries to the mean through the view
+// matrix's depth row.  Records are then 10 floats in LDS and in the accumulator.
+template <bool STAMP, bool BWD, bool MEDIAN, bool CONTRIB = true, bool DEPTHG = false>
 __global__ __launch_bounds__(kBlock, (BWD || STAMP) ? 1 : (CONTRIB ? 5 : 4)) void raster_blend_kernel(
     unsigned long long* __restrict__ stamps,
     int P, int W, int H, int gy, const int* __restrict__ starts, const Rect* __restrict__ rects,
@@ -536,7 +545,9 @@ __global__ __launch_bounds__(kBlock, (BWD || STAMP) ? 1 : (CONTRIB ? 5 : 4)) voi
   float4* l_b = l_a + kStage;                                      // BWD: conic.z, opacity, depth, r; fwd: see staging
   float4* l_c = l_b + kStage;                                      // BWD: g, b, coverage bits, -
   unsigned* l_id = reinterpret_cast<unsigned*>(l_c + kStage);     // BWD only
-  float* l_g = reinterpret_cast<float*>(l_id + kStage);           // BWD only: [kStage][9]
+  float* l_g = reinterpret_cast<float*>(l_id + kStage);           // BWD only: [kStage][NG]
+  static_assert(!DEPTHG || BWD, "DEPTHG is a mode of the backward");
+  constexpr int NG = DEPTHG ? 10 : 9;                              // per-record sums
   __shared__ int l_wtot[kScanUnroll * (kBlock / 64)];
   __shared__ int l_ready;
   __shared__ int l_fmax, l_generic;      // forward: largest need factor (float bits) / a GENERIC record in the staged batch
@@ -587,12 +598,13 @@ __global__ __launch_bounds__(kBlock, (BWD || STAMP) ? 1 : (CONTRIB ? 5 : 4)) voi
   // backward-only per-pixel state
   f2 dL0 = splat(0.f), dL1 = splat(0.f), dL2 = splat(0.f), S0 = splat(0.f), S1 = splat(0.f), S2 = splat(0.f);
   f2 Tfin = splat(0.f), bgdot = splat(0.f);
+  f2 gD = splat(0.f), Dfin = splat(0.f), Dp = splat(0.f);      // DEPTHG: dL/dD, the forward's D, its running prefix
   int n_lastA = 0, n_lastB = 0;
   if constexpr (BWD) {
     const long npix = (long)W * H;
-    struct PixelBwd { float d0, d1, d2, s0, s1, s2, tf, bd; int nl; };
+    struct PixelBwd { float d0, d1, d2, s0, s1, s2, tf, bd; int nl; float gd, df; };
     auto load = [&](bool inside, int py) {
-      PixelBwd q = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0};
+      PixelBwd q = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0, 0.f, 0.f};
       if (!inside) return q;
       const long pix = (long)py * W + pxi;
       q.d0 = bw.dL_dcolor[(v * 3 + 0) * npix + pix];
@@ -604,6 +616,13 @@ __global__ __launch_bounds__(kBlock, (BWD || STAMP) ? 1 : (CONTRIB ? 5 : 4)) voi
       q.s2 = bw.fwd_color[(v * 3 + 2) * npix + pix] - q.tf * bg[2];
       q.bd = bg[0] * q.d0 + bg[1] * q.d1 + bg[2] * q.d2;
       q.nl = (int)bw.fwd_n_contrib[v * npix + pix];
+      if constexpr (DEPTHG) {
+        if (bw.dL_ddepth) {
+          q.gd = bw.dL_ddepth[v * npix + pix];
+          q.df = bw.fwd_depth[v * npix + pix];
+        }
+        if (bw.dL_dfinal_T) q.bd += bw.dL_dfinal_T[v * npix + pix];      // -T_final / (1 - alpha) * (bg . dL/dC + dL/dT_final)
+      }
       return q;
     };
     const PixelBwd qa = load(insideA, pyA), qb = load(insideB, pyB);
@@ -611,6 +630,10 @@ __global__ __launch_bounds__(kBlock, (BWD || STAMP) ? 1 : (CONTRIB ? 5 : 4)) voi
     S0 = f2{qa.s0, qb.s0}; S1 = f2{qa.s1, qb.s1}; S2 = f2{qa.s2, qb.s2};
     Tfin = f2{qa.tf, qb.tf}; bgdot = f2{qa.bd, qb.bd};
     n_lastA = qa.nl; n_lastB = qb.nl;
+    if constexpr (DEPTHG) {
+      gD = f2{qa.gd, qb.gd};
+      Dfin = f2{qa.df, qb.df};
+    }
     doneA = doneA || (n_lastA == 0);
     doneB = doneB || (n_lastB == 0);
   }
@@ -676,7 +699,7 @@ __global__ __launch_bounds__(kBlock, (BWD || STAMP) ? 1 : (CONTRIB ? 5 : 4)) voi
           l_c[tid] = make_float4(col[1], col[2], __uint_as_float(cov), 0.f);
           l_id[tid] = id;
 #pragma unroll
-          for (int k = 0; k < 9; ++k) l_g[tid * 9 + k] = 0.f;
+          for (int k = 0; k < NG; ++k) l_g[tid * NG + k] = 0.f;
         } else {
           // forward: the staged form of raster_blend_math.h; the record's tile coverage is in its per-pixel constant
           // term — pixel A (tile A) / pixel B (tile B) see L = log2(opacity) (GENERIC: the opacity) only if the record
@@ -853,6 +876,10 @@ __global__ __launch_bounds__(kBlock, (BWD || STAMP) ? 1 : (CONTRIB ? 5 : 4)) voi
             inv.y = __builtin_amdgcn_rcpf(om.y);
             f2 dLda = dL0 * (splat(b.w) * T - (S0 - C0) * inv) + dL1 * (splat(cg) * T - (S1 - C1) * inv) +
                       dL2 * (splat(cb) * T - (S2 - C2) * inv) - Tfin * inv * bgdot;
+            if constexpr (DEPTHG) {
+              Dp = fma2(splat(b.z), wgt, Dp);              // the depth prefix, like a colour channel with colour z_i
+              dLda = dLda + gD * (splat(b.z) * T - (Dfin - Dp) * inv);
+            }
             dLda.x = contribA ? dLda.x : 0.f;
             dLda.y = contribB ? dLda.y : 0.f;
             const f2 dG = splat(b.y) * dLda;
@@ -872,6 +899,11 @@ __global__ __launch_bounds__(kBlock, (BWD || STAMP) ? 1 : (CONTRIB ? 5 : 4)) voi
             g[6] = k6.x + k6.y;
             g[7] = k7.x + k7.y;
             g[8] = k8.x + k8.y;
+            float g9 = 0.f;                                // DEPTHG: dL/dz_i
+            if constexpr (DEPTHG) {
+              const f2 k9 = wgt * gD;
+              g9 = k9.x + k9.y;
+            }
             if (__ballot(contribA || contribB) != 0ull) {
               // Transposed reduction on the VALU (DPP), no LDS traffic: each halving step keeps half
               // of the values per lane, so 8 values cost 4+2+1 pair-sums instead of 8 x 6; lane l
@@ -899,7 +931,16 @@ __global__ __launch_bounds__(kBlock, (BWD || STAMP) ? 1 : (CONTRIB ? 5 : 4)) voi
               e += dpp_mov<kDppHalfMirror>(e);
               e += dpp_mov<kDppRowMirror>(e);
               const int l16 = lane & 15;
-              if (l16 < 9) atomicAdd(&l_g[(j0 + u) * 9 + l16], l16 == 8 ? e : r);
+              if constexpr (DEPTHG) {
+                float e9 = g9;
+                e9 += dpp_mov<kDppQuadXor1>(e9);
+                e9 += dpp_mov<kDppQuadXor2>(e9);
+                e9 += dpp_mov<kDppHalfMirror>(e9);
+                e9 += dpp_mov<kDppRowMirror>(e9);
+                if (l16 < 10) atomicAdd(&l_g[(j0 + u) * 10 + l16], l16 == 9 ? e9 : (l16 == 8 ? e : r));
+              } else {
+                if (l16 < 9) atomicAdd(&l_g[(j0 + u) * 9 + l16], l16 == 8 ? e : r);
+              }
             }
             T.x = contribA ? test_T.x : T.x;
             T.y = contribB ? test_T.y : T.y;
@@ -914,12 +955,12 @@ __global__ __launch_bounds__(kBlock, (BWD || STAMP) ? 1 : (CONTRIB ? 5 : 4)) voi
       if constexpr (BWD) {
         // Float atomics execute at the memory side as 64-B requests: the rate is set by the
         // number of requests, not of adds.  16 lanes per record (9 active) keep a record's 36
-        // contiguous bytes in 1-2 requests; one lane per record would issue 9.
+        // contiguous bytes in 1-2 requests; one lane per record would issue 9.  (DEPTHG: 10 lanes, 40 bytes.)
         for (int r0 = 0; r0 < ns; r0 += kBlock / 16) {
           const int r = r0 + tid / 16, k = tid % 16;
-          if (r < ns && k < 9) {
-            const float val = l_g[r * 9 + k];
-            if (val != 0.f) atomicAdd(&bw.acc[(base + l_id[r]) * 9 + k], val);
+          if (r < ns && k < NG) {
+            const float val = l_g[r * NG + k];
+            if (val != 0.f) atomicAdd(&bw.acc[(base + l_id[r]) * NG + k], val);
           }
         }
         __syncthreads();
@@ -1128,7 +1169,9 @@ __global__ __launch_bounds__(kBlock, (BWD || STAMP) ? 1 : (CONTRIB ? 5 : 4)) voi
 // Backward of the per-Gaussian stages (backward.cu:144-276 computeCov2DCUDA, :346-396 preprocessCUDA,
 // :278-342 computeCov3D): one thread per Gaussian, views summed in ascending order (deterministic).
 // acc (V,P,9) comes from the backward blend: mean2D x,y | conic x,y,z | opacity | colour r,g,b.
+// DEPTHG: acc is (V,P,10), the tenth sum is dL/dz of the view-space depth z = view[:,2] . (mean, 1).
 // ---------------------------------------------------------------------------------------------
+template <bool DEPTHG>
 __global__ __launch_bounds__(kBlock) void raster_preprocess_backward_kernel(
     int P, int n_views, int W, int H, const float* __restrict__ means3D, const float* __restrict__ scales,
     float scale_modifier, const float* __restrict__ rotations, const float* __restrict__ cov3D_precomp,
@@ -1170,7 +1213,7 @@ __global__ __launch_bounds__(kBlock) void raster_preprocess_backward_kernel(
   float dmean[3] = {0.f, 0.f, 0.f}, dcov[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   float dcol[3] = {0.f, 0.f, 0.f}, dop = 0.f;
   for (int v = 0; v < n_views; ++v) {
-    const float* a9 = acc + ((long)v * P + idx) * 9;
+    const float* a9 = acc + ((long)v * P + idx) * (DEPTHG ? 10 : 9);
     dop += a9[5];
     dcol[0] += a9[6]; dcol[1] += a9[7]; dcol[2] += a9[8];
     if (dL_dmeans2D) {
@@ -1183,6 +1226,11 @@ __global__ __launch_bounds__(kBlock) void raster_preprocess_backward_kernel(
     const float* vm = cam.view;
     const float* pm = cam.proj;
     const float dcx = a9[2], dcy = a9[3], dcz = a9[4];
+    if constexpr (DEPTHG) {
+      dmean[0] += vm[2] * a9[9];
+      dmean[1] += vm[6] * a9[9];
+      dmean[2] += vm[10] * a9[9];
+    }
     float t0 = vm[0] * mx + vm[4] * my + vm[8] * mz + vm[12];
     float t1 = vm[1] * mx + vm[5] * my + vm[9] * mz + vm[13];
     const float t2 = vm[2] * mx + vm[6] * my + vm[10] * mz + vm[14];
@@ -1297,7 +1345,8 @@ struct RasterBufs {
   size_t total, bwd_total;                                // bytes the forward / the backward needs
 };
 
-inline RasterBufs raster_layout(void* workspace, int P, int n_views) {
+// acc_stride: floats per (view, Gaussian) of the backward's accumulator: 9, or 10 with the depth gradients
+inline RasterBufs raster_layout(void* workspace, int P, int n_views, int acc_stride = 9) {
   const size_t n = (size_t)P * n_views;
   RasterBufs b;
   size_t off = 0;
@@ -1318,7 +1367,7 @@ inline RasterBufs raster_layout(void* workspace, int P, int n_views) {
   take(b.cursor, (size_t)n_views * kBuckets * sizeof(int));
   take(b.status, 256);
   b.total = off;
-  take(b.acc, n * 9 * sizeof(float));
+  take(b.acc, n * acc_stride * sizeof(float));
   take(b.radii, n * sizeof(int));
   b.bwd_total = off;
   return b;
@@ -1488,11 +1537,22 @@ size_t ocrf_rasterize_backward_workspace_bytes(int P, int n_views) {
   return raster_layout(nullptr, P, n_views).bwd_total;
 }
 
+size_t ocrf_rasterize_backward_depth_workspace_bytes(int P, int n_views) {
+  if (P <= 0 || n_views <= 0) return 0;
+  return raster_layout(nullptr, P, n_views, 10).bwd_total;
+}
+
+}  // extern "C"
+
+// DEPTHG: the backward that also takes dL/d(mean depth) and dL/d(final_T) (either may be null): the same front end
+// and the same two launches, in their ten-sum instantiations.
+template <bool DEPTHG>
 static int rasterize_backward_impl(int P, int n_views, int H, int W, const float* means3D, const float* colors,
                                    const float* opacities, const float* scales, float scale_modifier,
                                    const float* rotations, const float* cov3D_precomp, const float* cameras,
-                                   const float* bg, const float* fwd_color, const float* fwd_final_T,
-                                   const uint32_t* fwd_n_contrib, const float* dL_dcolor, float* dL_dmeans3D,
+                                   const float* bg, const float* fwd_color, const float* fwd_depth,
+                                   const float* fwd_final_T, const uint32_t* fwd_n_contrib, const float* dL_dcolor,
+                                   const float* dL_ddepth, const float* dL_dfinal_T, float* dL_dmeans3D,
                                    float* dL_dcolors, float* dL_dopacity, float* dL_dscales, float* dL_drotations,
                                    float* dL_dcov3D, float* dL_dmeans2D, void* workspace, size_t workspace_bytes,
                                    ocrf_stream_t stream_) {
@@ -1505,10 +1565,11 @@ static int rasterize_backward_impl(int P, int n_views, int H, int W, const float
   const int gx = (W + kTileX - 1) / kTileX, gy = (H + kTileY - 1) / kTileY;
   if (gx > 65535 || gy > 65535) return (int)hipErrorInvalidValue;
   if (!workspace) return (int)hipErrorInvalidValue;
-  const RasterBufs b = raster_layout(workspace, P, n_views);
+  constexpr int kSums = DEPTHG ? 10 : 9;
+  const RasterBufs b = raster_layout(workspace, P, n_views, kSums);
   if (workspace_bytes < b.bwd_total) return (int)hipErrorInvalidValue;
   const Camera* cams = reinterpret_cast<const Camera*>(cameras);
-  hipError_t e = ocrf::zero_async(b.acc, (size_t)n_views * P * 9 * sizeof(float), stream);
+  hipError_t e = ocrf::zero_async(b.acc, (size_t)n_views * P * kSums * sizeof(float), stream);
   // the forward's lists again: one set of n_views views, no selection, no gate, its radii into the workspace
   if (e == hipSuccess)
     e = raster_front_end(b, Lists::kReference, P, n_views, n_views, W, H, gx, gy, means3D, opacities, scales,
@@ -1518,8 +1579,10 @@ static int rasterize_backward_impl(int P, int n_views, int H, int W, const float
   BwdArgs bw;
   bw.dL_dcolor = dL_dcolor; bw.fwd_color = fwd_color; bw.fwd_final_T = fwd_final_T;
   bw.fwd_n_contrib = fwd_n_contrib; bw.acc = b.acc;
-  const size_t lds = (size_t)kCapRec * 8 + (size_t)kStage * (16 + 16 + 16 + 4 + 36);
-  ocrf::launch(OCRF_K_RASTER_BLEND_BWD, raster_blend_kernel<false, true, true>, dim3(gx, (gy + 1) / 2, n_views),
+  bw.dL_ddepth = dL_ddepth; bw.dL_dfinal_T = dL_dfinal_T; bw.fwd_depth = fwd_depth;
+  const size_t lds = (size_t)kCapRec * 8 + (size_t)kStage * (16 + 16 + 16 + 4 + 4 * kSums);
+  ocrf::launch(DEPTHG ? OCRF_K_RASTER_BLEND_BWD_DEPTH : OCRF_K_RASTER_BLEND_BWD,
+               raster_blend_kernel<false, true, true, true, DEPTHG>, dim3(gx, (gy + 1) / 2, n_views),
                dim3(kBlock), lds, stream, (unsigned long long*)nullptr, P, W, H, gy, static_cast<const int*>(b.starts),
                static_cast<const Rect*>(b.rects), static_cast<const Rect*>(b.b_rect),
                static_cast<const unsigned long long*>(b.b_comp),
@@ -1527,12 +1590,15 @@ static int rasterize_backward_impl(int P, int n_views, int H, int W, const float
                (float*)nullptr, (float*)nullptr, (unsigned*)nullptr, b.status, bw, n_views, (int*)nullptr);
   e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
-  ocrf::launch(OCRF_K_RASTER_PRE_BWD, raster_preprocess_backward_kernel, dim3((P + kBlock - 1) / kBlock), dim3(kBlock),
+  ocrf::launch(DEPTHG ? OCRF_K_RASTER_PRE_BWD_DEPTH : OCRF_K_RASTER_PRE_BWD, raster_preprocess_backward_kernel<DEPTHG>,
+               dim3((P + kBlock - 1) / kBlock), dim3(kBlock),
                0, stream, P, n_views, W, H, means3D, scales, scale_modifier, rotations, cov3D_precomp, cams,
                static_cast<const int*>(b.radii), static_cast<const float*>(b.acc), dL_dmeans3D, dL_dcolors, dL_dopacity,
                dL_dscales, dL_drotations, dL_dcov3D, dL_dmeans2D);
   return (int)hipGetLastError();
 }
+
+extern "C" {
 
 int ocrf_rasterize_backward(int P, int n_views, int H, int W, const float* means3D, const float* colors,
                             const float* opacities, const float* scales, float scale_modifier,
@@ -1543,10 +1609,10 @@ int ocrf_rasterize_backward(int P, int n_views, int H, int W, const float* means
                             float* dL_dmeans2D, void* workspace, size_t workspace_bytes,
                             ocrf_stream_t stream) {
   if (!scales || !rotations) return (int)hipErrorInvalidValue;
-  return rasterize_backward_impl(P, n_views, H, W, means3D, colors, opacities, scales, scale_modifier, rotations,
-                                 nullptr, cameras, bg, fwd_color, fwd_final_T, fwd_n_contrib, dL_dcolor, dL_dmeans3D,
-                                 dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, nullptr, dL_dmeans2D, workspace,
-                                 workspace_bytes, stream);
+  return rasterize_backward_impl<false>(P, n_views, H, W, means3D, colors, opacities, scales, scale_modifier, rotations,
+                                        nullptr, cameras, bg, fwd_color, nullptr, fwd_final_T, fwd_n_contrib, dL_dcolor,
+                                        nullptr, nullptr, dL_dmeans3D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations,
+                                        nullptr, dL_dmeans2D, workspace, workspace_bytes, stream);
 }
 
 int ocrf_rasterize_backward_cov3d(int P, int n_views, int H, int W, const float* means3D, const float* colors,
@@ -1556,10 +1622,32 @@ int ocrf_rasterize_backward_cov3d(int P, int n_views, int H, int W, const float*
                                   float* dL_dcolors, float* dL_dopacity, float* dL_dcov3D, float* dL_dmeans2D,
                                   void* workspace, size_t workspace_bytes, ocrf_stream_t stream) {
   if (!cov3D_precomp) return (int)hipErrorInvalidValue;
-  return rasterize_backward_impl(P, n_views, H, W, means3D, colors, opacities, nullptr, 1.0f, nullptr, cov3D_precomp,
-                                 cameras, bg, fwd_color, fwd_final_T, fwd_n_contrib, dL_dcolor, dL_dmeans3D, dL_dcolors,
-                                 dL_dopacity, nullptr, nullptr, dL_dcov3D, dL_dmeans2D, workspace, workspace_bytes,
-                                 stream);
+  return rasterize_backward_impl<false>(P, n_views, H, W, means3D, colors, opacities, nullptr, 1.0f, nullptr,
+                                        cov3D_precomp, cameras, bg, fwd_color, nullptr, fwd_final_T, fwd_n_contrib,
+                                        dL_dcolor, nullptr, nullptr, dL_dmeans3D, dL_dcolors, dL_dopacity, nullptr, nullptr,
+                                        dL_dcov3D, dL_dmeans2D, workspace, workspace_bytes, stream);
+}
+
+int ocrf_rasterize_backward_depth(int P, int n_views, int H, int W, const float* means3D, const float* colors,
+                                  const float* opacities, const float* scales, float scale_modifier,
+                                  const float* rotations, const float* cov3D_precomp, const float* cameras,
+                                  const float* bg, const float* fwd_color, const float* fwd_depth,
+                                  const float* fwd_final_T, const uint32_t* fwd_n_contrib, const float* dL_dcolor,
+                                  const float* dL_ddepth, const float* dL_dfinal_T, float* dL_dmeans3D, float* dL_dcolors,
+                                  float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
+                                  float* dL_dmeans2D, void* workspace, size_t workspace_bytes, ocrf_stream_t stream) {
+  // no depth / final_T gradient at all is the colour-only entries' case; a depth gradient needs the forward's depth
+  if ((!dL_ddepth && !dL_dfinal_T) || (dL_ddepth && !fwd_depth)) return (int)hipErrorInvalidValue;
+  if (cov3D_precomp) {
+    scales = nullptr; rotations = nullptr; scale_modifier = 1.0f;
+    dL_dscales = nullptr; dL_drotations = nullptr;
+  } else {
+    dL_dcov3D = nullptr;
+  }
+  return rasterize_backward_impl<true>(P, n_views, H, W, means3D, colors, opacities, scales, scale_modifier, rotations,
+                                       cov3D_precomp, cameras, bg, fwd_color, fwd_depth, fwd_final_T, fwd_n_contrib,
+                                       dL_dcolor, dL_ddepth, dL_dfinal_T, dL_dmeans3D, dL_dcolors, dL_dopacity, dL_dscales,
+                                       dL_drotations, dL_dcov3D, dL_dmeans2D, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

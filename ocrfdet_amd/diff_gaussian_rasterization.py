@@ -21,8 +21,12 @@ single launch sequence and also returns ``final_T`` (1 - accumulated opacity) an
 
 Compute: ``csrc/rasterize.hip`` through the C ABI (``ocrf_rasterize_forward`` /
 ``ocrf_rasterize_backward``).  The backward covers what the fork's does — the colour output w.r.t.
-means3D, means2D (screen-space, for densification statistics), colours, opacities, scales, rotations;
-depth has no backward in the fork either (diff-gaussian-rasterization-w-depth/README.md:13).
+means3D, means2D (screen-space, for densification statistics), colours, opacities, scales, rotations.
+Depth has no backward in the fork (diff-gaussian-rasterization-w-depth/README.md:13); here it is differentiable on
+request: ``depth_mode='mean', depth_grad=True`` on ``GaussianRasterizer``, ``rasterize_views_autograd`` and
+``rasterize_packed_autograd`` makes the mean depth ``D = sum_i alpha_i T_i z_i`` (and, on the batched surfaces,
+``final_T``) differentiable outputs (``ocrf_rasterize_backward_depth``).  ``D`` is unnormalised; the normalised expected
+depth is ``D / (1 - final_T).clamp_min(eps)``, differentiable in both.  The defaults are the fork's graph.
 ``cov3D_precomp`` has its own backward (gradient w.r.t. the six covariance entries).  SH colours (``shs`` (P,M,3) with
 ``raster_settings.sh_degree`` / ``campos``; OcRFDet itself passes ``shs=None``) are evaluated by ``ocrf_sh_to_rgb`` into the
 (P,3) colours of the ordinary pipeline, forward and backward (``forward.cu:20-71``, ``backward.cu:20-140``).
@@ -118,12 +122,17 @@ def _camera_rows(packed_cameras, viewmatrices, projmatrices, tanfovx, tanfovy, H
 
 def rasterize_views_backward(grad_color, fwd, means3D, colors, opacities, scales, rotations, viewmatrices,
                              projmatrices, tanfovx, tanfovy, image_height, image_width, bg, scale_modifier=1.0,
-                             want_means2D=False, packed_cameras=None, cov3D_precomp=None):
+                             want_means2D=False, packed_cameras=None, cov3D_precomp=None, grad_depth=None,
+                             grad_final_T=None):
     """Backward of ``rasterize_views``' colour output, summed over the views.  ``fwd`` is the dict
     ``rasterize_views`` returned for the same inputs.  Returns a dict ``means3D`` (P,3), ``colors``
     (P,3), ``opacities`` (P,1), ``scales`` (P,3), ``rotations`` (P,4) [, ``means2D`` (V,P,3)]; with
     ``cov3D_precomp`` (P,6) (``scales`` / ``rotations`` None) ``cov3D`` (P,6) instead of the last two
-    (backward.cu:346-396 without computeCov3D's backward)."""
+    (backward.cu:346-396 without computeCov3D's backward).
+
+    ``grad_depth`` (V,[1,]H,W) / ``grad_final_T`` (V,H,W): gradients of the MEAN depth (``fwd`` then rendered with
+    ``depth_mode='mean'`` and holds ``'depth'``) and of ``final_T``.  With either one the call goes to
+    ``ocrf_rasterize_backward_depth``, which adds them to the same sums; without, to the colour-only entries."""
     has_cov = cov3D_precomp is not None
     _lib.require_cuda(means3D, colors, opacities, *((cov3D_precomp,) if has_cov else (scales, rotations)), grad_color)
     dev = means3D.device
@@ -145,7 +154,28 @@ def rasterize_views_backward(grad_color, fwd, means3D, colors, opacities, scales
     m2d = torch.empty(V, P, 3, device=dev) if want_means2D else None
     if m2d is not None:
         out['means2D'] = m2d
+    gd = gt = fd = None
+    if grad_depth is not None:
+        if fwd.get('depth') is None:
+            raise RuntimeError("rasterize_views_backward: grad_depth needs the forward's mean depth in fwd['depth']")
+        _lib.require_cuda(grad_depth, fwd['depth'])
+        if grad_depth.numel() != V * H * W or fwd['depth'].numel() != V * H * W:
+            raise RuntimeError('rasterize_views_backward: depth and its gradient do not match the view batch')
+        gd, fd = _f32c(grad_depth).reshape(V, H, W), _f32c(fwd['depth']).reshape(V, H, W)
+    if grad_final_T is not None:
+        _lib.require_cuda(grad_final_T)
+        if grad_final_T.numel() != V * H * W:
+            raise RuntimeError('rasterize_views_backward: grad_final_T does not match the view batch')
+        gt = _f32c(grad_final_T).reshape(V, H, W)
     if P == 0:
+        return out
+    if gd is not None or gt is not None:
+        ws = _lib.workspace.get(dev, _lib.lib().ocrf_rasterize_backward_depth_workspace_bytes(P, V), 'raster')
+        _lib.launch('ocrf_rasterize_backward_depth', dev, P, V, H, W, means3D, colors, opac,
+                    None if has_cov else _f32c(scales), float(scale_modifier), None if has_cov else _f32c(rotations),
+                    _f32c(cov3D_precomp).reshape(P, 6) if has_cov else None, cams, bg, fc, fd, ft, fn, g, gd, gt,
+                    out['means3D'], out['colors'], out['opacities'], out.get('scales'), out.get('rotations'),
+                    out.get('cov3D'), m2d, ws, ws.numel())
         return out
     ws = _lib.workspace.get(dev, _lib.lib().ocrf_rasterize_backward_workspace_bytes(P, V), 'raster')
     shared = (cams, bg, fc, ft, fn, g, out['means3D'], out['colors'], out['opacities'])
@@ -230,8 +260,10 @@ def rasterize_sets(means3D, colors, opacities, scales, rotations, packed_cameras
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                cov3Ds_precomp, raster_settings):
+                cov3Ds_precomp, raster_settings, depth_mode='median', depth_grad=False):
         rs = raster_settings
+        ctx.depth_grad = _check_depth_grad(depth_mode, depth_grad)
+        ctx.set_materialize_grads(False)
         ctx.has_sh = sh is not None and sh.numel() > 0
         if ctx.has_sh:
             # colours of THIS view from the SH coefficients (forward.cu:240-247); everything after is the ordinary pipeline
@@ -241,19 +273,21 @@ class _RasterizeGaussians(torch.autograd.Function):
                               rs.viewmatrix.reshape(1, 4, 4), rs.projmatrix.reshape(1, 4, 4),
                               float(rs.tanfovx), float(rs.tanfovy), rs.image_height, rs.image_width,
                               rs.bg, float(rs.scale_modifier), cov3Ds_precomp if ctx.has_cov else None,
+                              depth_mode=depth_mode,
                               want_n_contrib=any(ctx.needs_input_grad))      # only the backward reads it
         color, radii, depth = out['color'][0], out['radii'][0], out['depth'][0]
-        ctx.mark_non_differentiable(radii, depth)
+        ctx.mark_non_differentiable(radii, *(() if ctx.depth_grad else (depth,)))
         ctx.raster_settings = rs
         # the forward's outputs are saved through autograd (not as plain attributes): the backward
         # rebuilds S = C_out - T_final * bg from them, so an in-place edit of the rendered image
         # (clamp_, mul_) must raise instead of silently changing the gradients.  The same holds for the SH
         # coefficients and their clamp mask, which the backward of the colours reads: last in the tuple.
-        # The covariance is saved in the shape it came in: (cov3D,) or (scales, rotations)
+        # The covariance is saved in the shape it came in: (cov3D,) or (scales, rotations).  depth_grad: the mean depth is
+        # saved the same way (the backward needs D - prefix_D), in front of the SH pair.
         shape = (cov3Ds_precomp,) if ctx.has_cov else (scales, rotations)
         sh_saved = (sh, sh_clamped) if ctx.has_sh else ()
         ctx.save_for_backward(means3D, colors_precomp, opacities, *shape, color, out['final_T'], out.get('n_contrib'),
-                              *sh_saved)
+                              *((depth,) if ctx.depth_grad else ()), *sh_saved)
         return color, radii, depth
 
     @staticmethod
@@ -267,77 +301,118 @@ class _RasterizeGaussians(torch.autograd.Function):
         return d_means, d_sh.to(sh.dtype), None
 
     @staticmethod
-    def backward(ctx, grad_color, _r, _d):
+    def backward(ctx, grad_color, _r, grad_depth):
         """Gradient tuple in the reference's order (diff_gaussian_rasterization/__init__.py:96-149):
-        means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings."""
+        means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings (and None for the
+        two depth switches).  ``grad_depth`` is None unless the depth is differentiable and the loss reached it: the
+        colour-only entry runs then."""
         rs = ctx.raster_settings
         n = 4 if ctx.has_cov else 5
         means3D, colors, opacities, *shape = ctx.saved_tensors[:n]
         scales, rotations, cov = (None, None, *shape) if ctx.has_cov else (*shape, None)
         fwd_color, fwd_T, fwd_n = ctx.saved_tensors[n:n + 3]
         fwd = dict(color=fwd_color.unsqueeze(0), final_T=fwd_T, n_contrib=fwd_n)
+        if ctx.depth_grad and grad_depth is not None:
+            fwd['depth'] = ctx.saved_tensors[n + 3]
+        else:
+            grad_depth = None
+        if grad_color is None:
+            grad_color = torch.zeros_like(fwd_color)
         g = rasterize_views_backward(grad_color.unsqueeze(0), fwd, means3D, colors, opacities, scales, rotations,
                                      rs.viewmatrix.reshape(1, 4, 4), rs.projmatrix.reshape(1, 4, 4),
                                      float(rs.tanfovx), float(rs.tanfovy), rs.image_height, rs.image_width, rs.bg,
-                                     float(rs.scale_modifier), want_means2D=True, cov3D_precomp=cov)
+                                     float(rs.scale_modifier), want_means2D=True, cov3D_precomp=cov,
+                                     grad_depth=grad_depth)
         d_means, d_sh, d_col = _RasterizeGaussians._sh_grads(ctx, means3D, g)
         grads = (d_means, g['means2D'][0], d_sh, d_col, g['opacities'].reshape(opacities.shape),
                  g.get('scales'), g.get('rotations'), g['cov3D'].reshape(cov.shape) if ctx.has_cov else None, None)
         # inputs that were not tensors needing a gradient (means2D=None from render()) must get None
-        return tuple(v if need else None for v, need in zip(grads, ctx.needs_input_grad))
+        return tuple(v if need else None for v, need in zip(grads, ctx.needs_input_grad)) + (None, None)
 
 
 class _RasterizeViews(torch.autograd.Function):
     """Differentiable batched render over packed camera rows ((V,36) of ``pack_cameras``, on the device: nothing of the
     call or its backward touches the host's copy of the calibration): colour (V,3,H,W) w.r.t. the Gaussian
-    parameters, gradients summed over the views in one backward launch sequence."""
+    parameters, gradients summed over the views in one backward launch sequence.  With ``depth_grad`` (mean depth
+    only) the depth and ``final_T`` are differentiable too; a backward that neither of them reached is the colour-only
+    one."""
 
     @staticmethod
-    def forward(ctx, means3D, colors, opacities, scales, rotations, packed, H, W, bg, scale_modifier):
+    def forward(ctx, means3D, colors, opacities, scales, rotations, packed, H, W, bg, scale_modifier,
+                depth_mode='median', depth_grad=False):
+        ctx.depth_grad = _check_depth_grad(depth_mode, depth_grad)
+        ctx.set_materialize_grads(False)
         out = rasterize_views(means3D, colors, opacities, scales, rotations, None, None, None, None, H, W, bg,
-                              scale_modifier, packed_cameras=packed)
+                              scale_modifier, depth_mode=depth_mode, packed_cameras=packed)
         ctx.cam = (packed, H, W, bg, scale_modifier)
-        ctx.save_for_backward(means3D, colors, opacities, scales, rotations, out['color'], out['final_T'], out['n_contrib'])
-        ctx.mark_non_differentiable(out['depth'], out['radii'], out['final_T'])
+        # the rendered depth is saved through autograd like the colour: an in-place edit raises in backward
+        ctx.save_for_backward(means3D, colors, opacities, scales, rotations, out['color'], out['final_T'], out['n_contrib'],
+                              *((out['depth'],) if ctx.depth_grad else ()))
+        ctx.mark_non_differentiable(out['radii'], *(() if ctx.depth_grad else (out['depth'], out['final_T'])))
         return out['color'], out['depth'], out['final_T'], out['radii']
 
     @staticmethod
-    def backward(ctx, grad_color, _d, _t, _r):
-        means3D, colors, opacities, scales, rotations, fwd_color, fwd_T, fwd_n = ctx.saved_tensors
+    def backward(ctx, grad_color, grad_depth, grad_T, _r):
+        means3D, colors, opacities, scales, rotations, fwd_color, fwd_T, fwd_n = ctx.saved_tensors[:8]
         packed, H, W, bg, scale_modifier = ctx.cam
         fwd = dict(color=fwd_color, final_T=fwd_T, n_contrib=fwd_n)
+        if not ctx.depth_grad:
+            grad_depth = grad_T = None
+        if grad_depth is not None:
+            fwd['depth'] = ctx.saved_tensors[8]
+        if grad_color is None:
+            grad_color = torch.zeros_like(fwd_color)
         g = rasterize_views_backward(grad_color, fwd, means3D, colors, opacities, scales, rotations, None, None, None, None,
-                                     H, W, bg, scale_modifier, packed_cameras=packed)
+                                     H, W, bg, scale_modifier, packed_cameras=packed, grad_depth=grad_depth,
+                                     grad_final_T=grad_T)
         grads = (g['means3D'], g['colors'], g['opacities'].reshape(opacities.shape), g['scales'], g['rotations'])
-        return tuple(v if n else None for v, n in zip(grads, ctx.needs_input_grad)) + (None,) * 5
+        return tuple(v if n else None for v, n in zip(grads, ctx.needs_input_grad)) + (None,) * 7
+
+
+def _check_depth_grad(depth_mode, depth_grad):
+    """``depth_grad`` as a bool; only the mean depth has a gradient (the median depth is piecewise constant)."""
+    if depth_grad and depth_mode != 'mean':
+        raise ValueError(f"depth_grad=True needs depth_mode='mean' (the median depth is piecewise constant), "
+                         f'got depth_mode={depth_mode!r}')
+    return bool(depth_grad)
 
 
 def rasterize_views_autograd(means3D, colors, opacities, scales, rotations, viewmatrices, projmatrices, tanfovx,
-                             tanfovy, image_height, image_width, bg, scale_modifier=1.0):
+                             tanfovy, image_height, image_width, bg, scale_modifier=1.0, depth_mode='median',
+                             depth_grad=False):
     """``rasterize_views`` with autograd through the colour output: returns (color (V,3,H,W),
-    depth (V,1,H,W), final_T (V,H,W), radii (V,P))."""
+    depth (V,1,H,W), final_T (V,H,W), radii (V,P)).  ``depth_grad=True`` (needs ``depth_mode='mean'``, else
+    ``ValueError``): the mean depth ``D = sum_i alpha_i T_i z_i`` and ``final_T`` are differentiable outputs too.  ``D`` is
+    not normalised; a normalised expected depth is ``D / (1 - final_T).clamp_min(eps)``, differentiable in both."""
     H, W = int(image_height), int(image_width)
     packed = pack_cameras(viewmatrices, projmatrices, tanfovx, tanfovy, H, W, means3D.device)
-    return _RasterizeViews.apply(means3D, colors, opacities, scales, rotations, packed, H, W, bg, scale_modifier)
+    return _RasterizeViews.apply(means3D, colors, opacities, scales, rotations, packed, H, W, bg, scale_modifier,
+                                 depth_mode, depth_grad)
 
 
-def rasterize_packed_autograd(means3D, colors, opacities, scales, rotations, packed_cameras, image_height, image_width, bg):
+def rasterize_packed_autograd(means3D, colors, opacities, scales, rotations, packed_cameras, image_height, image_width, bg,
+                              depth_mode='median', depth_grad=False):
     """``rasterize_views_autograd`` with the cameras given as packed device rows (V,36):
-    -> (color (V,3,H,W), depth (V,1,H,W), final_T (V,H,W), radii (V,P)), autograd through the colour."""
+    -> (color (V,3,H,W), depth (V,1,H,W), final_T (V,H,W), radii (V,P)), autograd through the colour and, with
+    ``depth_grad=True`` (``depth_mode='mean'``), through the depth and ``final_T``."""
     return _RasterizeViews.apply(means3D, colors, opacities, scales, rotations, packed_cameras, int(image_height),
-                                 int(image_width), bg, 1.0)
+                                 int(image_width), bg, 1.0, depth_mode, depth_grad)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                        cov3Ds_precomp, raster_settings):
+                        cov3Ds_precomp, raster_settings, depth_mode='median', depth_grad=False):
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales,
-                                     rotations, cov3Ds_precomp, raster_settings)
+                                     rotations, cov3Ds_precomp, raster_settings, depth_mode, depth_grad)
 
 
 class GaussianRasterizer(nn.Module):
-    def __init__(self, raster_settings):
+    """``depth_mode`` / ``depth_grad`` are beyond the fork: with ``depth_mode='mean', depth_grad=True`` the third return
+    is the differentiable mean depth (the fork's depth has no backward)."""
+
+    def __init__(self, raster_settings, depth_mode='median', depth_grad=False):
         super().__init__()
         self.raster_settings = raster_settings
+        self.depth_mode, self.depth_grad = depth_mode, _check_depth_grad(depth_mode, depth_grad)
 
     def markVisible(self, positions):
         """Near-plane test of ``in_frustum`` (auxiliary.h:139-164): view-space z > 0.2."""
@@ -354,4 +429,4 @@ class GaussianRasterizer(nn.Module):
                 ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                   cov3D_precomp, self.raster_settings)
+                                   cov3D_precomp, self.raster_settings, self.depth_mode, self.depth_grad)

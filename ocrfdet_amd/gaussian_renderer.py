@@ -11,9 +11,10 @@ from .diff_gaussian_rasterization import GaussianRasterizationSettings, Gaussian
 __all__ = ['render', 'render_views', 'getWorld2View2', 'getProjectionMatrix', 'camera_from_calibration']
 
 
-def render(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color):
+def render(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, depth_grad=False):
     """data: dict(FovX, FovY, height, width, world_view_transform, full_proj_transform,
-    camera_center) -> (image (3,H,W), depth (1,H,W)).  ``bg_color``: list of 3 floats."""
+    camera_center) -> (image (3,H,W), depth (1,H,W)).  ``bg_color``: list of 3 floats.  ``depth_grad=True`` (beyond the
+    reference): the depth is the differentiable MEAN depth instead of the median depth, which has no gradient."""
     bg = torch.tensor(bg_color, dtype=torch.float32, device=pts_xyz.device)
     settings = GaussianRasterizationSettings(
         image_height=int(data['height']), image_width=int(data['width']),
@@ -21,7 +22,8 @@ def render(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color):
         bg=bg, scale_modifier=1.0, viewmatrix=data['world_view_transform'],
         projmatrix=data['full_proj_transform'], sh_degree=3, campos=data['camera_center'],
         prefiltered=False)
-    image, _, depth = GaussianRasterizer(raster_settings=settings)(
+    image, _, depth = GaussianRasterizer(raster_settings=settings, depth_mode='mean' if depth_grad else 'median',
+                                         depth_grad=depth_grad)(
         means3D=pts_xyz, means2D=None, shs=None, colors_precomp=pts_rgb, opacities=opacity,
         scales=scales, rotations=rotations, cov3D_precomp=None)
     return image, depth

@@ -343,8 +343,9 @@ class RenderLosses(torch.autograd.Function):
 
 
 def render_losses(gt_images, renders, render_depths, gt_depth, cam_idx_list, boxes_per_sample, use_mask, depth_range):
-    """Fused ``render_losses_torch``: ``boxes_per_sample`` the (n_b,4) boxes of each sample's camera.  The render depth
-    of the second render (``render_depth_G_all``) gets no gradient, as from the rasteriser."""
+    """Fused ``render_losses_torch``: ``boxes_per_sample`` the (n_b,4) boxes of each sample's camera.  Every render depth
+    that requires grad gets a gradient; the second (``render_depth_G_all``) requires one only when the rasteriser rendered
+    it differentiable (``depth_mode='mean', depth_grad=True``: ``OcRFViewTransformerFull.render_depth_grad``)."""
     r0, r1, r2 = renders
     _lib.require_cuda(gt_images, r0, r1, r2, *render_depths, gt_depth)
     B, C, H, W = r0.shape
@@ -366,6 +367,6 @@ def render_losses(gt_images, renders, render_depths, gt_depth, cam_idx_list, box
     dev = r0.device
     boxes, meta, n_max = pack_boxes(boxes_per_sample, cam_idx_list, dev)
     f = lambda t: t.float()                    # noqa: E731
-    return RenderLosses.apply(f(gt_images), f(r0), f(r1), f(r2), f(rd0), rd1.detach().float(), f(rd2), boxes, meta,
+    return RenderLosses.apply(f(gt_images), f(r0), f(r1), f(r2), f(rd0), f(rd1), f(rd2), boxes, meta,
                               n_max, bool(use_mask), True, f(gt_depth), tuple(float(v) for v in depth_range[:2]),
                               (20.0, 1.0, 1.0), (B, 3, C, H, W))

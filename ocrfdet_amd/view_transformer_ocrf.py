@@ -483,6 +483,12 @@ def _float32_under_autocast(fn):
 
 
 class OcRFViewTransformerFull(nn.Module):
+    # True: the training path (view_transform_core) renders the Gaussians with depth_mode='mean', depth_grad=True, so
+    # render_depth_G_all is the differentiable mean depth and loss_render_depth reaches the Gaussians through
+    # LinearWeightedDepth and get_loss.  The reference's depth has no gradient: off by default.  Eval, the captured
+    # graph and the planned renders keep the median depth.  A class attribute: not in the state_dict.
+    render_depth_grad = False
+
     def __init__(self, pc_range, bev_h=128, bev_w=128, num_height=13, collapse_z=True, loss_semantic_weight=25,
                  depth_threshold=1, semantic_threshold=0.25, depthnet_cfg=dict(), grid_config=None, input_size=None,
                  downsample=16, in_channels=512, out_channels=64, accelerate=False, loss_depth_weight=3.0,
@@ -893,7 +899,9 @@ class OcRFViewTransformerFull(nn.Module):
         render_G, render_depth_G = [], []
         for bs in range(B):
             img, dep, _, _ = rasterize_packed_autograd(voxel_coor[bs], color[bs], opacity[bs], scaling[bs], rotation[bs],
-                                                       cameras['packed'][bs:bs + 1], H, W, self._bg)
+                                                       cameras['packed'][bs:bs + 1], H, W, self._bg,
+                                                       **(dict(depth_mode='mean', depth_grad=True)
+                                                          if self.render_depth_grad else {}))
             render_G.append(img), render_depth_G.append(dep)
         render_image_G_all, render_depth_G_all = torch.cat(render_G), torch.cat(render_depth_G)
         render_image = self.LinearWeightedImage(render_image_G_all, render_N)

@@ -2,7 +2,7 @@
 ``view_transform_core`` (per-forward index preparation, differentiable torch ops around the HIP
 bev_pool_v2 / rasteriser forward + backward kernels), wall time per iteration and the top device ops.
 
-    python tools/time_neck_train.py [config] [--iters N] [--profile]
+    python tools/time_neck_train.py [config] [--iters N] [--profile] [--render-depth-grad]
 """
 import argparse
 import os
@@ -23,6 +23,8 @@ def main():
     ap.add_argument('--host', action='store_true', help='cProfile of the host side')
     ap.add_argument('--layers', action='store_true', help="the voxel heads as torch layers (fused_heads_training = False)")
     ap.add_argument('--cudnn-benchmark', action='store_true', help='torch.backends.cudnn.benchmark = True (MIOpen find mode)')
+    ap.add_argument('--render-depth-grad', action='store_true',
+                    help='render_depth_grad = True: the mean depth rendered differentiable, its gradient through the rasteriser')
     ap.add_argument('--host-geometry', action='store_true', help='device_geometry = False: the calibration read to the host per forward')
     a = ap.parse_args()
     cfg = synthetic.CONFIGS[a.config]
@@ -31,6 +33,7 @@ def main():
     neck = hotpath.NeckPath(cfg, dev, accelerate=False)
     m = neck.module.train()
     m.fused_heads_training = not a.layers
+    m.render_depth_grad = bool(a.render_depth_grad)
     if a.host_geometry:
         m.device_geometry = False
     pre = neck.depthnet_out
