@@ -1155,6 +1155,27 @@ int ocrf_hoa1_forward(const float *opacity, const float *alpha, const float *wei
 int ocrf_hoa1_weights_len(void);
 
 /*
+ * HOA-1 under autograd (csrc/hoa1_train.hip), same configuration and limits as ocrf_hoa1_forward (Y/6 >= 6, X/6 >= 6,
+ * <= 1600 query tokens, <= 128 kv tokens; anything else: hipErrorInvalidValue).
+ * ocrf_hoa1_train_workspace_floats (host only): floats of the workspace both calls take, 0 for an unsupported shape.  The
+ *   forward keeps the kv tokens (k | v | grid) and every query token's softmax maximum and sum in it; the rest is the
+ *   backward's scratch.  The caller keeps it untouched between the forward and its backward.
+ * ocrf_hoa1_forward_train: out as ocrf_hoa1_forward, bit for bit when dropout_mask is NULL.  dropout_mask
+ *   (B, ntok, nkv) bytes, 1 = keep: the attention weights are multiplied by mask * dropout_scale (1 / (1 - p)) after the
+ *   softmax normalisation, as nn.Dropout does on attn.  Two launches.
+ * ocrf_hoa1_backward: grad_out (B,13,Y,X) -> grad_opacity, grad_alpha (B,13,Y,X) and grad_weights
+ *   (ocrf_hoa1_weights_len() floats, the layout of `weights`), with the inputs, mask and workspace of the forward.  Six
+ *   launches, no atomics (reruns are bit-identical), no host read, no memset.
+ */
+size_t ocrf_hoa1_train_workspace_floats(int B, int Y, int X);
+int ocrf_hoa1_forward_train(const float *opacity, const float *alpha, const float *weights, int B, int Y, int X,
+                            float offset_scale, const unsigned char *dropout_mask, float dropout_scale, float *workspace,
+                            float *out, ocrf_stream_t stream);
+int ocrf_hoa1_backward(const float *grad_out, const float *opacity, const float *alpha, const float *weights, int B, int Y,
+                       int X, float offset_scale, const unsigned char *dropout_mask, float dropout_scale, float *workspace,
+                       float *grad_opacity, float *grad_alpha, float *grad_weights, ocrf_stream_t stream);
+
+/*
  * Pillar projections consumed by the colour / alpha sampling and retain_valid_pixels
  * (view_transformer_ocrf.py:1057-1066 from get_sampling_point :687-740), same inputs as
  * ocrf_ht_prepare (pc_range: 6 floats in HOST memory):
@@ -1527,7 +1548,14 @@ enum {
   OCRF_K_KD_FINAL = 144,              /* kd_final_kernel */
   OCRF_K_KD_BWD = 145,                /* kd_backward_kernel */
   OCRF_K_RASTER_BLEND_BWD_DEPTH = 146, /* raster_blend_kernel<false, true, true, true, true> */
-  OCRF_K_RASTER_PRE_BWD_DEPTH = 147   /* raster_preprocess_backward_kernel<true> */
+  OCRF_K_RASTER_PRE_BWD_DEPTH = 147,  /* raster_preprocess_backward_kernel<true> */
+  OCRF_K_HOA1_ATTN_TRAIN = 148,       /* hoa1_attention_train_kernel */
+  OCRF_K_HOA1_UP_GRAD = 149,          /* hoa1_up_grad_kernel */
+  OCRF_K_HOA1_ATTN_GRAD = 150,        /* hoa1_attn_grad_kernel */
+  OCRF_K_HOA1_KV_GRAD = 151,          /* hoa1_kv_grad_kernel */
+  OCRF_K_HOA1_TOKEN_GRAD = 152,       /* hoa1_token_grad_kernel */
+  OCRF_K_HOA1_PIXEL_GRAD = 153,       /* hoa1_pixel_grad_kernel */
+  OCRF_K_HOA1_WEIGHT_SUM = 154        /* hoa1_weight_sum_kernel */
 };
 const char *ocrf_kernel_name(int kernel_id);           /* symbol as rocprofv3 prints it */
 /* Diagnostic: a one-thread kernel that stores the device's constant-rate clock (wall_clock64, 100 MHz)

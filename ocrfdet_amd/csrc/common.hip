@@ -196,6 +196,13 @@ const char* ocrf_kernel_name(int kernel_id) {
     case OCRF_K_KD_BWD: return "kd_backward_kernel";
     case OCRF_K_RASTER_BLEND_BWD_DEPTH: return "raster_blend_kernel<false, true, true, true, true>";
     case OCRF_K_RASTER_PRE_BWD_DEPTH: return "raster_preprocess_backward_kernel<true>";
+    case OCRF_K_HOA1_ATTN_TRAIN: return "hoa1_attention_train_kernel";
+    case OCRF_K_HOA1_UP_GRAD: return "hoa1_up_grad_kernel";
+    case OCRF_K_HOA1_ATTN_GRAD: return "hoa1_attn_grad_kernel";
+    case OCRF_K_HOA1_KV_GRAD: return "hoa1_kv_grad_kernel";
+    case OCRF_K_HOA1_TOKEN_GRAD: return "hoa1_token_grad_kernel";
+    case OCRF_K_HOA1_PIXEL_GRAD: return "hoa1_pixel_grad_kernel";
+    case OCRF_K_HOA1_WEIGHT_SUM: return "hoa1_weight_sum_kernel";
     default: return "";
   }
 }

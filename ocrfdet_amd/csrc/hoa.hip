@@ -13,6 +13,7 @@
 
 #include <algorithm>
 
+#include "hoa1_common.h"
 #include "launch.h"
 #include "ocrf_hip.h"
 
@@ -762,29 +763,10 @@ int ocrf_hoa_gated_conv1x1(const float* x, const float* gate, int B, int C, int 
 // =================================================================================================
 namespace {
 
-constexpr int kHD = 13, kHI = 8, kHMaxTok = 1600, kHMaxKV = 128;
-constexpr int oQ = 0, oDW = oQ + 8 * 13, oDB = oDW + 8 * 36, oPW = oDB + 8, oK = oPW + 16, oV = oK + 104,
-              oO = oV + 104, oOB = oO + 104, oC0W = oOB + 13, oC0B = oC0W + 6, oC1W = oC0B + 3, oC1B = oC1W + 9,
-              oC2W = oC1B + 3, oC2B = oC2W + 3, kHoaWeights = oC2B + 1;
-
-// F.interpolate(..., mode='bilinear', align_corners=True) sample of one channel plane at (sy, sx): the four corner taps
-// and their mix, separately — corner q of a sample is one load, the mix happens once they are all back
-struct AcTaps { int y0, y1, x0, x1; float ly, lx; };
-__device__ __forceinline__ AcTaps ac_taps(int H, int W, float sy, float sx) {
-  AcTaps a;
-  a.y0 = min((int)sy, H - 1); a.x0 = min((int)sx, W - 1);
-  a.y1 = min(a.y0 + 1, H - 1); a.x1 = min(a.x0 + 1, W - 1);
-  a.ly = sy - (float)a.y0; a.lx = sx - (float)a.x0;
-  return a;
-}
-__device__ __forceinline__ float ac_mix(float p00, float p01, float p10, float p11, float ly, float lx) {
-  const float top = p00 * (1.f - lx) + p01 * lx;
-  const float bot = p10 * (1.f - lx) + p11 * lx;
-  return top * (1.f - ly) + bot * ly;
-}
-
-constexpr int kHoaWLoads = (kHoaWeights + kBlock - 1) / kBlock;      // 3
-constexpr int kHoaWLds = kHoaWLoads * kBlock;    // LDS copy of the packed weights: every thread stores every word it loaded
+// the fixed configuration, the packed-weight offsets, ac_taps / ac_mix, the DPP merge and the body of the attention
+// kernel: hoa1_common.h (shared with the training kernels, hoa1_train.hip)
+using namespace ocrf::hoa1;
+static_assert(kHoaBlock == kBlock, "the HOA-1 kernels are written for 256 threads");
 
 // ONE kv token per workgroup (grid (nkv, B): 128 workgroups at 2 x 200 x 200, where one workgroup per 8 tokens left
 // the chip to 16): offsets (depthwise 6x6 stride 4 pad 1 -> GELU -> 1x1 -> tanh -> * scale), sampling grid, bilinear
@@ -927,22 +909,10 @@ __global__ __launch_bounds__(kBlock) void hoa1_kv_kernel(const float* __restrict
   }
 }
 
-// attention + to_out + bilinear upsample + residual of one 16x16 output tile.  The tile's pixels interpolate between
-// at most kTT x kTT tokens of the (hq, wq) attention map ((hq - 1) / (Y - 1) < 1/6: 15 pixels span < 2.5 tokens); the
-// workgroup rebuilds q for those tokens from the opacity volume, runs their attention over the sample's kv tokens
-// (LDS, online softmax, kAttSplit lanes per token merged by a fixed DPP butterfly) and keeps the 13 output channels
-// in LDS for the interpolation: no q / attention buffers and no separate upsample launch.  Tokens shared by
-// neighbouring tiles are recomputed (a token's attention is ~6 k flops).  The kernel is a latency chain on a chip
-// it cannot fill (338 workgroups at 2 x 200 x 200), so every global load — the token's 52 bilinear taps, the pixel's
-// 13 residual values, weights and kv tokens — is issued before the first barrier.
-constexpr int kAttSplit = 8, kTP = 16, kTT = 5;
-constexpr int kKvLoads = (kHMaxKV * 9 + kBlock - 1) / kBlock;       // 8-byte words of the kv tokens per thread (5)
-constexpr int kDppXor1 = 0xB1, kDppXor2 = 0x4E, kDppMirror8 = 0x141;   // quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror
-template <int CTRL>
-__device__ __forceinline__ float hoa_dpp(float x) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, true));
-}
-
+// attention + to_out + bilinear upsample + residual of one 16x16 output tile (structure: hoa1_common.h,
+// attention_upsample_body, which the training forward instantiates with the dropout mask and the saved softmax
+// state and which tests/test_hoa1_train_gpu.py holds to this kernel bit for bit).  Kept as its own kernel: behind
+// the shared body hipcc allocated 111 instead of 94 VGPRs for it (4 instead of 5 waves per SIMD).
 __global__ __launch_bounds__(kBlock) void hoa1_attention_upsample_kernel(
     const float* __restrict__ opacity, const float* __restrict__ kvbuf, const float* __restrict__ wts, int Y, int X,
     int hq, int wq, int nkv, float* __restrict__ out) {
@@ -1091,6 +1061,16 @@ __global__ __launch_bounds__(kBlock) void hoa1_attention_upsample_kernel(
 
 }  // namespace
 
+namespace ocrf {
+namespace hoa1 {
+void launch_kv(hipStream_t stream, const float* opacity, const float* alpha, const float* wts, int B, int Y, int X, int hq,
+               int wq, int hk, int wk, float offset_scale, float* kvbuf) {
+  ocrf::launch(OCRF_K_HOA1_KV, hoa1_kv_kernel, dim3(hk * wk, B), dim3(kBlock), 0, stream, opacity, alpha, wts, Y, X, hq, wq,
+               hk, wk, offset_scale, kvbuf);
+}
+}  // namespace hoa1
+}  // namespace ocrf
+
 extern "C" {
 
 int ocrf_hoa1_weights_len(void) { return kHoaWeights; }
@@ -1106,8 +1086,7 @@ int ocrf_hoa1_forward(const float* opacity, const float* alpha, const float* wei
   if (ntok > kHMaxTok || nkv > kHMaxKV) return (int)hipErrorInvalidValue;
   // (the workspace keeps round 1's layout att | q | kv; only the kv part is used now)
   float* kvbuf = att_workspace + (size_t)B * kHD * ntok + (size_t)B * ntok * kHI;
-  ocrf::launch(OCRF_K_HOA1_KV, hoa1_kv_kernel, dim3(nkv, B), dim3(kBlock), 0, stream, opacity, alpha, weights, Y, X, hq, wq,
-               hk, wk, offset_scale, kvbuf);
+  launch_kv(stream, opacity, alpha, weights, B, Y, X, hq, wq, hk, wk, offset_scale, kvbuf);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
   ocrf::launch(OCRF_K_HOA1_ATTN, hoa1_attention_upsample_kernel, dim3((X + kTP - 1) / kTP, (Y + kTP - 1) / kTP, B),

@@ -18,10 +18,14 @@ channel mean/max + 7x7 conv + sigmoid + gate for HOA-3, global max + quarter MLP
 ``ca(x) * x`` multiply) for HeightAttention.  The small dense convolutions of the UNet and of the
 deformable attention stay PyTorch-ROCm ops (plumbing; SURVEY.md 8a rows a24-a25 note they are
 ~40 tiny launches, not custom-kernel targets of the reference either).  GPU tensors only.
+
+HOA-1 also has a differentiable fused path, opt-in: ``hoa1(..., fused_training=True)`` runs ``_Hoa1Train``
+(``csrc/hoa1_train.hip``: two launches forward, six backward) instead of the op sequence under autograd.
 """
 import torch
 import torch.nn.functional as F
 from torch import nn
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .neck_ops import tall_linear
@@ -456,6 +460,11 @@ class _Scale(nn.Module):
         return x * self.scale
 
 
+def _dropout_scale(p):
+    """What nn.Dropout(p) multiplies the kept entries with."""
+    return 1.0 / (1.0 - p) if p < 1.0 else 0.0
+
+
 class CPB(nn.Module):
     """Continuous positional bias MLP (cross_attention_2d.py:49-89)."""
 
@@ -505,7 +514,9 @@ class DeformableAttention2D(nn.Module):
         self.to_v = nn.Conv2d(dim, inner, 1, groups=offset_groups if group_key_values else 1, bias=False)
         self.to_out = nn.Conv2d(inner, dim, 1)
 
-    def forward(self, x_q, x_kv, return_vgrid=False):
+    def forward(self, x_q, x_kv, return_vgrid=False, dropout_mask=None):
+        """``dropout_mask`` (b, queries, keys), 1 = keep: applied to ``attn`` with the scale ``1 / (1 - dropout.p)`` in
+        place of ``nn.Dropout`` (whatever the mode), so that a fixed mask can be compared across implementations."""
         b, _, h, w = x_q.shape
         g, heads = self.offset_groups, self.heads
         q = self.to_q(x_q)
@@ -527,18 +538,27 @@ class DeformableAttention2D(nn.Module):
         grid_scaled = _normalize_grid(_grid_like(x_kv), dim=0)
         sim = sim + self.rel_pos_bias(grid_scaled, vgrid_scaled)
         sim = sim - sim.amax(dim=-1, keepdim=True).detach()
-        attn = self.dropout(sim.softmax(dim=-1))
+        attn = sim.softmax(dim=-1)
+        if dropout_mask is None:
+            attn = self.dropout(attn)
+        else:
+            attn = attn * (dropout_mask.unsqueeze(1).to(attn.dtype) * _dropout_scale(self.dropout.p))
         out = (attn @ v).transpose(2, 3).reshape(b, -1, h, w)
         out = self.to_out(out)
         return (out, vgrid) if return_vgrid else out
 
 
+def _hoa1_params(m):
+    """The 14 parameters in the order of the packed vector (csrc/hoa1_common.h)."""
+    return [m.to_q.weight, m.to_offsets[0].weight, m.to_offsets[0].bias, m.to_offsets[2].weight, m.to_k.weight,
+            m.to_v.weight, m.to_out.weight, m.to_out.bias, m.rel_pos_bias.mlp[0][0].weight, m.rel_pos_bias.mlp[0][0].bias,
+            m.rel_pos_bias.mlp[1][0].weight, m.rel_pos_bias.mlp[1][0].bias, m.rel_pos_bias.mlp[2].weight,
+            m.rel_pos_bias.mlp[2].bias]
+
+
 def _hoa1_packed(m):
     """The module's weights in the layout of ``ocrf_hoa1_forward`` (csrc/hoa.hip); cached."""
-    ps = [m.to_q.weight, m.to_offsets[0].weight, m.to_offsets[0].bias, m.to_offsets[2].weight, m.to_k.weight,
-          m.to_v.weight, m.to_out.weight, m.to_out.bias, m.rel_pos_bias.mlp[0][0].weight, m.rel_pos_bias.mlp[0][0].bias,
-          m.rel_pos_bias.mlp[1][0].weight, m.rel_pos_bias.mlp[1][0].bias, m.rel_pos_bias.mlp[2].weight,
-          m.rel_pos_bias.mlp[2].bias]
+    ps = _hoa1_params(m)
     key = tuple((p._version, p.data_ptr()) for p in ps)
     if getattr(m, '_hoa1_key', None) != key:
         with torch.no_grad():
@@ -554,13 +574,85 @@ def _hoa1_fusable(m, x):
             and len(m.rel_pos_bias.mlp) == 3 and m.rel_pos_bias.mlp[0][0].out_features == 3)
 
 
-def hoa1(defor_cross_attention, opacity, alpha_lidar, heights, Y, X):
+def _hoa1_config(m):
+    """The one configuration the HOA-1 kernels are written for (csrc/hoa1_common.h)."""
+    return (m.heads == 1 and m.offset_groups == 1 and m.downsample_factor == 4 and m.to_q.in_channels == 13
+            and m.to_q.out_channels == 8 and m.to_offsets[0].kernel_size == (6, 6) and len(m.rel_pos_bias.mlp) == 3
+            and m.rel_pos_bias.mlp[0][0].out_features == 3)
+
+
+def _hoa1_train_fusable(m, o, alpha, heights, Y, X):
+    """Operands ``_Hoa1Train`` takes: CUDA, float32, the fixed configuration, a map size the library has a workspace
+    for (``ocrf_hoa1_train_workspace_floats``: the size limits live in the library)."""
+    if not (o.is_cuda and alpha.is_cuda and o.device == alpha.device and o.dtype == alpha.dtype == torch.float32
+            and heights == 13 and alpha.shape == o.shape and _hoa1_config(m)):
+        return False
+    if not all(p.dtype == torch.float32 and p.device == o.device for p in _hoa1_params(m)):
+        return False
+    return _lib.lib().ocrf_hoa1_train_workspace_floats(o.shape[0], Y, X) > 0
+
+
+class _Hoa1Train(torch.autograd.Function):
+    """HOA-1 forward and backward on the HIP kernels of ``csrc/hoa1_train.hip``: two launches forward (the eval
+    kernels' arithmetic, an optional dropout keep-mask on the attention weights, the kv tokens and every query token's
+    softmax state kept), six backward (no atomics: reruns are bit-identical).  Inputs: opacity, alpha (B,13,Y,X), the
+    14 parameters in ``_hoa1_params`` order, the keep-mask (B, queries, keys) uint8 or None, then the module (for its
+    cached weight pack) and the dropout scale.  A double backward is not supported: the backward says so."""
+
+    @staticmethod
+    def forward(ctx, opacity, alpha, *rest):
+        params, (mask, m, dscale) = rest[:14], rest[14:]
+        o32, a32 = _f32c(opacity), _f32c(alpha)
+        B, _, Y, X = o32.shape
+        w = _hoa1_packed(m)                     # one cat, or the cached pack when versions and pointers match
+        L = _lib.lib()
+        assert w.numel() == L.ocrf_hoa1_weights_len()
+        ws = torch.empty(L.ocrf_hoa1_train_workspace_floats(B, Y, X), device=o32.device)
+        out = torch.empty_like(o32)
+        scale = float(m.to_offsets[4].scale)
+        _lib.launch('ocrf_hoa1_forward_train', o32.device, o32, a32, w, B, Y, X, scale, mask, float(dscale), ws, out)
+        ctx.save_for_backward(o32, a32, w, mask, ws)
+        ctx.offset_scale, ctx.dscale = scale, float(dscale)
+        ctx.param_shapes = [p.shape for p in params]
+        return out
+
+    @staticmethod
+    @once_differentiable                 # no double backward: differentiating the backward raises
+    def backward(ctx, grad_out):
+        o32, a32, w, mask, ws = ctx.saved_tensors
+        B, _, Y, X = o32.shape
+        go = _f32c(grad_out)
+        g_op, g_al, g_w = torch.empty_like(o32), torch.empty_like(a32), torch.empty_like(w)
+        _lib.launch('ocrf_hoa1_backward', o32.device, go, o32, a32, w, B, Y, X, ctx.offset_scale, mask, ctx.dscale, ws,
+                    g_op, g_al, g_w)
+        grads = [g.view(s) for g, s in zip(g_w.split([s.numel() for s in ctx.param_shapes]), ctx.param_shapes)]
+        return (g_op, g_al, *grads, None, None, None)
+
+
+def hoa1(defor_cross_attention, opacity, alpha_lidar, heights, Y, X, fused_training=False, dropout_mask=None):
     """view_transformer_ocrf.py:1159-1161: opacity (B*heights*Y*X, 1) from A_MLP (B = 1 in the
     reference's per-sample loop), alpha_lidar (B,heights,Y,X) -> opacity_alpha (B,heights,Y,X).
-    Eval mode on the GPU runs the two fused HIP kernels; otherwise the reference's op sequence."""
+    Eval mode on the GPU runs the two fused HIP kernels; otherwise the reference's op sequence.
+
+    ``fused_training`` (off by default): on CUDA, in float32, for the fixed configuration and within the size limits the
+    differentiable ``_Hoa1Train`` runs instead, in ``train()`` and in ``eval()``; anything else takes the op sequence.
+    ``dropout_mask`` (B, queries, keys) uint8, 1 = keep: used in place of the module's dropout on both paths, with the
+    scale ``1 / (1 - dropout.p)``.  Without one, ``train()`` with ``dropout.p > 0`` draws it with one torch call from
+    torch's generator (no sync); ``eval()`` has no dropout."""
     m = defor_cross_attention
     o = opacity.view(-1, heights, Y, X)
-    if _hoa1_fusable(m, o) and heights == 13:
+    if fused_training and _hoa1_train_fusable(m, o, alpha_lidar, heights, Y, X):
+        mask, p = dropout_mask, float(m.dropout.p)
+        hq, wq = Y // 6, X // 6
+        shape = (o.shape[0], hq * wq, ((hq - 4) // 4 + 1) * ((wq - 4) // 4 + 1))        # (B, queries, keys)
+        if mask is None and m.training and p > 0.0:
+            mask = torch.empty(shape, dtype=torch.uint8, device=o.device).bernoulli_(1.0 - p)
+        if mask is not None:
+            if tuple(mask.shape) != shape or mask.device != o.device:
+                raise _lib.OcrfHipError(f'dropout_mask must be {shape} on {o.device}, got {tuple(mask.shape)} on {mask.device}')
+            mask = mask.to(torch.uint8).contiguous()
+        return _Hoa1Train.apply(o, alpha_lidar, *_hoa1_params(m), mask, m, _dropout_scale(p) if mask is not None else 1.0)
+    if _hoa1_fusable(m, o) and heights == 13 and dropout_mask is None:
         _lib.require_cuda(o, alpha_lidar)
         o32, a32 = _f32c(o), _f32c(alpha_lidar)
         B = o32.shape[0]
@@ -573,5 +665,5 @@ def hoa1(defor_cross_attention, opacity, alpha_lidar, heights, Y, X):
     size = (int(Y / 6), int(X / 6))
     o_up = F.interpolate(o, size=size, mode='bilinear', align_corners=True)
     a_up = F.interpolate(alpha_lidar, size=size, mode='bilinear', align_corners=True)
-    att = m(o_up, a_up)
+    att = m(o_up, a_up) if dropout_mask is None else m(o_up, a_up, dropout_mask=dropout_mask)
     return F.interpolate(att, size=(Y, X), mode='bilinear', align_corners=True) + o

@@ -488,6 +488,10 @@ class OcRFViewTransformerFull(nn.Module):
     # LinearWeightedDepth and get_loss.  The reference's depth has no gradient: off by default.  Eval, the captured
     # graph and the planned renders keep the median depth.  A class attribute: not in the state_dict.
     render_depth_grad = False
+    # Training branch: HOA-1 on the fused HIP forward + backward (hoa._Hoa1Train: 2 + 6 launches) instead of the
+    # reference's ~50-launch op sequence and its autograd.  Off by default (measured, not yet the default);
+    # shapes and dtypes the kernels do not take fall back to the op sequence.  A class attribute: not in the state_dict.
+    fused_hoa1_training = False
 
     def __init__(self, pc_range, bev_h=128, bev_w=128, num_height=13, collapse_z=True, loss_semantic_weight=25,
                  depth_threshold=1, semantic_threshold=0.25, depthnet_cfg=dict(), grid_config=None, input_size=None,
@@ -909,7 +913,8 @@ class OcRFViewTransformerFull(nn.Module):
         gt_images = imgs_wo_norm[torch.arange(B, device=x.device), cam_sel.long()] / 255.0
 
         # HOA-1 for the whole batch (the reference loops samples, :1159-1161)
-        opacity_alpha = hoa.hoa1(self.defor_cross_attention, opacity.reshape(-1, 1), alpha_lidar, Zh, Y, X)
+        opacity_alpha = hoa.hoa1(self.defor_cross_attention, opacity.reshape(-1, 1), alpha_lidar, Zh, Y, X,
+                                 fused_training=self.fused_hoa1_training)
 
         channel_feat = self.fuser(lss_feat, ht_feat)
         zeros = _zeros((B, Y, X), x)            # positional encodings only read its shape / device

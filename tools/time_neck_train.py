@@ -26,6 +26,10 @@ def main():
     ap.add_argument('--render-depth-grad', action='store_true',
                     help='render_depth_grad = True: the mean depth rendered differentiable, its gradient through the rasteriser')
     ap.add_argument('--host-geometry', action='store_true', help='device_geometry = False: the calibration read to the host per forward')
+    ap.add_argument('--fused-hoa1', action='store_true',
+                    help='fused_hoa1_training = True: HOA-1 on the fused HIP forward + backward (csrc/hoa1_train.hip)')
+    ap.add_argument('--ab-hoa1', action='store_true',
+                    help='alternate blocks with fused_hoa1_training off and on in this process; prints both with their spread')
     a = ap.parse_args()
     cfg = synthetic.CONFIGS[a.config]
     dev = torch.device('cuda:0')
@@ -49,6 +53,27 @@ def main():
         m.zero_grad(set_to_none=True)
         return loss
 
+    m.fused_hoa1_training = bool(a.fused_hoa1)
+    if a.ab_hoa1:
+        arms = {False: [], True: []}
+        for on in (False, True):
+            m.fused_hoa1_training = on
+            for _ in range(3):
+                it()
+        for _ in range(7):
+            for on in (False, True):
+                m.fused_hoa1_training = on
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(a.iters):
+                    it()
+                torch.cuda.synchronize()
+                arms[on].append(1e3 * (time.perf_counter() - t0) / a.iters)
+        for on in (False, True):
+            b = sorted(arms[on])
+            print(f'{cfg.name}: B={neck.batch} fused_hoa1_training={on}: {b[0]:.2f} ms per iteration '
+                  f'(best of 7 alternating blocks of {a.iters}; median {b[3]:.2f}, worst {b[-1]:.2f})')
+        return
     for _ in range(3):
         it()
     # host-bound (~1 500 launches per iteration): the host's clock and placement move the figure by 20 % from block to
