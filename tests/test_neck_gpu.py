@@ -642,6 +642,39 @@ def test_graphed_neck_follows_new_inputs(core):
         assert ex[5] == cams
 
 
+def test_pinned_staging_outlasts_its_slots(core):
+    """More refreshes in a row than the pinned rings have slots (four behind a staged camera dict, eight behind
+    ``_small_h2d``): every refresh lands on the device with the host's values, and the module, which owns neither pinned
+    memory nor events, stays deep-copyable."""
+    import copy
+    import math
+    from ocrfdet_amd import gaussian_renderer
+    from ocrfdet_amd.diff_gaussian_rasterization import pack_cameras
+    m, inp = copy.deepcopy(core['m']), core['inp']
+    dev, (H, W) = inp[0].device, m.input_size
+    geo = m._geometry(inp)                       # host formulation: the rows are made on the host and staged
+    K, c2w = inp[3].cpu(), inp[11].cpu()
+
+    def row(b, c):
+        cam = gaussian_renderer.camera_from_calibration(K[b, c].numpy(), c2w[b, c].numpy(), H, W, znear=m.znear, zfar=m.zfar)
+        return pack_cameras(cam['world_view_transform'][None], cam['full_proj_transform'][None],
+                            math.tan(float(cam['FovX']) * 0.5), math.tan(float(cam['FovY']) * 0.5), H, W, 'cpu')
+    rng = np.random.default_rng(3)
+    cams = m.stage_cameras(geo, [0, 0], dev)
+    for _ in range(10):
+        pick = [int(c) for c in rng.integers(0, 6, core['B'])]
+        assert m.stage_cameras(geo, pick, dev, out=cams) is cams
+        assert cams['cam_idx_list'] == pick and cams['cam_sel'].dtype == torch.int32
+        assert cams['cam_sel'].cpu().tolist() == pick
+        assert torch.equal(cams['packed'].cpu(), torch.cat([row(b, c) for b, c in enumerate(pick)]))
+    for i in range(10):
+        host = torch.from_numpy(rng.integers(-2 ** 31, 2 ** 31, 1 + 7 * i, dtype=np.int64).astype(np.int32))
+        got = m._small_h2d(host, dev)
+        assert got.dtype == torch.int32 and got.device == dev and torch.equal(got.cpu(), host)
+    m2 = copy.deepcopy(m)
+    assert torch.equal(m2._small_h2d(host, dev).cpu(), host)
+
+
 def test_cbam_entry_points_edge_cases_and_argument_errors():
     """Tiny planes (fewer elements than one chunk / one tile), K at the channel_mlp limit, and the C entry points'
     refusal of malformed calls (hipErrorInvalidValue = 1 instead of a launch)."""

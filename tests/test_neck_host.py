@@ -43,6 +43,23 @@ def test_config_referenced_attribute_names(core):
         assert hasattr(m, name), name
 
 
+def test_geometry_mode_table():
+    """``neck_geometry.choose_mode`` over every (accelerate, fused, device_geometry, calibration on the GPU): only a
+    forward-only geometry of a module without ``accelerate`` may write the persistent rank buffers, and it alone is lazy;
+    ranks are synchronised exactly under autograd without device geometry; ``pre_compute`` synchronises and owns its ranks."""
+    from ocrfdet_amd import neck_geometry as ng
+    assert ng.CACHED == (True, False, False)            # (sync, lazy, persistent)
+    for acc in (False, True):
+        for fused in (False, True):
+            for dg in (None, True, False):
+                for on_dev in (False, True):
+                    m = ng.choose_mode(acc, fused, dg, on_dev)
+                    device_ranks = fused or (dg is not False and on_dev and not acc)
+                    assert m.sync == (not device_ranks)
+                    assert m.lazy == m.persistent == (fused and not acc)
+                    assert not (m.persistent and m.sync)
+
+
 def test_gauss_head_packing(core):
     cfg, g, p, m = core
     prm = neck_ops.pack_gauss_head_params(m.ObtainVoxelFeature, m.S_MLP, m.R_MLP, m.A_MLP, m.C_MLP).numpy().astype(np.float64)
