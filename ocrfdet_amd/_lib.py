@@ -228,6 +228,47 @@ class StepRecorder:
         return CompiledStep(self.items, self.names)
 
 
+class StepStreams:
+    """The streams of a step by name, in slot order (slot 0, ``'main'``, is the caller's), and the hand-overs between
+    them.  ``fork`` / ``join`` issue the ordering edge — an event recorded on ``frm`` that ``to`` then waits for — and mark
+    it for the recorder of a step that is being recorded, in that order: a recorded step holds the edges that were issued.
+    Each edge's event is created once and reused (``wait_stream`` creates one per call, ~5 us of host time); ``bind``
+    takes the caller's stream and the recorder of the next step and keeps the events.  ``event``: the event type."""
+
+    def __init__(self, streams, names, rec=None, event=None):
+        assert len(streams) == len(names) == len(set(names)) and names[0] == 'main'
+        self.streams, self.names, self.rec = list(streams), tuple(names), rec
+        self.slot = {name: i for i, name in enumerate(names)}
+        self._event, self._events = event or torch.cuda.Event, {}
+
+    def bind(self, cur, rec=None):
+        self.streams[0], self.rec = cur, rec
+        return self
+
+    def __getitem__(self, name):
+        return self.streams[self.slot[name]]
+
+    def _edge(self, frm, to):
+        a, b = self.slot[frm], self.slot[to]
+        if (a, b) not in self._events:
+            self._events[a, b] = self._event()
+        self._events[a, b].record(self.streams[a])
+        self.streams[b].wait_event(self._events[a, b])
+        return a, b
+
+    def fork(self, frm, to):
+        """``to`` starts behind everything issued on ``frm`` so far."""
+        a, b = self._edge(frm, to)
+        if self.rec is not None:
+            self.rec.fork(a, b)
+
+    def join(self, frm, to):
+        """What ``to`` gets next is ordered behind everything issued on ``frm`` so far."""
+        a, b = self._edge(frm, to)
+        if self.rec is not None:
+            self.rec.join(a, b)
+
+
 class _RecordingLib:
     """What ``lib()`` hands out while a step is recorded: every entry point that enqueues work (its last parameter is an
     ``ocrf_stream_t``, ``_ENQUEUEING``) is logged, then called; every other one is passed through."""

@@ -88,9 +88,6 @@ def test_replayed_step_follows_a_scene_that_turns_object_centric_and_back(cuda):
         for h in (hp, ref):
             for k, v in sets[kind].items():
                 h.frame_gauss[0][k].copy_(torch.from_numpy(v).to(cuda))
-        for plan, f0, nf, gg in hp._plans():
-            for k in ('rgb', 'opacity', 'scales', 'rotations'):
-                gg[k].copy_(torch.stack([hp.frame_gauss[b][k] for b in range(f0, f0 + nf)]))
         got = hp.step(depth, feat)[2][0]
         want = ref.render()[0]
         torch.cuda.synchronize()
@@ -264,7 +261,6 @@ def test_cfg2_step_options_give_the_same_outputs(cuda):
     # new values everywhere, same tensors: inputs of the poolings, of the renders, of HOA
     d2, f2 = ref_hp.make_inputs(seed=5)
     d1.copy_(d2), f1.copy_(f2)
-    X, Y, _ = cfg.bev_xyz
     for hpx in (one, ref_hp):
         g = torch.Generator(device='cpu').manual_seed(11)
         for fg in hpx.frame_gauss:
@@ -272,11 +268,6 @@ def test_cfg2_step_options_give_the_same_outputs(cuda):
             fg['rgb'].copy_(torch.rand(fg['rgb'].shape, generator=g).to(cuda))
             fg['scales'].copy_((torch.rand(fg['scales'].shape, generator=g) * 0.1 + 0.7).to(cuda))
         hpx.alpha_lidar.copy_(torch.rand(hpx.alpha_lidar.shape, generator=g).to(cuda))
-        # the step reads the STACKED parameter tensors of its plans and the flat opacity volume of HOA-1: in place too
-        for plan, f0, nf, gg in hpx._plans():
-            for k in ('rgb', 'opacity', 'scales', 'rotations'):
-                gg[k].copy_(torch.stack([hpx.frame_gauss[b][k] for b in range(f0, f0 + nf)]))
-        hpx._opac_flat.copy_(torch.stack([fg['opacity'].view(cfg.num_height, Y, X) for fg in hpx.frame_gauss]).reshape(-1, 1))
     want = ref_hp.step(d2, f2)
     got = one.step(d1, f1)
     torch.cuda.synchronize()
@@ -311,15 +302,6 @@ def test_per_sample_step_by_one_host_call_equals_the_step_call_by_call(cuda, kw)
         for fg in hpx.frame_gauss:
             fg['opacity'].copy_((torch.rand(fg['opacity'].shape, generator=g) * 0.3 + 0.3).to(cuda))
             fg['rgb'].copy_(torch.rand(fg['rgb'].shape, generator=g).to(cuda))
-        if hpx.render_plans:
-            for plan, f0, nf, gg in hpx.render_plans:
-                for k in ('rgb', 'opacity'):
-                    gg[k].copy_(torch.stack([hpx.frame_gauss[b][k] for b in range(f0, f0 + nf)]))
-        if getattr(hpx, '_sets', None):                  # the per-call render of the batch reads the stacked sets
-            for k in ('rgb', 'opacity'):
-                hpx._sets[k].copy_(torch.stack([fg[k] for fg in hpx.frame_gauss]))
-        X, Y, _ = cfg.bev_xyz
-        hpx._opac_flat.copy_(torch.stack([fg['opacity'].view(cfg.num_height, Y, X) for fg in hpx.frame_gauss]).reshape(-1, 1))
     want = ref.step(d2, f2)
     got = one.step(d1, f1)
     torch.cuda.synchronize()
