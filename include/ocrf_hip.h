@@ -693,8 +693,8 @@ int ocrf_upsample_cat_backward_bf16(int B, int C2, int C1, int Hin, int Win, int
                                     unsigned short *grad_x1, ocrf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
- * Temporal BEV alignment (csrc/bev_align.hip, csrc/bev_align_index.h): BEVDet4D.shift_feature
- * (mmdet3d/models/detectors/bevdet.py:305-376), the warp of an adjacent frame's BEV feature into the key ego frame,
+ * Temporal BEV alignment (csrc/bev_align.hip, csrc/bev_align_index.h, csrc/bev_align_taps.h):
+ * BEVDet4D.shift_feature (mmdet3d/models/detectors/bevdet.py:305-376), the warp of an adjacent frame's BEV feature into the key ego frame,
  * written into its channels of the concatenation in front of the BEV encoder (bevdet.py:529-536, ocrfdet.py:267-274).
  * Deterministic, no atomics, no workspace, no host reads.  f32.
  *
@@ -741,6 +741,44 @@ int ocrf_bev_align_forward_bf16(int n, int c, int h, int w, const unsigned short
 int ocrf_bev_align_backward_bf16(int n, int c, int h, int w, const unsigned short *grad_out,
                                  long long grad_batch_stride, const float *tf, unsigned short *grad_x,
                                  ocrf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Streaming temporal alignment (csrc/bev_stream_align.hip): the whole concatenation in front of the BEV encoder in ONE
+ * launch, from a ring of the last S = K + 1 key-frame BEV maps (OcRFDet4D.stream_step; K = num_adj).  Forward only,
+ * f32.  Deterministic, no atomics, no workspace, no host reads; every destination element is written once.
+ *
+ * Operands:
+ *   ring (S, B, C, h, w) f32 contiguous: slot `head` (0 <= head < S) holds the current key frame's map (the caller
+ *     writes it there; the kernel does not copy it in), slot (head - e) mod S the map of e steps ago.
+ *   valid (B) int32 on the device: the number of real history frames of each sample (0 right after a reset); a negative
+ *     value counts as 0, one above K as K.
+ *   sensor2ego0, ego2global0 (S, B, 4, 4) f32, bda (S, B, 3, 3) f32: per slot the raw poses of camera 0 and the BEV
+ *     augmentation at that slot's time.  Affine (last row (0, 0, 0, 1), not checked).
+ *   interval_x / _y, lower_x / _y: the view transformer's grid_interval and grid_lower_bound, x and y; intervals > 0.
+ *   align: 0 copies every group (align_after_view_transfromation = False).
+ *   out: element [b][g * C + ch][i][j] at out + b * out_batch_stride + ((g * C + ch) * h + i) * w + j (floats), so that
+ *     out may be a channel slice of a wider buffer; out_batch_stride >= S * C * h * w.
+ *   tf_out (K, B, 3, 3) f32 or NULL: tf_out[g][b] receives the nine floats that group g of sample b was warped with, the
+ *     identity for a copied group.
+ *
+ * Channel group g = 0 .. K - 1 holds age a = K - g (oldest first, as extract_img_feat orders its list), group K the key
+ * frame.  For sample b the effective age is e = min(a, valid[b]) and the source slot s = (head - e) mod S.  e = 0 or
+ * align = 0: the group is a copy of the source plane.  Otherwise it is the warp of the source plane under tf by the
+ * sampling rule of the temporal BEV alignment above, the same code: bit for bit what ocrf_bev_align_forward writes for
+ * that plane and that tf.  tf is temporal.feature_transform's value for curr = inv(E_h) E_h S_h, adj = inv(E_h) E_s S_s
+ * (E = ego2global0, S = sensor2ego0, h = head), bda = bda[h], bda_adj = bda[s], evaluated in f64 with closed-form affine
+ * inverses (adjugate / determinant) and rounded once to f32; once per (b, g) and workgroup, not per pixel.
+ * 16-byte stores when h * w and out_batch_stride are multiples of 4 and out is 16-byte aligned, 4-byte stores otherwise.
+ * With S = 1 (K = 0) the launch only copies.
+ * Limits: S, B, C, h, w > 0, S * B < 2^24, the ring and out ((B - 1) * out_batch_stride + S * C * h * w floats) below
+ * 2 GiB; anything else (a head out of range, a stride below a row, a NULL operand other than tf_out, an interval that is
+ * not > 0) returns hipErrorInvalidValue and launches nothing.  With non-finite poses the result is unspecified, but no
+ * address outside the operands is formed.
+ */
+int ocrf_bev_stream_align(int S, int B, int C, int h, int w, const float *ring, int head, const int *valid,
+                          const float *sensor2ego0, const float *ego2global0, const float *bda, double interval_x,
+                          double interval_y, double lower_x, double lower_y, int align, float *out,
+                          long long out_batch_stride, float *tf_out, ocrf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Frame poses of the 4D detectors (csrc/frame_poses.hip): the pose algebra of BEVDet4D.prepare_inputs
@@ -1555,7 +1593,8 @@ enum {
   OCRF_K_HOA1_KV_GRAD = 151,          /* hoa1_kv_grad_kernel */
   OCRF_K_HOA1_TOKEN_GRAD = 152,       /* hoa1_token_grad_kernel */
   OCRF_K_HOA1_PIXEL_GRAD = 153,       /* hoa1_pixel_grad_kernel */
-  OCRF_K_HOA1_WEIGHT_SUM = 154        /* hoa1_weight_sum_kernel */
+  OCRF_K_HOA1_WEIGHT_SUM = 154,       /* hoa1_weight_sum_kernel */
+  OCRF_K_BEV_STREAM_ALIGN = 155       /* bev_stream_align_kernel<V> */
 };
 const char *ocrf_kernel_name(int kernel_id);           /* symbol as rocprofv3 prints it */
 /* Diagnostic: a one-thread kernel that stores the device's constant-rate clock (wall_clock64, 100 MHz)

@@ -30,6 +30,9 @@ Drop-in mirrors of the reference's Python surface for that path (and nothing els
   DefaultOptimizerConstructor custom_keys
   ...detectors.ocrfdet.OcRFDet4D and              ocrfdet_amd.detector (OcRFDet4D, prepare_inputs, frame_poses,
   BEVDet4D.prepare_inputs                         frame_poses_torch, also exported here)
+  (none: the reference's sequential test cannot   ocrfdet_amd.streaming (stream_step, StreamState, key_frame_inputs;
+  run)                                            OcRFDet4D.stream_step / simple_test_stream) over
+                                                  temporal.stream_align / stream_align_torch
   ...datasets.pipelines.loading                   ocrfdet_amd.inputs (sample_augmentation, post_homography,
   PrepareImageInputs (image and point-label       sample_bda_augmentation, bev_transform, assemble_img_inputs,
   stage), LoadAnnotationsBEVDepth.bev_transform   prepare_images, point_label_maps and their *_torch forms, also
@@ -51,11 +54,12 @@ from . import _lib  # noqa: F401
 __version__ = "0.1.0"
 _LAZY = ('ResNet', 'CustomFPN', 'ImageEncoder')
 _LAZY_TEMPORAL = ('feature_transform', 'shift_feature', 'shift_feature_torch', 'align_and_cat', 'gen_grid',
-                  'shift_feature_method')
+                  'shift_feature_method', 'stream_align', 'stream_align_torch')
 _LAZY_OPTIM = ('FusedAdamW', 'ModelEMA', 'paramwise_groups')
 _LAZY_DETECTOR = ('OcRFDet4D', 'OcRFDet4DVGGT', 'prepare_inputs', 'frame_poses', 'frame_poses_torch')
 _LAZY_DISTILL = ('build_cost_volume', 'group_corr_volume', 'group_corr_volume_torch', 'kd_losses', 'kd_losses_torch',
                  'CrossAttentionAlign')
+_LAZY_STREAMING = ('StreamState', 'stream_step', 'key_frame_inputs')
 _LAZY_INPUTS = ('sample_augmentation', 'post_homography', 'sample_bda_augmentation', 'bev_transform',
                 'assemble_img_inputs', 'prepare_images', 'prepare_images_torch', 'point_label_maps',
                 'point_label_maps_torch')
@@ -80,6 +84,9 @@ def __getattr__(name):
     if name in _LAZY_DISTILL:
         from . import distill
         return getattr(distill, name)
+    if name in _LAZY_STREAMING:
+        from . import streaming
+        return getattr(streaming, name)
     if name in _LAZY_INPUTS:
         from . import inputs
         return getattr(inputs, name)

@@ -3,7 +3,8 @@
 // encoder (bevdet.py:529-536, ocrfdet.py:267-274).  The transform is affine in pixel coordinates (gen_grid's tf), so
 // the forward is grid_sample(bilinear, zeros, align_corners=True) without the grid tensor and without the normalise /
 // unnormalise round trip, and the backward is a gather: no atomics, no workspace, no host synchronisation; repeated runs
-// are bit-identical.  The sampling rule and the box of candidates are in bev_align_index.h.
+// are bit-identical.  The sampling rule and the box of candidates are in bev_align_index.h, the taps of an output
+// pixel and the value sampled at them in bev_align_taps.h (bev_stream_align.hip warps with the same).
 //
 // Forward.  A unit is (batch, block of kChannels channels, chunk of the plane); a thread walks its groups of V output
 // pixels as plane_walk.h describes, computes the four tap addresses, the validity of the taps and the two fractions of
@@ -28,6 +29,7 @@
 #include <hip/hip_runtime.h>
 
 #include "bev_align_index.h"
+#include "bev_align_taps.h"
 #include "launch.h"
 #include "ocrf_hip.h"
 #include "plane_walk.h"
@@ -39,41 +41,6 @@ using namespace bev_align;
 
 constexpr int kChannels = 2;                       // channels per forward unit: coordinates are computed once for them
 constexpr int kBwdChannels = 4;                    // channels per backward thread
-
-struct Taps {
-  int r0, r1, c0, c1;                              // row offsets (row * w) and columns of the taps, clamped to the plane
-  float lx, ly;
-  bool v00, v01, v10, v11;                         // the tap lies inside the plane
-};
-
-__device__ __forceinline__ Taps taps_at(const float* t, int i, int j, int h, int w) {
-  const Sample s = sample_at(t, i, j);
-  const bool x0_in = s.x0 >= 0.0f && s.x0 <= (float)(w - 1), x1_in = s.x0 >= -1.0f && s.x0 <= (float)(w - 2);
-  const bool y0_in = s.y0 >= 0.0f && s.y0 <= (float)(h - 1), y1_in = s.y0 >= -1.0f && s.y0 <= (float)(h - 2);
-  const int x0 = clamped_floor(s.x0, w), y0 = clamped_floor(s.y0, h);
-  Taps p;
-  p.c0 = max(x0, 0);
-  p.c1 = min(x0 + 1, w - 1);
-  p.r0 = max(y0, 0) * w;
-  p.r1 = min(y0 + 1, h - 1) * w;
-  p.lx = s.lx;
-  p.ly = s.ly;
-  p.v00 = x0_in && y0_in;
-  p.v01 = x1_in && y0_in;
-  p.v10 = x0_in && y1_in;
-  p.v11 = x1_in && y1_in;
-  return p;
-}
-
-// T: float or bf16_t.  ONE float32 expression for both: the bf16 form widens its taps, the caller rounds the result once
-template <typename T>
-__device__ __forceinline__ float sample_value(const T* __restrict__ s, const Taps& p) {
-  const float v00 = p.v00 ? load_f32(s + (p.r0 + p.c0)) : 0.0f, v01 = p.v01 ? load_f32(s + (p.r0 + p.c1)) : 0.0f;
-  const float v10 = p.v10 ? load_f32(s + (p.r1 + p.c0)) : 0.0f, v11 = p.v11 ? load_f32(s + (p.r1 + p.c1)) : 0.0f;
-  const float mx = 1.0f - p.lx, my = 1.0f - p.ly;
-  const float top = mx * v00 + p.lx * v01, bot = mx * v10 + p.lx * v11;
-  return my * top + p.ly * bot;
-}
 
 template <typename T, int V>
 __global__ void __launch_bounds__(kThreads) bev_align_kernel(int c, int h, int w, int cblocks, int chunks, int units,

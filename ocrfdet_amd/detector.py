@@ -15,7 +15,9 @@
 is not checked: a check would synchronise.  Nothing assumes an orthonormal rotation; a singular matrix gives inf / nan.
 
 Out of scope: mmcv's ``Config`` and registries, ``DataContainer`` unwrapping, ``train_step``, the dataset pipeline,
-``grid_mask``, ``extract_img_feat_sequential`` and ``pred_prev`` (both raise ``NotImplementedError``).
+``grid_mask``, ``extract_img_feat_sequential`` and ``pred_prev`` (both raise ``NotImplementedError``: neither can run in
+the reference; streaming inference has its own names, ``OcRFDet4D.stream_step`` / ``simple_test_stream``,
+``ocrfdet_amd/streaming.py``).
 """
 import torch
 from torch import nn
@@ -259,11 +261,11 @@ class OcRFDet4D(nn.Module):
                               fused=self.fused_poses)
 
     # ---------------------------------------------------------------- ocrfdet.py:144-173
-    def prepare_bev_feat(self, img, rot, tran, sensor2keyego, ego2global, intrin, post_rot, post_tran, bda, mlp_input,
-                         feat_prev_iv, k2s_sensor, extra_ref_frame, imgs_wo_norm, imgs_wo_aug, c2w):
-        if extra_ref_frame:
-            return None, None, None, self.extract_stereo_ref_feat(img), None
-        x, stereo_feat = self.image_encoder(img, stereo=True)
+    def lift_to_bev(self, x, stereo_feat, img, rot, tran, intrin, post_rot, post_tran, bda, mlp_input, feat_prev_iv,
+                    k2s_sensor, imgs_wo_norm, imgs_wo_aug, c2w):
+        """What follows the image encoder in ``prepare_bev_feat``: the view transformer on the image feature ``x`` with
+        ``cv_feat_list = [feat_prev_iv, stereo_feat]``, then ``pre_process_net``.  ``(bev_feat, depth, bev_mask,
+        extras)``."""
         vt = self.img_view_transformer
         metas = dict(k2s_sensor=k2s_sensor, intrins=intrin, post_rots=post_rot, post_trans=post_tran,
                      frustum=vt.cv_frustum.to(x), cv_downsample=4, downsample=vt.downsample,
@@ -272,10 +274,39 @@ class OcRFDet4D(nn.Module):
             [x, rot, tran, intrin, post_rot, post_tran, bda, mlp_input, img, imgs_wo_norm, imgs_wo_aug, c2w], metas)
         if self.pre_process:
             bev_feat = self.pre_process_net(bev_feat)[0]
+        return bev_feat, depth, bev_mask, extras
+
+    def prepare_bev_feat(self, img, rot, tran, sensor2keyego, ego2global, intrin, post_rot, post_tran, bda, mlp_input,
+                         feat_prev_iv, k2s_sensor, extra_ref_frame, imgs_wo_norm, imgs_wo_aug, c2w):
+        if extra_ref_frame:
+            return None, None, None, self.extract_stereo_ref_feat(img), None
+        x, stereo_feat = self.image_encoder(img, stereo=True)
+        bev_feat, depth, bev_mask, extras = self.lift_to_bev(x, stereo_feat, img, rot, tran, intrin, post_rot, post_tran,
+                                                             bda, mlp_input, feat_prev_iv, k2s_sensor, imgs_wo_norm,
+                                                             imgs_wo_aug, c2w)
         return bev_feat, depth, bev_mask, stereo_feat, extras
 
     def extract_img_feat_sequential(self, inputs, feat_prev):
-        raise NotImplementedError('extract_img_feat_sequential: the streaming test is not part of this package')
+        raise NotImplementedError('extract_img_feat_sequential: the reference\'s sequential test cannot run (it calls '
+                                  'prepare_bev_feat with 8 of its 16 arguments); streaming inference is stream_step')
+
+    # ---------------------------------------------------------------- streaming inference (ocrfdet_amd/streaming.py)
+    def stream_step(self, img_inputs, state=None, new_sequence=None, multi_frame=False):
+        """One streaming step on ONE frame: ``(([x], depth, bev_mask), state)``.  ``streaming.stream_step``."""
+        from .streaming import stream_step
+        return stream_step(self, img_inputs, state=state, new_sequence=new_sequence, multi_frame=multi_frame)
+
+    def simple_test_stream(self, img_inputs, img_metas=None, state=None, new_sequence=None, rescale=False,
+                           multi_frame=False):
+        """``simple_test`` on a stream: ``stream_step``, then ``simple_test_pts``.  Returns ``(results, state)``,
+        ``results`` the list over the samples of ``dict(pts_bbox=dict(boxes_3d, scores_3d, labels_3d))``."""
+        (img_feats, _, _), state = self.stream_step(img_inputs, state=state, new_sequence=new_sequence,
+                                                    multi_frame=multi_frame)
+        if img_metas is None:
+            img_metas = [dict() for _ in range(img_inputs[0].shape[0])]
+        with torch.no_grad():
+            pts = self.simple_test_pts(img_feats, img_metas, rescale=rescale)
+        return [dict(pts_bbox=pts_bbox) for pts_bbox in pts], state
 
     # ---------------------------------------------------------------- ocrfdet.py:206-279
     def extract_img_feat(self, img, img_metas=None, pred_prev=False, sequential=False, **kwargs):
@@ -466,14 +497,9 @@ class OcRFDet4DVGGT(OcRFDet4D):
             return None, None, None, self.extract_stereo_ref_feat(img), None, None
         x, stereo_feat = self.image_encoder(img, stereo=True)
         F_ts = self.distill_volumes(img, x) if self.training and key_frame else None
-        vt = self.img_view_transformer
-        metas = dict(k2s_sensor=k2s_sensor, intrins=intrin, post_rots=post_rot, post_trans=post_tran,
-                     frustum=vt.cv_frustum.to(x), cv_downsample=4, downsample=vt.downsample,
-                     grid_config=vt.grid_config, cv_feat_list=[feat_prev_iv, stereo_feat])
-        bev_feat, depth, bev_mask, extras = vt(
-            [x, rot, tran, intrin, post_rot, post_tran, bda, mlp_input, img, imgs_wo_norm, imgs_wo_aug, c2w], metas)
-        if self.pre_process:
-            bev_feat = self.pre_process_net(bev_feat)[0]
+        bev_feat, depth, bev_mask, extras = self.lift_to_bev(x, stereo_feat, img, rot, tran, intrin, post_rot, post_tran,
+                                                             bda, mlp_input, feat_prev_iv, k2s_sensor, imgs_wo_norm,
+                                                             imgs_wo_aug, c2w)
         return bev_feat, depth, bev_mask, stereo_feat, extras, F_ts
 
     # ---------------------------------------------------------------- ocrfdet_vggt.py:328-401

@@ -8,6 +8,8 @@
 * ``shift_feature(input, tf, out=None, keep_bf16=False)``: the same warp as one HIP launch (``csrc/bev_align.hip``), its
   backward a gather launch without atomics: deterministic;
 * ``align_and_cat``: every frame warped (the key frame copied) straight into its channels of one concatenation;
+* ``stream_align`` / ``stream_align_torch``: the streaming step's concatenation from a ring of the last key-frame maps
+  and the raw poses kept with them, the transforms included, as one HIP launch (``csrc/bev_stream_align.hip``);
 * ``gen_grid`` / ``shift_feature_method``: the reference's method signatures, adopted by assignment.
 
 Sampling rule of the kernels (include/ocrf_hip.h): with ``t`` the float32 rounding of rows 0 and 1 of ``tf``, output
@@ -360,6 +362,122 @@ def align_and_cat(feats, frame_ids, sensor2keyegos, bda, grid_interval, grid_low
     if keep:
         return torch.cat([x if tf is None else _shift_feature_torch_bf16(x, tf) for x, tf in zip(feats, tfs)], dim=1)
     return torch.cat([x if tf is None else shift_feature_torch(_cast(x), tf) for x, tf in zip(feats, tfs)], dim=1)
+
+
+# ------------------------------------------------------------------------------------------------ streaming
+def _check_stream_operands(ring, head, valid, sensor2ego0, ego2global0, bda, out):
+    if ring.dim() != 5 or ring.numel() == 0:
+        raise ValueError(f'ring must be a non-empty (S, B, C, H, W) tensor, got {tuple(ring.shape)}')
+    S, B, C, H, W = ring.shape
+    if not 0 <= int(head) < S:
+        raise ValueError(f'head must be in [0, {S}), got {head}')
+    want = dict(valid=(B,), sensor2ego0=(S, B, 4, 4), ego2global0=(S, B, 4, 4), bda=(S, B, 3, 3))
+    got = dict(valid=valid, sensor2ego0=sensor2ego0, ego2global0=ego2global0, bda=bda)
+    for name, shape in want.items():
+        if tuple(got[name].shape) != shape:
+            raise ValueError(f'{name} must be {shape}, got {tuple(got[name].shape)}')
+        if got[name].device != ring.device:
+            raise ValueError(f'{name} is on {got[name].device}, the ring on {ring.device}')
+    if valid.dtype.is_floating_point or valid.dtype == torch.bool:
+        raise ValueError(f'valid must be an integer tensor, got {valid.dtype}')
+    if out is not None and not (tuple(out.shape) == (B, S * C, H, W) and out.dtype == ring.dtype
+                                and out.device == ring.device and out.stride()[1:] == (H * W, W, 1)
+                                and (B == 1 or out.stride(0) >= S * C * H * W)):
+        raise ValueError(f'out must be a {ring.dtype} (B, S * C, H, W) = ({B}, {S * C}, {H}, {W}) view with contiguous '
+                         '(S * C, H, W) blocks on the device of the ring')
+    return S, B, C, H, W
+
+
+def stream_align_torch(ring, head, valid, sensor2ego0, ego2global0, bda, grid_interval, grid_lower_bound, align=True,
+                       out=None):
+    """The streaming step's aligned concatenation in torch, on any device and for any floating dtype; forward only (it
+    runs under ``no_grad``), no host read.
+
+    ``ring`` (S, B, C, H, W) holds the last S = K + 1 key-frame BEV maps, slot ``head`` the current one; ``valid`` (B)
+    integers, the number of real history frames of each sample; ``sensor2ego0`` / ``ego2global0`` (S, B, 4, 4) and
+    ``bda`` (S, B, 3, 3) the raw poses of camera 0 and the BEV augmentation at each slot's time.
+
+    Selection rule: channel group g = 0 .. K - 1 of the result holds age a = K - g, oldest first, group K the key frame.
+    For sample b the effective age is ``e = min(a, valid[b])`` and the source slot ``(head - e) mod S``; ``e == 0`` or
+    ``align`` false copies the source plane, otherwise it is warped (``shift_feature_torch``) under
+    ``feature_transform`` for ``curr = inv(E_h) E_h S_h`` and ``adj = inv(E_h) E_s S_s`` (h the head slot, s the source
+    slot) with ``bda[h]`` and ``bda_adj = bda[s]``, evaluated in float64.
+
+    Returns ``(out (B, S * C, H, W), tf (K, B, 3, 3) float32)``: ``tf[g][b]`` is the transform group g of sample b was
+    warped with, the identity for a copied group.  ``out``: a view to write into (``shift_feature``'s)."""
+    S, B, C, H, W = _check_stream_operands(ring, head, valid, sensor2ego0, ego2global0, bda, out)
+    K, head, dev = S - 1, int(head), ring.device
+    with torch.no_grad():
+        rows = torch.arange(B, device=dev)
+        e2g, s2e = ego2global0.double(), sensor2ego0.double()
+        head2global = e2g[head]
+        rinv = _inverse3(head2global[:, :3, :3])
+        global2head = torch.zeros_like(head2global)
+        global2head[:, :3, :3], global2head[:, 3, 3] = rinv, 1.0
+        global2head[:, :3, 3] = -torch.einsum('nij,nj->ni', rinv, head2global[:, :3, 3])
+        curr = global2head @ (head2global @ s2e[head])
+        groups, tfs = [], []
+        eye = torch.eye(3, dtype=torch.float64, device=dev).expand(B, 3, 3)
+        for g in range(K):
+            e = torch.clamp(valid.long(), min=0, max=K - g)
+            slot = torch.remainder(head - e, S)
+            src = ring[slot, rows]
+            if not align:
+                groups.append(src)
+                tfs.append(eye)
+                continue
+            adj = global2head @ (e2g[slot, rows] @ s2e[slot, rows])
+            tf = feature_transform([curr[:, None], adj[:, None]], bda[head], grid_interval, grid_lower_bound,
+                                   bda_adj=bda[slot, rows])
+            copied = e == 0
+            groups.append(torch.where(copied.view(B, 1, 1, 1), src, shift_feature_torch(src, tf)))
+            tfs.append(torch.where(copied.view(B, 1, 1), eye, tf))
+        groups.append(ring[head])
+        tf_out = torch.stack(tfs).float() if K else torch.zeros(0, B, 3, 3, dtype=torch.float32, device=dev)
+        if out is None:
+            return torch.cat(groups, dim=1), tf_out
+        for g, x in enumerate(groups):
+            out[:, g * C:(g + 1) * C].copy_(x)
+        return out, tf_out
+
+
+def stream_align_fusable(ring, valid, sensor2ego0, ego2global0, bda, grid_interval, grid_lower_bound):
+    """The kernel takes these: a CUDA float32 contiguous ring, ``valid`` int32 and float32 contiguous poses on its device,
+    and grid constants on the host (a sequence or a CPU tensor: reading a device tensor would synchronise)."""
+    if not (ring.is_cuda and ring.dtype == torch.float32 and ring.is_contiguous() and ring.dim() == 5
+            and ring.numel() > 0):
+        return False
+    if not (valid.dtype == torch.int32 and valid.device == ring.device and valid.is_contiguous()):
+        return False
+    if any(isinstance(v, torch.Tensor) and v.device.type != 'cpu' for v in (grid_interval, grid_lower_bound)):
+        return False
+    return all(t.dtype == torch.float32 and t.device == ring.device and t.is_contiguous()
+               for t in (sensor2ego0, ego2global0, bda))
+
+
+def stream_align(ring, head, valid, sensor2ego0, ego2global0, bda, grid_interval, grid_lower_bound, align=True,
+                 out=None, fused=None):
+    """``stream_align_torch`` with the usual dispatch: operands that ``stream_align_fusable`` accepts take ONE launch of
+    ``ocrf_bev_stream_align`` (``csrc/bev_stream_align.hip``), which evaluates the transforms itself and writes every
+    group of the concatenation; everything else, the CPU included, the torch formulation.  ``fused`` (default
+    ``FUSED_ALIGN_DEFAULT``) False forces the latter.  Forward only: nothing here records a gradient.
+
+    A warped group of the kernel is bit-equal to ``shift_feature(ring[slot], tf[g], out=...)``, the existing kernel fed
+    the returned ``tf``; ``tf`` agrees with the torch formulation's within one float32 ulp (both round a float64 value
+    once)."""
+    if not ((FUSED_ALIGN_DEFAULT if fused is None else fused)
+            and stream_align_fusable(ring, valid, sensor2ego0, ego2global0, bda, grid_interval, grid_lower_bound)):
+        return stream_align_torch(ring, head, valid, sensor2ego0, ego2global0, bda, grid_interval, grid_lower_bound,
+                                  align=align, out=out)
+    S, B, C, H, W = _check_stream_operands(ring, head, valid, sensor2ego0, ego2global0, bda, out)
+    if out is None:
+        out = torch.empty(B, S * C, H, W, dtype=torch.float32, device=ring.device)
+    tf_out = torch.empty(S - 1, B, 3, 3, dtype=torch.float32, device=ring.device)
+    ix, iy = _pair(grid_interval, ring)
+    lx, ly = _pair(grid_lower_bound, ring)
+    _lib.launch('ocrf_bev_stream_align', ring.device, S, B, C, H, W, ring, int(head), valid, sensor2ego0, ego2global0,
+                bda, ix, iy, lx, ly, 1 if align else 0, out, _batch_stride(out), tf_out)
+    return out, tf_out
 
 
 # ------------------------------------------------------------------------------------------------ drop-in methods
