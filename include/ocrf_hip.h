@@ -651,6 +651,22 @@ int ocrf_center_decode(int B, int T, const int *ncls, int H, int W, const float 
                        float score_threshold, const float *post_center_limit_range, const int *nms_circle,
                        const double *nms_threshold, const float *rescale_factor, float *boxes, float *scores,
                        int *labels, int *counts, void *workspace, size_t workspace_bytes, ocrf_stream_t stream);
+/*
+ * ocrf_center_decode_bf16: the same call with the 6T head tensors read as bfloat16 in place (a head under bf16 autocast):
+ *   heads[6T] is a host table of device bf16 pointers (passed as unsigned short), same shapes.  Only the select kernel
+ *   reads the heads; it widens every load to f32 (exact) and is the f32 code from there on, so boxes, scores, labels
+ *   and counts are bit-equal to ocrf_center_decode on the widened heads.  bf16 scores tie often: the order (score
+ *   descending, then (class, cell) index ascending, the first `remain` equals in index order) decides ties as it does
+ *   in f32.  Same workspace, same workspace query, four launches.
+ */
+int ocrf_center_decode_bf16(int B, int T, const int *ncls, int H, int W, const unsigned short *const *heads,
+                            int with_velocity, int norm_bbox, int max_num, int pre_max_size, int post_max_size,
+                            float out_size_factor, const float *voxel_size, const float *pc_range,
+                            int has_coder_score_threshold, float coder_score_threshold, const float *post_center_range,
+                            int has_score_threshold, float score_threshold, const float *post_center_limit_range,
+                            const int *nms_circle, const double *nms_threshold, const float *rescale_factor,
+                            float *boxes, float *scores, int *labels, int *counts, void *workspace,
+                            size_t workspace_bytes, ocrf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Upsample + concatenate of the BEV encoder's neck (csrc/upsample_cat.hip): FPN_LSS.forward's
@@ -779,6 +795,23 @@ int ocrf_bev_stream_align(int S, int B, int C, int h, int w, const float *ring, 
                           const float *sensor2ego0, const float *ego2global0, const float *bda, double interval_x,
                           double interval_y, double lower_x, double lower_y, int align, float *out,
                           long long out_batch_stride, float *tf_out, ocrf_stream_t stream);
+/*
+ * The same launch on a bfloat16 ring (a streaming step under bf16 autocast): ring and out are bf16, passed as unsigned
+ * short; the poses, valid and tf_out stay as above, out_batch_stride is counted in elements.  The kernel is the f32
+ * kernel's body instantiated for the 2-byte element: units, selection rule, the f64 transform by one lane and the tf_out
+ * report are the same code.  Contracts:
+ *   a warped group is bit for bit what ocrf_bev_align_forward_bf16 writes for the same plane and the returned tf: the
+ *     f32 value on the widened taps, rounded ONCE to bf16, to nearest even;
+ *   a copied group is a bit copy of its source plane (no widening, no rounding: a NaN keeps its payload);
+ *   tf_out is bit-equal to what ocrf_bev_stream_align reports for the same poses.
+ * 16-byte stores (8 elements) when h * w and out_batch_stride are multiples of 8 and out is 16-byte aligned, 2-byte
+ * stores otherwise; a copied group of the wide form loads 16 bytes when the ring is 16-byte aligned too, 2 bytes at a
+ * time otherwise.  Limits: those above, the 2 GiB counted in bytes of the 2-byte element.
+ */
+int ocrf_bev_stream_align_bf16(int S, int B, int C, int h, int w, const unsigned short *ring, int head,
+                               const int *valid, const float *sensor2ego0, const float *ego2global0, const float *bda,
+                               double interval_x, double interval_y, double lower_x, double lower_y, int align,
+                               unsigned short *out, long long out_batch_stride, float *tf_out, ocrf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Frame poses of the 4D detectors (csrc/frame_poses.hip): the pose algebra of BEVDet4D.prepare_inputs
@@ -1594,7 +1627,9 @@ enum {
   OCRF_K_HOA1_TOKEN_GRAD = 152,       /* hoa1_token_grad_kernel */
   OCRF_K_HOA1_PIXEL_GRAD = 153,       /* hoa1_pixel_grad_kernel */
   OCRF_K_HOA1_WEIGHT_SUM = 154,       /* hoa1_weight_sum_kernel */
-  OCRF_K_BEV_STREAM_ALIGN = 155       /* bev_stream_align_kernel<V> */
+  OCRF_K_BEV_STREAM_ALIGN = 155,      /* bev_stream_align_kernel<float, V> */
+  OCRF_K_BEV_STREAM_ALIGN_BF16 = 156, /* bev_stream_align_kernel<unsigned short, V> */
+  OCRF_K_CD_SELECT_BF16 = 157         /* cd_select_kernel<unsigned short> */
 };
 const char *ocrf_kernel_name(int kernel_id);           /* symbol as rocprofv3 prints it */
 /* Diagnostic: a one-thread kernel that stores the device's constant-rate clock (wall_clock64, 100 MHz)

@@ -14,7 +14,9 @@ post_max_size:
   for every (sample, task) at once and reads nothing back.
 
 bfloat16 head outputs (bf16 autocast) are cast to float32 first (``bf16_as_float32``), so they decode in float32 on
-either path; float16 ones take the torch formulation as they are.
+either path; float16 ones take the torch formulation as they are.  Opt-in (``CenterHead.fused_decode_bf16``) head
+outputs that are ALL CUDA bfloat16 skip the casts: ``ocrf_center_decode_bf16`` reads them in place, widens each load
+exactly and returns the bits the float32 call returns on ``.float()`` of the same heads.
 
 Rules both keep:
 
@@ -394,13 +396,20 @@ def bf16_as_float32(preds_dicts):
             for p in preds_dicts]
 
 
-def fused_ok(preds_dicts):
+def fused_ok(preds_dicts, dtype=torch.float32):
+    """The kernel takes these heads: all on the GPU and all of ``dtype`` (float32, or bfloat16 for the ``_bf16`` entry
+    point; a mixed list is refused), every task with a ``reg`` head."""
     ts = [v for p in preds_dicts for k, v in p[0].items() if k in HEAD_KEYS]
-    return all(t.is_cuda and t.dtype == torch.float32 for t in ts) and all('reg' in p[0] for p in preds_dicts)
+    return all(t.is_cuda and t.dtype == dtype for t in ts) and all('reg' in p[0] for p in preds_dicts)
+
+
+_ENTRY = {torch.float32: 'ocrf_center_decode', torch.bfloat16: 'ocrf_center_decode_bf16'}
 
 
 def decode_fused(preds_dicts, cfg, norm_bbox=True):
-    """``decode_torch`` by ``ocrf_center_decode``."""
+    """``decode_torch`` by ``ocrf_center_decode``, or by ``ocrf_center_decode_bf16`` when every head is bfloat16 (read in
+    place; the float32 results are bit-equal to those on ``.float()`` of the heads).  A list of mixed dtypes is
+    refused."""
     T = len(preds_dicts)
     p0 = preds_dicts[0][0]
     B, _, H, W = p0['heatmap'].shape
@@ -419,17 +428,21 @@ def decode_fused(preds_dicts, cfg, norm_bbox=True):
                 raise ValueError(f'task {t}: {k} must be ({B}, {c}, {H}, {W}), got {tuple(d[k].shape)}')
         heads.append([d[k].detach().contiguous() for k in keys] + ([] if with_vel else [None]))
     flat = [h for hs in heads for h in hs]
+    dtype = p0['heatmap'].dtype
+    if dtype not in _ENTRY or any(h is not None and h.dtype != dtype for h in flat):
+        raise _lib.OcrfHipError('decode_fused takes head outputs that are all float32 or all bfloat16, got '
+                                f'{sorted({str(h.dtype) for h in flat if h is not None})}')
     C = 9 if with_vel else 7
     M = T * cfg.post_max
-    boxes = torch.empty(B, M, C, device=dev)
-    scores = torch.empty(B, M, device=dev)
+    boxes = torch.empty(B, M, C, dtype=torch.float32, device=dev)
+    scores = torch.empty(B, M, dtype=torch.float32, device=dev)
     labels = torch.empty(B, M, dtype=torch.int32, device=dev)
     counts = torch.empty(B, dtype=torch.int32, device=dev)
     ws = _lib.workspace.get(dev, _lib.lib().ocrf_center_decode_workspace_bytes(B, T, cfg.K, cfg.post_max), 'center_decode')
     coder = cfg.coder
     f2 = lambda v: (ctypes.c_float * len(v))(*[float(x) for x in v])  # noqa: E731
     ptrs = (ctypes.c_void_p * len(flat))(*[t.data_ptr() if t is not None else 0 for t in flat])
-    _lib.launch('ocrf_center_decode', dev,
+    _lib.launch(_ENTRY[dtype], dev,
                 B, T, (ctypes.c_int * T)(*cfg.ncls), H, W, ptrs, int(with_vel), int(norm_bbox), cfg.K, cfg.pre_max,
                 cfg.post_max, float(coder.out_size_factor), f2(coder.voxel_size[:2]), f2(coder.pc_range[:2]),
                 int(cfg.coder_thr is not None), cfg.coder_thr or 0.0, f2(cfg.center) if cfg.center else None,

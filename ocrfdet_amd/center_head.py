@@ -443,7 +443,13 @@ def reduce_counts(counts):
 # --------------------------------------------------------------------------------------------- head
 class CenterHead(nn.Module):
     """The reference's ``CenterHead`` (same arguments, attributes and state_dict).  ``fused_loss`` (default True)
-    selects the HIP targets and losses when the inputs are float32 CUDA tensors."""
+    selects the HIP targets and losses when the inputs are float32 CUDA tensors.
+
+    ``fused_decode_bf16`` (class attribute, default False): head outputs that are all CUDA bfloat16 (a head under bf16
+    autocast) are decoded in place by ``ocrf_center_decode_bf16`` instead of being cast to float32 first, one cast
+    launch per head tensor; the results are the same bits."""
+
+    fused_decode_bf16 = False
 
     def __init__(self, in_channels=[128], tasks=None, train_cfg=None, test_cfg=None, bbox_coder=None,
                  common_heads=dict(), loss_cls=dict(type='GaussianFocalLoss', reduction='mean'),
@@ -600,6 +606,8 @@ class CenterHead(nn.Module):
         bottom-centre z, scores (B, M) f32, labels (B, M) int32 and counts (B,) int32, M = T * post_max_size; rows past
         a sample's count are zero."""
         cfg = self._decode_cfg()
+        if self.fused_decode and self.fused_decode_bf16 and cd.fused_ok(preds_dicts, torch.bfloat16):
+            return cd.decode_fused(preds_dicts, cfg, self.norm_bbox)        # read in place: no casts
         preds_dicts = cd.bf16_as_float32(preds_dicts)
         if self.fused_decode and cd.fused_ok(preds_dicts):
             return cd.decode_fused(preds_dicts, cfg, self.norm_bbox)

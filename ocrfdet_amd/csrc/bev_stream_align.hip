@@ -22,6 +22,13 @@
 // Units are the forward kernel's: (sample, group, block of kChannels channels, chunk of the plane), plane_walk.h groups,
 // 16-byte stores when the plane, the stride and the pointer allow it.  Every destination element is written once; no
 // atomics, no workspace, no host read; reruns are bit-identical.
+//
+// bfloat16 (ocrf_bev_stream_align_bf16: the ring of a streaming step under bf16 autocast).  The kernel is a template on
+// the element type and the bf16 form is the same body: units, selection, slot_transform and the tf_out report do not
+// depend on the element, the taps are 2-byte loads widened exactly (sample_value<T>), the value is the float32
+// expression and store_group rounds it once to nearest even: bit for bit what bev_align_kernel<unsigned short, V> writes
+// for the same plane and tf.  A copied group moves the bits (no widening, no rounding).  Strides are counted in
+// elements; a 16-byte store is V = 8 pixels, the narrow form a 2-byte store.
 #include <hip/hip_runtime.h>
 
 #include "bev_align_taps.h"
@@ -39,17 +46,18 @@ using namespace pose;
 constexpr int kChannels = 2;                       // channels per unit, as in bev_align.hip
 constexpr long long kMaxSlots = 1 << 24;           // S * B: the pose operands (16 floats each) far below 2 GiB
 
+template <typename T>
 struct Args {
   int S, B, C, h, w, head, align;
   int cblocks, chunks, units;
   int wide_source;                                 // the ring is 16-byte aligned: a copied group may be one 16-byte load
-  const float* ring;
+  const T* ring;
   const int* valid;
   const float* sensor2ego0;
   const float* ego2global0;
   const float* bda;
   double ix, iy, lx, ly;
-  float* out;
+  T* out;
   long long out_batch_stride;
   float* tf_out;
 };
@@ -68,7 +76,8 @@ __device__ __forceinline__ void augmented(const float* __restrict__ a, const Mat
 
 // temporal.feature_transform from the raw poses of head slot `hs` and source slot `ss` (indices of (slot, sample)
 // matrices): rows 0 and 1 of tf, rounded once to float32
-__device__ __forceinline__ void slot_transform(const Args& a, size_t hs, size_t ss, float (&tf)[6]) {
+template <typename T>
+__device__ __forceinline__ void slot_transform(const Args<T>& a, size_t hs, size_t ss, float (&tf)[6]) {
   const Mat4 head2global = load4(a.ego2global0 + hs * 16);
   const Mat4 global2head = affine_inverse(head2global);
   const Mat4 curr = mul4(global2head, mul4(head2global, load4(a.sensor2ego0 + hs * 16)));
@@ -105,21 +114,42 @@ __device__ __forceinline__ void slot_transform(const Args& a, size_t hs, size_t 
   tf[5] = (float)((rm[1][0] * a.lx + rm[1][1] * a.ly + tm[1] - a.ly) / a.iy);
 }
 
+// One group of a copied plane, bits unchanged: one 16-byte load when the source allows it (`wide`), else element loads;
+// the store is the group's (16 bytes for V > 1)
 template <int V>
-__device__ __forceinline__ void load_group(const float* __restrict__ p, bool wide, float (&v)[V]) {
+__device__ __forceinline__ void copy_group(float* __restrict__ d, const float* __restrict__ p, bool wide) {
   if constexpr (V == 4) {
     if (wide) {
-      const float4 q = *reinterpret_cast<const float4*>(p);
-      v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+      *reinterpret_cast<float4*>(d) = *reinterpret_cast<const float4*>(p);
       return;
     }
   }
+  float v[V];
 #pragma unroll
   for (int k = 0; k < V; ++k) v[k] = p[k];
+  store_group<V>(d, v);
+}
+template <int V>
+__device__ __forceinline__ void copy_group(bf16_t* __restrict__ d, const bf16_t* __restrict__ p, bool wide) {
+  if constexpr (V == 8) {
+    uint4 q;
+    if (wide) {
+      q = *reinterpret_cast<const uint4*>(p);
+    } else {
+      q.x = (unsigned)p[0] | ((unsigned)p[1] << 16);
+      q.y = (unsigned)p[2] | ((unsigned)p[3] << 16);
+      q.z = (unsigned)p[4] | ((unsigned)p[5] << 16);
+      q.w = (unsigned)p[6] | ((unsigned)p[7] << 16);
+    }
+    *reinterpret_cast<uint4*>(d) = q;
+  } else {
+    static_assert(V == 1, "a group of bf16 is 8 or 1");
+    *d = *p;
+  }
 }
 
-template <int V>
-__global__ void __launch_bounds__(kThreads) bev_stream_align_kernel(Args a) {
+template <typename T, int V>
+__global__ void __launch_bounds__(kThreads) bev_stream_align_kernel(Args<T> a) {
   __shared__ float tf_shared[6];
   const int P = a.h * a.w, K = a.S - 1;
   const Walk<V> walk(a.w);
@@ -150,17 +180,13 @@ __global__ void __launch_bounds__(kThreads) bev_stream_align_kernel(Args a) {
       }
     }
     __syncthreads();
-    const float* s = a.ring + (((size_t)slot * a.B + b) * a.C + c0) * P;
-    float* o = a.out + (size_t)b * a.out_batch_stride + ((size_t)g * a.C + c0) * P;
+    const T* s = a.ring + (((size_t)slot * a.B + b) * a.C + c0) * P;
+    T* o = a.out + (size_t)b * a.out_batch_stride + ((size_t)g * a.C + c0) * P;
     if (!warp) {
       walk.groups(walk.first(chunk), P, [&](int idx, int, int) {
 #pragma unroll
         for (int ch = 0; ch < kChannels; ++ch) {
-          if (ch < nc) {
-            float v[V];
-            load_group<V>(s + ch * P + idx, a.wide_source != 0, v);
-            store_group<V>(o + ch * P + idx, v);
-          }
+          if (ch < nc) copy_group<V>(o + ch * P + idx, s + ch * P + idx, a.wide_source != 0);
         }
       });
       continue;
@@ -181,7 +207,7 @@ __global__ void __launch_bounds__(kThreads) bev_stream_align_kernel(Args a) {
 #pragma unroll
       for (int ch = 0; ch < kChannels; ++ch) {
         if (ch < nc) {
-          const float* sc = s + ch * P;
+          const T* sc = s + ch * P;
           float v[V];
 #pragma unroll
           for (int k = 0; k < V; ++k) v[k] = sample_value(sc, p[k]);
@@ -192,16 +218,15 @@ __global__ void __launch_bounds__(kThreads) bev_stream_align_kernel(Args a) {
   }
 }
 
-}  // namespace
-
-extern "C" int ocrf_bev_stream_align(int S, int B, int C, int h, int w, const float* ring, int head, const int* valid,
-                                     const float* sensor2ego0, const float* ego2global0, const float* bda,
-                                     double interval_x, double interval_y, double lower_x, double lower_y, int align,
-                                     float* out, long long out_batch_stride, float* tf_out, ocrf_stream_t stream) {
+template <typename T>
+int stream_align(int kernel_id, int S, int B, int C, int h, int w, const T* ring, int head, const int* valid,
+                 const float* sensor2ego0, const float* ego2global0, const float* bda, double interval_x,
+                 double interval_y, double lower_x, double lower_y, int align, T* out, long long out_batch_stride,
+                 float* tf_out, ocrf_stream_t stream) {
   if (S <= 0 || B <= 0 || C <= 0 || h <= 0 || w <= 0 || head < 0 || head >= S) return (int)hipErrorInvalidValue;
   if (!ring || !valid || !sensor2ego0 || !ego2global0 || !bda || !out) return (int)hipErrorInvalidValue;
   if (!(interval_x > 0.0) || !(interval_y > 0.0)) return (int)hipErrorInvalidValue;          // NaN too
-  const long long limit = kTwoGiB / (long long)sizeof(float);
+  const long long limit = kTwoGiB / (long long)sizeof(T);            // elements of the operand's type
   const long long slots = (long long)S * B, P = (long long)h * w;                            // each below 2^62
   if (slots >= kMaxSlots || P >= limit) return (int)hipErrorInvalidValue;
   const long long planes = slots * C;                                                        // below 2^55
@@ -211,22 +236,43 @@ extern "C" int ocrf_bev_stream_align(int S, int B, int C, int h, int w, const fl
     return (int)hipErrorInvalidValue;
   }
   const int cblocks = (C + kChannels - 1) / kChannels;
-  const bool vec = P % 4 == 0 && out_batch_stride % 4 == 0 && aligned16(out);
-  const Units n = units_of(slots * cblocks, P, vec ? 4 : 1);
+  constexpr int W = kWide<T>;                                    // elements of a 16-byte group: 4 floats, 8 bf16
+  const bool vec = P % W == 0 && out_batch_stride % W == 0 && aligned16(out);
+  const Units n = units_of(slots * cblocks, P, vec ? W : 1);
   if (n.units >= kTwoGiB) return (int)hipErrorInvalidValue;
-  Args a;
+  Args<T> a;
   a.S = S, a.B = B, a.C = C, a.h = h, a.w = w, a.head = head, a.align = align;
   a.cblocks = cblocks, a.chunks = n.chunks, a.units = (int)n.units;
-  a.wide_source = aligned16(ring) ? 1 : 0;                       // with P % 4 == 0 every plane of the ring then is
+  a.wide_source = aligned16(ring) ? 1 : 0;                       // with P % W == 0 every plane of the ring then is
   a.ring = ring, a.valid = valid, a.sensor2ego0 = sensor2ego0, a.ego2global0 = ego2global0, a.bda = bda;
   a.ix = interval_x, a.iy = interval_y, a.lx = lower_x, a.ly = lower_y;
   a.out = out, a.out_batch_stride = out_batch_stride, a.tf_out = tf_out;
   if (vec) {
-    ocrf::launch(OCRF_K_BEV_STREAM_ALIGN, bev_stream_align_kernel<4>, dim3(n.grid), dim3(kThreads), 0,
-                 (hipStream_t)stream, a);
+    ocrf::launch(kernel_id, bev_stream_align_kernel<T, W>, dim3(n.grid), dim3(kThreads), 0, (hipStream_t)stream, a);
   } else {
-    ocrf::launch(OCRF_K_BEV_STREAM_ALIGN, bev_stream_align_kernel<1>, dim3(n.grid), dim3(kThreads), 0,
-                 (hipStream_t)stream, a);
+    ocrf::launch(kernel_id, bev_stream_align_kernel<T, 1>, dim3(n.grid), dim3(kThreads), 0, (hipStream_t)stream, a);
   }
   return (int)hipGetLastError();
 }
+
+}  // namespace
+
+extern "C" {
+
+int ocrf_bev_stream_align(int S, int B, int C, int h, int w, const float* ring, int head, const int* valid,
+                          const float* sensor2ego0, const float* ego2global0, const float* bda, double interval_x,
+                          double interval_y, double lower_x, double lower_y, int align, float* out,
+                          long long out_batch_stride, float* tf_out, ocrf_stream_t stream) {
+  return stream_align(OCRF_K_BEV_STREAM_ALIGN, S, B, C, h, w, ring, head, valid, sensor2ego0, ego2global0, bda,
+                      interval_x, interval_y, lower_x, lower_y, align, out, out_batch_stride, tf_out, stream);
+}
+
+int ocrf_bev_stream_align_bf16(int S, int B, int C, int h, int w, const unsigned short* ring, int head,
+                               const int* valid, const float* sensor2ego0, const float* ego2global0, const float* bda,
+                               double interval_x, double interval_y, double lower_x, double lower_y, int align,
+                               unsigned short* out, long long out_batch_stride, float* tf_out, ocrf_stream_t stream) {
+  return stream_align(OCRF_K_BEV_STREAM_ALIGN_BF16, S, B, C, h, w, ring, head, valid, sensor2ego0, ego2global0, bda,
+                      interval_x, interval_y, lower_x, lower_y, align, out, out_batch_stride, tf_out, stream);
+}
+
+}  // extern "C"

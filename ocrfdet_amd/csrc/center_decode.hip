@@ -16,14 +16,26 @@
 //           post_max_size kept boxes;
 //   write   one block per sample: the tasks' kept boxes in task order, the rotate tasks' post_center_limit_range
 //           filter, z -= dz / 2, the class offsets; rows past the count are zeroed.
+//
+// bfloat16 heads (ocrf_center_decode_bf16: a head under bf16 autocast, read in place).  Only the select kernel reads the
+// heads: the heatmap in the four radix passes and the compaction, and reg, height, dim, rot, vel at the K selected cells.
+// It is a template on the element type; the bf16 form widens each load to float32 (a shift: exact) and everything after
+// the load is the float32 code, so the four results are bit-equal to the float32 call on the widened heads.  bf16
+// scores tie often.  Nothing is needed for that: the order (score descending, then (class, cell) index ascending, the
+// first `remain` keys equal to the K-th in index order) already decides every tie, and it does not depend on how many
+// keys are equal.  mask, scan and write read the workspace only and are shared.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
 #include "launch.h"
 #include "ocrf_hip.h"
+#include "plane_walk.h"
 
 namespace {
+
+using plane::bf16_t;
+using plane::load_f32;
 
 constexpr int kSelThreads = 1024;
 constexpr int kMaxK = OCRF_CD_MAX_NUM;
@@ -39,7 +51,7 @@ struct DecodeArgs {
   int ncls[OCRF_CD_MAX_TASKS], cls_off[OCRF_CD_MAX_TASKS], circle[OCRF_CD_MAX_TASKS];
   double thr[OCRF_CD_MAX_TASKS];
   float factor[OCRF_CD_MAX_TASKS][OCRF_CD_MAX_CLASSES];
-  const float* heads[OCRF_CD_MAX_TASKS][6];   // heatmap logits, reg, height, dim, rot, vel
+  const void* heads[OCRF_CD_MAX_TASKS][6];    // heatmap logits, reg, height, dim, rot, vel: float or bf16_t (select)
   float* cand_row;                            // (B*T, K, 9): the decoded row with its final dims
   float* cand_bev;                            // (B*T, K, 5): the NMS box after the round trip
   float* cand_score;
@@ -143,11 +155,13 @@ __device__ double iou_rotated(const float* a, const float* b) {
 }
 
 // --------------------------------------------------------------------------------------------- select + decode
+// T: float or bf16_t, the element of the heads; every head value enters through load_f32
+template <typename T>
 __global__ void __launch_bounds__(kSelThreads) cd_select_kernel(DecodeArgs a) {
   const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const int bt = b * a.T + t;
   const int HW = a.H * a.W, ncls = a.ncls[t], N = ncls * HW, K = a.K;
-  const float* hm = a.heads[t][0] + (size_t)b * N;
+  const T* hm = static_cast<const T*>(a.heads[t][0]) + (size_t)b * N;
   __shared__ unsigned hist[256];
   __shared__ unsigned s_prefix, s_remain;
   __shared__ int s_wave[16];
@@ -159,7 +173,7 @@ __global__ void __launch_bounds__(kSelThreads) cd_select_kernel(DecodeArgs a) {
     if (tid < 256) hist[tid] = 0;
     __syncthreads();
     for (int i = tid; i < N; i += kSelThreads) {
-      const unsigned key = __float_as_uint(sigmoid_key(hm[i]));
+      const unsigned key = __float_as_uint(sigmoid_key(load_f32(hm + i)));
       if ((key & pmask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
     }
     __syncthreads();
@@ -192,7 +206,7 @@ __global__ void __launch_bounds__(kSelThreads) cd_select_kernel(DecodeArgs a) {
   int eq_base = 0;
   for (int base = 0; base < N; base += kSelThreads) {
     const int i = base + tid;
-    const unsigned key = i < N ? __float_as_uint(sigmoid_key(hm[i])) : 0u;
+    const unsigned key = i < N ? __float_as_uint(sigmoid_key(load_f32(hm + i))) : 0u;
     const unsigned long long c = ((unsigned long long)key << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)i);
     if (i < N && key > v) comp[atomicAdd(&s_gt, 1u)] = c;
     int total;
@@ -227,12 +241,12 @@ __global__ void __launch_bounds__(kSelThreads) cd_select_kernel(DecodeArgs a) {
     score = __uint_as_float((unsigned)(c >> 32));
     cls = (int)(idx / (unsigned)HW);
     const int cell = (int)(idx % (unsigned)HW);
-    const float* reg = a.heads[t][1] + (size_t)b * 2 * HW;
-    const float* hei = a.heads[t][2] + (size_t)b * HW;
-    const float* dim = a.heads[t][3] + (size_t)b * 3 * HW;
-    const float* rot = a.heads[t][4] + (size_t)b * 2 * HW;
-    float xs = (float)(cell % a.W) + reg[cell];
-    float ys = (float)(cell / a.W) + reg[HW + cell];
+    const T* reg = static_cast<const T*>(a.heads[t][1]) + (size_t)b * 2 * HW;
+    const T* hei = static_cast<const T*>(a.heads[t][2]) + (size_t)b * HW;
+    const T* dim = static_cast<const T*>(a.heads[t][3]) + (size_t)b * 3 * HW;
+    const T* rot = static_cast<const T*>(a.heads[t][4]) + (size_t)b * 2 * HW;
+    float xs = (float)(cell % a.W) + load_f32(reg + cell);
+    float ys = (float)(cell / a.W) + load_f32(reg + HW + cell);
     xs = xs * a.osf;
     xs = xs * a.vs0;
     xs = xs + a.pc0;
@@ -241,13 +255,16 @@ __global__ void __launch_bounds__(kSelThreads) cd_select_kernel(DecodeArgs a) {
     ys = ys + a.pc1;
     row[0] = xs;
     row[1] = ys;
-    row[2] = hei[cell];
-    for (int k = 0; k < 3; ++k) row[3 + k] = a.norm_bbox ? expf(dim[k * HW + cell]) : dim[k * HW + cell];
-    row[6] = atan2f(rot[cell], rot[HW + cell]);
+    row[2] = load_f32(hei + cell);
+    for (int k = 0; k < 3; ++k) {
+      const float d = load_f32(dim + k * HW + cell);
+      row[3 + k] = a.norm_bbox ? expf(d) : d;
+    }
+    row[6] = atan2f(load_f32(rot + cell), load_f32(rot + HW + cell));
     if (a.with_vel) {
-      const float* vel = a.heads[t][5] + (size_t)b * 2 * HW;
-      row[7] = vel[cell];
-      row[8] = vel[HW + cell];
+      const T* vel = static_cast<const T*>(a.heads[t][5]) + (size_t)b * 2 * HW;
+      row[7] = load_f32(vel + cell);
+      row[8] = load_f32(vel + HW + cell);
     } else {
       row[7] = row[8] = 0.0f;
     }
@@ -420,27 +437,20 @@ Layout layout(int B, int T, int K, int post_max) {
   return l;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t ocrf_center_decode_workspace_bytes(int B, int T, int max_num, int post_max_size) {
-  if (B <= 0 || T <= 0 || max_num <= 0) return 0;
-  return layout(B, T, max_num, post_max_size).total;
-}
-
-int ocrf_center_decode(int B, int T, const int* ncls, int H, int W, const float* const* heads, int with_velocity,
-                       int norm_bbox, int max_num, int pre_max_size, int post_max_size, float out_size_factor,
-                       const float* voxel_size, const float* pc_range, int has_coder_score_threshold,
-                       float coder_score_threshold, const float* post_center_range, int has_score_threshold,
-                       float score_threshold, const float* post_center_limit_range, const int* nms_circle,
-                       const double* nms_threshold, const float* rescale_factor, float* boxes, float* scores,
-                       int* labels, int* counts, void* workspace, size_t workspace_bytes, ocrf_stream_t stream) {
+// E: the element of the heads; select_id: the kernel id its select launch reports under
+template <typename E>
+int center_decode(int select_id, int B, int T, const int* ncls, int H, int W, const E* const* heads, int with_velocity,
+                  int norm_bbox, int max_num, int pre_max_size, int post_max_size, float out_size_factor,
+                  const float* voxel_size, const float* pc_range, int has_coder_score_threshold,
+                  float coder_score_threshold, const float* post_center_range, int has_score_threshold,
+                  float score_threshold, const float* post_center_limit_range, const int* nms_circle,
+                  const double* nms_threshold, const float* rescale_factor, float* boxes, float* scores, int* labels,
+                  int* counts, void* workspace, size_t workspace_bytes, ocrf_stream_t stream) {
   if (B <= 0 || T <= 0 || T > OCRF_CD_MAX_TASKS || H <= 0 || W <= 0 || max_num <= 0 || max_num > kMaxK ||
       max_num > H * W || pre_max_size <= 0 || post_max_size <= 0 || !heads || !ncls || !boxes || !scores ||
       !labels || !counts)
     return (int)hipErrorInvalidValue;
-  if (workspace_bytes < ocrf_center_decode_workspace_bytes(B, T, max_num, post_max_size) || !workspace)
+  if (workspace_bytes < layout(B, T, max_num, post_max_size).total || !workspace)
     return (int)hipErrorInvalidValue;
   DecodeArgs a{};
   a.B = B;
@@ -500,12 +510,50 @@ int ocrf_center_decode(int B, int T, const int* ncls, int H, int W, const float*
   a.labels = labels;
   a.counts = counts;
   hipStream_t s = (hipStream_t)stream;
-  ocrf::launch(OCRF_K_CD_SELECT, cd_select_kernel, dim3(T, B), dim3(kSelThreads), 0, s, a);
+  ocrf::launch(select_id, cd_select_kernel<E>, dim3(T, B), dim3(kSelThreads), 0, s, a);
   ocrf::launch(OCRF_K_CD_MASK, cd_mask_kernel, dim3(a.nw, a.nw, B * T), dim3(64), 0, s, a);
   const size_t lds = (size_t)std::min(max_num, kScanLdsBytes / (8 * a.nw)) * a.nw * 8;
   ocrf::launch(OCRF_K_CD_SCAN, cd_scan_kernel, dim3(B * T), dim3(64), lds, s, a);
   ocrf::launch(OCRF_K_CD_WRITE, cd_write_kernel, dim3(B), dim3(kWriteThreads), 0, s, a);
   return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t ocrf_center_decode_workspace_bytes(int B, int T, int max_num, int post_max_size) {
+  if (B <= 0 || T <= 0 || max_num <= 0) return 0;
+  return layout(B, T, max_num, post_max_size).total;
+}
+
+int ocrf_center_decode(int B, int T, const int* ncls, int H, int W, const float* const* heads, int with_velocity,
+                       int norm_bbox, int max_num, int pre_max_size, int post_max_size, float out_size_factor,
+                       const float* voxel_size, const float* pc_range, int has_coder_score_threshold,
+                       float coder_score_threshold, const float* post_center_range, int has_score_threshold,
+                       float score_threshold, const float* post_center_limit_range, const int* nms_circle,
+                       const double* nms_threshold, const float* rescale_factor, float* boxes, float* scores,
+                       int* labels, int* counts, void* workspace, size_t workspace_bytes, ocrf_stream_t stream) {
+  return center_decode(OCRF_K_CD_SELECT, B, T, ncls, H, W, heads, with_velocity, norm_bbox, max_num, pre_max_size,
+                       post_max_size, out_size_factor, voxel_size, pc_range, has_coder_score_threshold,
+                       coder_score_threshold, post_center_range, has_score_threshold, score_threshold,
+                       post_center_limit_range, nms_circle, nms_threshold, rescale_factor, boxes, scores, labels, counts,
+                       workspace, workspace_bytes, stream);
+}
+
+int ocrf_center_decode_bf16(int B, int T, const int* ncls, int H, int W, const unsigned short* const* heads,
+                            int with_velocity, int norm_bbox, int max_num, int pre_max_size, int post_max_size,
+                            float out_size_factor, const float* voxel_size, const float* pc_range,
+                            int has_coder_score_threshold, float coder_score_threshold, const float* post_center_range,
+                            int has_score_threshold, float score_threshold, const float* post_center_limit_range,
+                            const int* nms_circle, const double* nms_threshold, const float* rescale_factor,
+                            float* boxes, float* scores, int* labels, int* counts, void* workspace,
+                            size_t workspace_bytes, ocrf_stream_t stream) {
+  return center_decode(OCRF_K_CD_SELECT_BF16, B, T, ncls, H, W, heads, with_velocity, norm_bbox, max_num, pre_max_size,
+                       post_max_size, out_size_factor, voxel_size, pc_range, has_coder_score_threshold,
+                       coder_score_threshold, post_center_range, has_score_threshold, score_threshold,
+                       post_center_limit_range, nms_circle, nms_threshold, rescale_factor, boxes, scores, labels, counts,
+                       workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -204,6 +204,8 @@ const char* ocrf_kernel_name(int kernel_id) {
     case OCRF_K_HOA1_PIXEL_GRAD: return "hoa1_pixel_grad_kernel";
     case OCRF_K_HOA1_WEIGHT_SUM: return "hoa1_weight_sum_kernel";
     case OCRF_K_BEV_STREAM_ALIGN: return "bev_stream_align_kernel<*>";
+    case OCRF_K_BEV_STREAM_ALIGN_BF16: return "bev_stream_align_kernel<unsigned short, *>";
+    case OCRF_K_CD_SELECT_BF16: return "cd_select_kernel<unsigned short>";
     default: return "";
   }
 }

@@ -251,10 +251,25 @@ def stereo_pack_bf16(x):
     return out
 
 
+def _checked_packed(entry, name, like, BN, C, H, W):
+    """A ``cv_feat_packed`` entry for features ``like`` (BN, C, H, W): the layout ``stereo_pack_bf16`` writes."""
+    shape = (BN, packed_blocks(C), H, W, PACK)
+    if not (isinstance(entry, torch.Tensor) and tuple(entry.shape) == shape and entry.dtype == torch.bfloat16
+            and entry.is_contiguous() and entry.device == like.device):
+        got = (tuple(entry.shape), entry.dtype, entry.device) if isinstance(entry, torch.Tensor) else type(entry)
+        raise ValueError(f'cv_feat_packed[{name}] must be a contiguous bfloat16 {shape} tensor on {like.device} '
+                         f'(stereo_pack_bf16 of the feature), got {got}')
+    return entry.detach()
+
+
 def stereo_cost_volume_hip_bf16(metas, bias, raw=False):
     """``stereo_cost_volume_hip`` for bfloat16 features without the cast to float32: two ``ocrf_stereo_pack_bf16``
     launches and ``ocrf_stereo_cost_volume_bf16``.  The float32 result holds the bits ``stereo_cost_volume_hip`` gives on
-    ``.float()`` of the same features."""
+    ``.float()`` of the same features.
+
+    ``metas['cv_feat_packed'] = [prev_packed | None, curr_packed | None]`` (optional): features the caller has packed
+    already (``stereo_pack_bf16``; a streaming step keeps the previous frame's).  An entry that is given is not packed
+    again; one of another shape, dtype or device raises ``ValueError`` before anything is launched."""
     prev, curr, D, H, W = _split(metas)
     BN, C = curr.shape[:2]
     if C < GROUP or prev.shape[1] != C:
@@ -267,9 +282,14 @@ def stereo_cost_volume_hip_bf16(metas, bias, raw=False):
                          'block addressing)')
     if D * H * W >= 2 ** 31:
         raise ValueError(f'stereo cost volume: D * H * W = {D * H * W} must be below 2^31')
+    given = metas.get('cv_feat_packed') or (None, None)
+    if len(given) != 2:
+        raise ValueError(f'cv_feat_packed holds [prev_packed, curr_packed], got {len(given)} entries')
+    given = [None if e is None else _checked_packed(e, name, x, BN, C, H, W)
+             for e, name, x in zip(given, ('prev', 'curr'), (prev, curr))]
     _lib.require_cuda(prev, curr)
     dev = curr.device
-    prev, curr = stereo_pack_bf16(prev), stereo_pack_bf16(curr)
+    prev, curr = (stereo_pack_bf16(x) if e is None else e for e, x in zip(given, (prev, curr)))
     cal = [metas[k].detach().to(dev, torch.float32).reshape(BN, -1).contiguous()
            for k in ('k2s_sensor', 'intrins', 'post_rots', 'post_trans')]
     fr = metas['frustum'].detach().to(dev, torch.float32)

@@ -19,6 +19,8 @@ Out of scope: mmcv's ``Config`` and registries, ``DataContainer`` unwrapping, ``
 the reference; streaming inference has its own names, ``OcRFDet4D.stream_step`` / ``simple_test_stream``,
 ``ocrfdet_amd/streaming.py``).
 """
+import contextlib
+
 import torch
 from torch import nn
 
@@ -189,7 +191,8 @@ class OcRFDet4D(nn.Module):
 
     ``fused_poses`` (class attribute, default True): the frame poses and ``mlp_input`` of a forward come from one HIP
     launch when ``img_inputs`` is on the GPU; False takes ``frame_poses_torch``.  ``fused_align`` (default
-    ``temporal.FUSED_ALIGN_DEFAULT``) is ``align_and_cat``'s flag."""
+    ``temporal.FUSED_ALIGN_DEFAULT``) is ``align_and_cat``'s flag.  ``bf16_inference()`` is the one switch for bfloat16
+    inference: autocast plus the three bf16 opt-ins of the sub-modules, restored on exit."""
 
     fused_poses = True
     fused_align = None
@@ -260,16 +263,49 @@ class OcRFDet4D(nn.Module):
         return prepare_inputs(inputs, self.num_frame, self.temporal_frame, self.extra_ref_frames, stereo=stereo,
                               fused=self.fused_poses)
 
+    # ---------------------------------------------------------------- bfloat16 inference
+    @contextlib.contextmanager
+    def bf16_inference(self):
+        """bfloat16 inference on fused kernels from the images to the boxes: enters
+        ``torch.autocast('cuda', dtype=torch.bfloat16)`` and turns on, where the sub-modules exist, ``self.autocast_bf16``
+        (the BEV encoder stays bfloat16), ``img_view_transformer.depth_net.fused_cost_volume_bf16`` on that instance (the
+        stereo cost volume reads bfloat16 features) and ``pts_bbox_head.fused_decode_bf16`` (the decode reads the
+        bfloat16 head outputs in place).  All three are put back on exit, on an exception too: an instance attribute
+        to its previous value, one that was only the class default is removed again.  Usable around ``simple_test``
+        and the other test-time calls; ``stream_step(bf16=True)`` enters it itself."""
+        targets = [(self, 'autocast_bf16')]
+        depth_net = getattr(getattr(self, 'img_view_transformer', None), 'depth_net', None)
+        if depth_net is not None:
+            targets.append((depth_net, 'fused_cost_volume_bf16'))
+        if self.with_pts_bbox:
+            targets.append((self.pts_bbox_head, 'fused_decode_bf16'))
+        missing = object()
+        before = [vars(obj).get(name, missing) for obj, name in targets]
+        try:
+            for obj, name in targets:
+                setattr(obj, name, True)
+            with torch.autocast('cuda', dtype=torch.bfloat16):
+                yield self
+        finally:
+            for (obj, name), value in zip(targets, before):
+                if value is missing:
+                    vars(obj).pop(name, None)
+                else:
+                    setattr(obj, name, value)
+
     # ---------------------------------------------------------------- ocrfdet.py:144-173
     def lift_to_bev(self, x, stereo_feat, img, rot, tran, intrin, post_rot, post_tran, bda, mlp_input, feat_prev_iv,
-                    k2s_sensor, imgs_wo_norm, imgs_wo_aug, c2w):
+                    k2s_sensor, imgs_wo_norm, imgs_wo_aug, c2w, cv_feat_packed=None):
         """What follows the image encoder in ``prepare_bev_feat``: the view transformer on the image feature ``x`` with
         ``cv_feat_list = [feat_prev_iv, stereo_feat]``, then ``pre_process_net``.  ``(bev_feat, depth, bev_mask,
-        extras)``."""
+        extras)``.  ``cv_feat_packed``: ``[packed feat_prev_iv | None, packed stereo_feat | None]`` for the bfloat16 cost
+        volume (``depthnet.stereo_cost_volume_hip_bf16``), from a caller that has them packed already."""
         vt = self.img_view_transformer
         metas = dict(k2s_sensor=k2s_sensor, intrins=intrin, post_rots=post_rot, post_trans=post_tran,
                      frustum=vt.cv_frustum.to(x), cv_downsample=4, downsample=vt.downsample,
                      grid_config=vt.grid_config, cv_feat_list=[feat_prev_iv, stereo_feat])
+        if cv_feat_packed is not None:
+            metas['cv_feat_packed'] = cv_feat_packed
         bev_feat, depth, bev_mask, extras = vt(
             [x, rot, tran, intrin, post_rot, post_tran, bda, mlp_input, img, imgs_wo_norm, imgs_wo_aug, c2w], metas)
         if self.pre_process:
@@ -291,20 +327,22 @@ class OcRFDet4D(nn.Module):
                                   'prepare_bev_feat with 8 of its 16 arguments); streaming inference is stream_step')
 
     # ---------------------------------------------------------------- streaming inference (ocrfdet_amd/streaming.py)
-    def stream_step(self, img_inputs, state=None, new_sequence=None, multi_frame=False):
-        """One streaming step on ONE frame: ``(([x], depth, bev_mask), state)``.  ``streaming.stream_step``."""
+    def stream_step(self, img_inputs, state=None, new_sequence=None, multi_frame=False, bf16=False):
+        """One streaming step on ONE frame: ``(([x], depth, bev_mask), state)``.  ``streaming.stream_step``; ``bf16``:
+        the step runs inside ``bf16_inference()`` with a bfloat16 ring."""
         from .streaming import stream_step
-        return stream_step(self, img_inputs, state=state, new_sequence=new_sequence, multi_frame=multi_frame)
+        return stream_step(self, img_inputs, state=state, new_sequence=new_sequence, multi_frame=multi_frame, bf16=bf16)
 
     def simple_test_stream(self, img_inputs, img_metas=None, state=None, new_sequence=None, rescale=False,
-                           multi_frame=False):
+                           multi_frame=False, bf16=False):
         """``simple_test`` on a stream: ``stream_step``, then ``simple_test_pts``.  Returns ``(results, state)``,
-        ``results`` the list over the samples of ``dict(pts_bbox=dict(boxes_3d, scores_3d, labels_3d))``."""
+        ``results`` the list over the samples of ``dict(pts_bbox=dict(boxes_3d, scores_3d, labels_3d))``.  ``bf16``:
+        the step, the head and the decode run inside ``bf16_inference()``; the results are float32 as without it."""
         (img_feats, _, _), state = self.stream_step(img_inputs, state=state, new_sequence=new_sequence,
-                                                    multi_frame=multi_frame)
+                                                    multi_frame=multi_frame, bf16=bf16)
         if img_metas is None:
             img_metas = [dict() for _ in range(img_inputs[0].shape[0])]
-        with torch.no_grad():
+        with torch.no_grad(), (self.bf16_inference() if bf16 else contextlib.nullcontext()):
             pts = self.simple_test_pts(img_feats, img_metas, rescale=rescale)
         return [dict(pts_bbox=pts_bbox) for pts_bbox in pts], state
 

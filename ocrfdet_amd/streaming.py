@@ -18,12 +18,19 @@ The one deliberate deviation: the cached adjacent map was computed with ITS OWN 
 ``mlp_input``, the batch forward uses the key frame's there (``get_mlp_input(rots[0], trans[0], ...)``).  The two agree
 when the rig's calibration and the BEV augmentation do not change between the frames, as at test time.
 
+``bf16=True`` streams in bfloat16 on fused kernels from the images to the BEV encoder: the step runs inside
+``OcRFDet4D.bf16_inference()``, the ring is bfloat16 and aligned by ``ocrf_bev_stream_align_bf16``, and the stereo feature
+is packed once per frame for ``ocrf_stereo_cost_volume_bf16``: the packed previous frame is the one the previous step
+packed (``StreamState.stereo_packed``).
+
 No device -> host read in a step.  A step whose ``new_sequence`` flags are mixed uploads them (B bytes, from pinned
 memory, asynchronously); a step without a flag uploads nothing.
 """
+import contextlib
+
 import torch
 
-from . import temporal
+from . import depthnet, temporal
 from .detector import frame_poses
 
 
@@ -52,15 +59,20 @@ class StreamState:
     * ``sensor2ego0``, ``ego2global0`` (S, B, 4, 4), ``bda`` (S, B, 3, 3): camera 0's raw poses and the BEV augmentation
       at each slot's time, what ``temporal.stream_align`` evaluates its transforms from;
     * ``stereo``: the last key frame's stereo feature (B * N, ...), ``sensor2egos`` / ``ego2globals`` (B, N, 4, 4) its
-      raw poses: the previous frame of the next step's cost volume;
+      raw poses: the previous frame of the next step's cost volume; ``stereo_packed``: the same feature as
+      ``depthnet.stereo_pack_bf16`` lays it out, (B * N, NB, H, W, 8) sample-major, kept only by bfloat16 steps whose
+      cost volume takes the bfloat16 kernel (else None);
+    * ``bf16``: the mode of the steps that made the state; a step of the other mode does not continue it;
     * ``valid`` (B) int32 on the device: the number of real history frames of each sample, ``valid_host`` its host
       mirror, kept by counting (never read back)."""
 
-    def __init__(self, num_adj):
+    def __init__(self, num_adj, bf16=False):
         self.num_adj = int(num_adj)
+        self.bf16 = bool(bf16)
         self.head = 0
         self.ring = self.sensor2ego0 = self.ego2global0 = self.bda = None
         self.stereo = self.sensor2egos = self.ego2globals = None
+        self.stereo_packed = None
         self.valid = None
         self.valid_host = None
         self.steps = 0
@@ -69,10 +81,14 @@ class StreamState:
     def slots(self):
         return self.num_adj + 1
 
+    def ring_dtype(self, bev_feat):
+        """bfloat16 in a bf16 state (a float32 map is narrowed once by the copy into the ring), else the map's."""
+        return torch.bfloat16 if self.bf16 else bev_feat.dtype
+
     def allocate(self, bev_feat, sensor2egos):
         """The buffers, from the first key-frame map (B, C, H, W) and its poses (B, N, 4, 4)."""
         S, B = self.slots, bev_feat.shape[0]
-        self.ring = bev_feat.new_empty(S, *bev_feat.shape)
+        self.ring = bev_feat.new_empty((S, *bev_feat.shape), dtype=self.ring_dtype(bev_feat))
         self.sensor2ego0 = sensor2egos.new_zeros(S, B, 4, 4)
         self.ego2global0 = sensor2egos.new_zeros(S, B, 4, 4)
         self.bda = sensor2egos.new_zeros(S, B, 3, 3)
@@ -80,8 +96,8 @@ class StreamState:
         self.valid_host = [0] * B
 
     def matches(self, bev_feat):
-        return self.ring is not None and self.ring.shape[1:] == bev_feat.shape and self.ring.dtype == bev_feat.dtype \
-            and self.ring.device == bev_feat.device
+        return self.ring is not None and self.ring.shape[1:] == bev_feat.shape \
+            and self.ring.dtype == self.ring_dtype(bev_feat) and self.ring.device == bev_feat.device
 
 
 def _flags(new_sequence, B, fresh):
@@ -111,7 +127,24 @@ def _select(mask, own, cached):
     return torch.where(m, own, cached)
 
 
-def stream_step(det, img_inputs, state=None, new_sequence=None, multi_frame=False):
+def _packed_stereo(det, stereo_feat, B, N):
+    """``stereo_feat`` packed for ``ocrf_stereo_cost_volume_bf16`` (one ``ocrf_stereo_pack_bf16`` launch), or None when
+    the view transformer's cost volume would not take that kernel: the feature is not CUDA bfloat16, has fewer than 4
+    channels or a map below 2 x 2, or the depth net's ``fused_cost_volume`` / ``fused_cost_volume_bf16`` is off."""
+    vt = det.img_view_transformer
+    depth_net = getattr(vt, 'depth_net', None)
+    if not (getattr(depth_net, 'fused_cost_volume', False) and getattr(depth_net, 'fused_cost_volume_bf16', False)):
+        return None
+    if not (stereo_feat.is_cuda and stereo_feat.dtype == torch.bfloat16):
+        return None
+    H, W = vt.cv_frustum.shape[1:3]
+    channels, rest = divmod(stereo_feat.numel(), B * N * H * W)
+    if H < 2 or W < 2 or rest or channels < depthnet.GROUP:
+        return None
+    return depthnet.stereo_pack_bf16(stereo_feat.reshape(B * N, -1, H, W))
+
+
+def stream_step(det, img_inputs, state=None, new_sequence=None, multi_frame=False, bf16=False):
     """One streaming step of ``det`` (an ``OcRFDet4D`` in eval mode) on ONE frame: ``img_inputs`` is the 12-entry list
     with images (B, N, 3, H, W) and poses (B, N, ...), or with ``multi_frame=True`` the multi-frame list, of which frame 0
     is taken (``key_frame_inputs``).  ``new_sequence``: a host sequence of B bools, the samples whose sequence starts with
@@ -125,7 +158,14 @@ def stream_step(det, img_inputs, state=None, new_sequence=None, multi_frame=Fals
     ``new_sequence`` the cached stereo feature and poses are its own (selected on the device) and ``valid = 0``.
 
     With ``det.with_prev`` False the step returns what the batch forward returns for the frame (zeros and the key frame)
-    and keeps no state."""
+    and keeps no state.
+
+    ``bf16=True``: the step runs inside ``det.bf16_inference()``.  The ring is bfloat16 (a float32 ``bev_feat``, from a
+    detector without ``pre_process``, is narrowed once by the copy into the ring) and ``temporal.stream_align`` keeps it
+    (``keep_bf16=True``); the new stereo feature is packed once and the view transformer gets ``cv_feat_packed =
+    [cached packed, own packed]``; ``[x]`` is what the BEV encoder returns under ``autocast_bf16``, ``depth`` and
+    ``bev_mask`` come back as the neck returns them.  A state made by steps of the other mode is not continued: the step
+    starts every sequence, as with ``state=None``.  CPU inputs raise ``ValueError`` before any module runs."""
     if det.training:
         raise RuntimeError('stream_step is a test mode: call eval() first (training takes extract_img_feat)')
     if multi_frame:
@@ -137,15 +177,19 @@ def stream_step(det, img_inputs, state=None, new_sequence=None, multi_frame=Fals
     if imgs.dim() != 5 or sensor2egos.dim() != 4:
         raise ValueError(f'stream_step takes ONE frame: images (B, N, 3, H, W) and poses (B, N, 4, 4), got '
                          f'{tuple(imgs.shape)} and {tuple(sensor2egos.shape)}')
+    bf16 = bool(bf16)
+    if bf16 and not all(t.is_cuda for t in img_inputs if isinstance(t, torch.Tensor)):
+        raise ValueError('stream_step(bf16=True) runs on the GPU only: the bfloat16 kernels have no CPU form; move '
+                         'img_inputs to the GPU or stream with bf16=False')
     B, N = imgs.shape[:2]
     K = det.num_frame - det.extra_ref_frames - 1
-    with torch.no_grad():
+    with torch.no_grad(), (det.bf16_inference() if bf16 else contextlib.nullcontext()):
         if not det.with_prev:
             return _step_without_history(det, img_inputs, K), None
         fresh = state is None or state.num_adj != K or state.ring is None or state.ring.shape[1] != B \
-            or state.sensor2egos.shape != sensor2egos.shape
+            or state.sensor2egos.shape != sensor2egos.shape or state.bf16 != bf16
         if fresh:
-            state = StreamState(K)
+            state = StreamState(K, bf16=bf16)
         flags = _flags(new_sequence, B, fresh)
         mask = None if all(flags) or not any(flags) else _upload(flags, imgs.device)
         own = all(flags)
@@ -159,13 +203,22 @@ def stream_step(det, img_inputs, state=None, new_sequence=None, multi_frame=Fals
             prev_stereo = _select(mask, stereo_feat, state.stereo)
             prev_s2e = _select(mask, sensor2egos, state.sensor2egos)
             prev_e2g = _select(mask, ego2globals, state.ego2globals)
+        packed = None
+        own_packed = _packed_stereo(det, stereo_feat, B, N) if bf16 else None
+        if own_packed is not None:
+            cached = state.stereo_packed
+            if own or cached is None or cached.shape != own_packed.shape:
+                cached = own_packed if own else None              # None: the cost volume packs the previous feature
+            elif mask is not None:
+                cached = _select(mask, own_packed, cached)
+            packed = [cached, own_packed]
         pair = lambda a, b: torch.stack([a, b], 1)                # noqa: E731  (B, 2, N, ...)
         _, curr2adj, mlp_input = frame_poses(pair(sensor2egos, prev_s2e), pair(ego2globals, prev_e2g), pair(rots, rots),
                                              pair(trans, trans), pair(intrins, intrins), pair(post_rots, post_rots),
                                              pair(post_trans, post_trans), bda, 1, fused=det.fused_poses)
         bev_feat, depth, bev_mask, _ = det.lift_to_bev(x, stereo_feat, imgs, rots, trans, intrins, post_rots,
                                                           post_trans, bda, mlp_input[0], prev_stereo, curr2adj[:, 0],
-                                                          imgs_wo_norm, imgs_wo_aug, c2w)
+                                                          imgs_wo_norm, imgs_wo_aug, c2w, cv_feat_packed=packed)
         if not state.matches(bev_feat):
             state.allocate(bev_feat, sensor2egos)
         head = state.head
@@ -182,11 +235,13 @@ def stream_step(det, img_inputs, state=None, new_sequence=None, multi_frame=Fals
         vt = det.img_view_transformer
         cat, _ = temporal.stream_align(state.ring, head, state.valid, state.sensor2ego0, state.ego2global0, state.bda,
                                        vt.grid_interval, vt.grid_lower_bound,
-                                       align=bool(det.align_after_view_transfromation), fused=det.fused_align)
+                                       align=bool(det.align_after_view_transfromation), fused=det.fused_align,
+                                       keep_bf16=bf16)
         out = det.bev_encoder(cat)
 
         state.head = (head + 1) % state.slots
         state.stereo, state.sensor2egos, state.ego2globals = stereo_feat, sensor2egos, ego2globals
+        state.stereo_packed = own_packed
         if K > 0:
             state.valid.add_(1).clamp_(max=K)
         state.valid_host = [min(v + 1, K) for v in state.valid_host]

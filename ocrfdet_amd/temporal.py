@@ -10,6 +10,7 @@
 * ``align_and_cat``: every frame warped (the key frame copied) straight into its channels of one concatenation;
 * ``stream_align`` / ``stream_align_torch``: the streaming step's concatenation from a ring of the last key-frame maps
   and the raw poses kept with them, the transforms included, as one HIP launch (``csrc/bev_stream_align.hip``);
+  ``keep_bf16=True`` keeps a bfloat16 ring bfloat16 (``ocrf_bev_stream_align_bf16`` / ``stream_align_torch_bf16``);
 * ``gen_grid`` / ``shift_feature_method``: the reference's method signatures, adopted by assignment.
 
 Sampling rule of the kernels (include/ocrf_hip.h): with ``t`` the float32 rounding of rows 0 and 1 of ``tf``, output
@@ -441,10 +442,12 @@ def stream_align_torch(ring, head, valid, sensor2ego0, ego2global0, bda, grid_in
         return out, tf_out
 
 
-def stream_align_fusable(ring, valid, sensor2ego0, ego2global0, bda, grid_interval, grid_lower_bound):
-    """The kernel takes these: a CUDA float32 contiguous ring, ``valid`` int32 and float32 contiguous poses on its device,
-    and grid constants on the host (a sequence or a CPU tensor: reading a device tensor would synchronise)."""
-    if not (ring.is_cuda and ring.dtype == torch.float32 and ring.is_contiguous() and ring.dim() == 5
+def stream_align_fusable(ring, valid, sensor2ego0, ego2global0, bda, grid_interval, grid_lower_bound,
+                         dtype=torch.float32):
+    """The kernel takes these: a CUDA contiguous ring of ``dtype`` (float32; bfloat16 for ``ocrf_bev_stream_align_bf16``),
+    ``valid`` int32 and float32 contiguous poses on its device, and grid constants on the host (a sequence or a CPU
+    tensor: reading a device tensor would synchronise)."""
+    if not (ring.is_cuda and ring.dtype == dtype and ring.is_contiguous() and ring.dim() == 5
             and ring.numel() > 0):
         return False
     if not (valid.dtype == torch.int32 and valid.device == ring.device and valid.is_contiguous()):
@@ -455,8 +458,29 @@ def stream_align_fusable(ring, valid, sensor2ego0, ego2global0, bda, grid_interv
                for t in (sensor2ego0, ego2global0, bda))
 
 
+def stream_align_torch_bf16(ring, head, valid, sensor2ego0, ego2global0, bda, grid_interval, grid_lower_bound,
+                            align=True, out=None):
+    """``stream_align_torch`` for a bfloat16 ring with a bfloat16 result, as ``ocrf_bev_stream_align_bf16`` computes it:
+    the selection and the float64 transforms are ``stream_align_torch``'s, every warped group is
+    ``_shift_feature_torch_bf16(src, tf)`` (the map widened, grid and ``grid_sample`` in float32 with autocast off, the
+    result rounded once) and a copied group is the bfloat16 source itself.  Any device; forward only."""
+    S, B, C, H, W = _check_stream_operands(ring, head, valid, sensor2ego0, ego2global0, bda, out)
+    if ring.dtype != torch.bfloat16:
+        raise ValueError(f'stream_align_torch_bf16 takes a bfloat16 ring, got {ring.dtype}')
+    with torch.no_grad(), torch.autocast(ring.device.type if ring.device.type in ('cuda', 'cpu') else 'cuda',
+                                         enabled=False):
+        # the widening is exact, the float32 warp rounded once is _shift_feature_torch_bf16, and a widened copied
+        # group rounds back to its own bits
+        wide, tf_out = stream_align_torch(ring.float(), head, valid, sensor2ego0, ego2global0, bda, grid_interval,
+                                          grid_lower_bound, align=align)
+        if out is None:
+            return wide.to(torch.bfloat16), tf_out
+        out.copy_(wide)
+        return out, tf_out
+
+
 def stream_align(ring, head, valid, sensor2ego0, ego2global0, bda, grid_interval, grid_lower_bound, align=True,
-                 out=None, fused=None):
+                 out=None, fused=None, keep_bf16=False):
     """``stream_align_torch`` with the usual dispatch: operands that ``stream_align_fusable`` accepts take ONE launch of
     ``ocrf_bev_stream_align`` (``csrc/bev_stream_align.hip``), which evaluates the transforms itself and writes every
     group of the concatenation; everything else, the CPU included, the torch formulation.  ``fused`` (default
@@ -464,18 +488,28 @@ def stream_align(ring, head, valid, sensor2ego0, ego2global0, bda, grid_interval
 
     A warped group of the kernel is bit-equal to ``shift_feature(ring[slot], tf[g], out=...)``, the existing kernel fed
     the returned ``tf``; ``tf`` agrees with the torch formulation's within one float32 ulp (both round a float64 value
-    once)."""
+    once).
+
+    ``keep_bf16`` (opt-in): a bfloat16 ring stays bfloat16.  The result is bfloat16 (``out=`` must then be a bfloat16
+    view); CUDA contiguous operands take ONE launch of ``ocrf_bev_stream_align_bf16``, everything else
+    ``stream_align_torch_bf16``, which computes as the kernel does.  A warped group of the kernel is bit-equal to
+    ``shift_feature(ring[slot], tf[g], keep_bf16=True)`` (the float32 kernel's value on the widened taps, rounded once),
+    a copied group a bit copy, ``tf`` bit-equal to the float32 kernel's.  Without the keyword, or with a ring that is
+    not bfloat16, the call goes exactly where it goes without it."""
+    keep = keep_bf16 and ring.dtype == torch.bfloat16
+    dtype = torch.bfloat16 if keep else torch.float32
     if not ((FUSED_ALIGN_DEFAULT if fused is None else fused)
-            and stream_align_fusable(ring, valid, sensor2ego0, ego2global0, bda, grid_interval, grid_lower_bound)):
-        return stream_align_torch(ring, head, valid, sensor2ego0, ego2global0, bda, grid_interval, grid_lower_bound,
-                                  align=align, out=out)
+            and stream_align_fusable(ring, valid, sensor2ego0, ego2global0, bda, grid_interval, grid_lower_bound,
+                                     dtype=dtype)):
+        return (stream_align_torch_bf16 if keep else stream_align_torch)(
+            ring, head, valid, sensor2ego0, ego2global0, bda, grid_interval, grid_lower_bound, align=align, out=out)
     S, B, C, H, W = _check_stream_operands(ring, head, valid, sensor2ego0, ego2global0, bda, out)
     if out is None:
-        out = torch.empty(B, S * C, H, W, dtype=torch.float32, device=ring.device)
+        out = torch.empty(B, S * C, H, W, dtype=dtype, device=ring.device)
     tf_out = torch.empty(S - 1, B, 3, 3, dtype=torch.float32, device=ring.device)
     ix, iy = _pair(grid_interval, ring)
     lx, ly = _pair(grid_lower_bound, ring)
-    _lib.launch('ocrf_bev_stream_align', ring.device, S, B, C, H, W, ring, int(head), valid, sensor2ego0, ego2global0,
+    _lib.launch('ocrf_bev_stream_align' + _SUFFIX[dtype], ring.device, S, B, C, H, W, ring, int(head), valid, sensor2ego0, ego2global0,
                 bda, ix, iy, lx, ly, 1 if align else 0, out, _batch_stride(out), tf_out)
     return out, tf_out
 

@@ -17,6 +17,15 @@ only; the acceptance conditions are structural (one launch for the alignment, on
 step) and checked by the tests.
 
     python tools/time_stream.py [--iters N] [--out profiles/stream_time.txt]
+    python tools/time_stream.py --bf16 [--iters N] [--out profiles/stream_bf16_time.txt]
+
+``--bf16`` times bfloat16 streaming instead, in the same way.  Align, on the same maps rounded to bfloat16:
+``stream_align(keep_bf16=True)`` (one launch of ``ocrf_bev_stream_align_bf16``) against the float32 kernel on the float32
+ring and against ``stream_align_torch`` on the bfloat16 ring, which is where a bfloat16 ring goes without the keyword.
+Whole detector, three arms alternating, each with a state of its own: (a) ``stream_step(bf16=True)``, (b) the float32
+``stream_step``, (c) ``stream_step`` under plain ``torch.autocast('cuda', torch.bfloat16)`` with every switch at its
+default.  Decode: ``CenterHead.get_bboxes_padded`` at B = 1 on the bfloat16 head outputs of a bf16 step, with and
+without ``fused_decode_bf16``.
 
 Every case runs in a child process of its own under a time limit (``--limit`` seconds); the first case that fails or
 runs out of time ends the run.
@@ -32,6 +41,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 CASES = ['align', 'detector']
+CASES_BF16 = ['align_bf16', 'detector_bf16']
 SEQUENCE = 6
 
 
@@ -172,10 +182,136 @@ def run_detector(iters):
           f'{_syncs(batch)} synchronisations | batch / stream device {bd / sd:.2f}x, wall median {bm / sm:.2f}x')
 
 
+def _arm(label, fn, wall, reps=5):
+    """One arm's figures as a phrase: device ms and launches per call (torch profiler), wall best / median, syncs."""
+    from time_detector import _profile, _syncs
+    launches, dev_ms, names = _profile(fn, reps=reps)
+    return (f'{label} {dev_ms:.3f} ms device, {launches:.0f} launches, wall best {wall[0]:.3f} / median {wall[1]:.3f} ms, '
+            f'{_syncs(fn)} synchronisations'), dev_ms, names
+
+
+def run_align_bf16(iters):
+    import numpy as np
+    import torch
+    from time_bev_encoder import _wall
+    from ocrfdet_amd import synthetic, temporal
+    dev = torch.device('cuda:0')
+    B, C, H, W = 1, 80, 128, 128
+    interval, lower = (0.8, 0.8, 8.0), (-51.2, -51.2, -5.0)
+    for K in (1, 7):
+        S = K + 1
+        gen = torch.Generator().manual_seed(K)
+        ring16 = torch.randn(S, B, C, H, W, generator=gen).to(dev).to(torch.bfloat16)
+        ring32 = ring16.float()
+        rig = synthetic.rig(1, (256, 704), B)
+        s2e = torch.from_numpy(np.ascontiguousarray(rig['c2w'], np.float32))[:, 0].to(dev)
+        G = global_pose()
+        e2g = torch.from_numpy(np.stack([G @ synthetic.ego_motion(K - s) for s in range(S)]).astype(np.float32))
+        e2g = e2g.view(S, 1, 4, 4).expand(S, B, 4, 4).contiguous().to(dev)
+        s2e_slots = s2e.expand(S, B, 4, 4).contiguous()
+        bda = torch.eye(3, device=dev).expand(S, B, 3, 3).contiguous()
+        valid = torch.full((B,), K, dtype=torch.int32, device=dev)
+        ops = (K, valid, s2e_slots, e2g, bda, interval, lower)
+
+        def bf16():
+            return temporal.stream_align(ring16, *ops, keep_bf16=True)[0]
+
+        def f32():
+            return temporal.stream_align(ring32, *ops)[0]
+
+        def torch16():
+            return temporal.stream_align(ring16, *ops)[0]           # no keyword: stream_align_torch on the bf16 ring
+        a, b, c = bf16(), f32(), torch16()
+        torch.cuda.synchronize()
+        exact = bool(torch.equal(a, b.bfloat16()))
+        diff = float((a.float() - c.float()).abs().max())
+        fns = [bf16, f32, torch16]
+        for fn in fns:
+            for _ in range(5):
+                fn()
+        walls = _wall(fns, iters)
+        texts = [_arm(label, fn, wall) for label, fn, wall in zip(
+            ('stream_align(keep_bf16=True)', 'float32 stream_align', 'stream_align_torch on bf16'), fns, walls)]
+        print(f'align, K = {K}, maps ({B}, {C}, {H}, {W}) bf16: ' + ' | '.join(t[0] for t in texts)
+              + f' | float32 / bf16 kernel device {texts[1][1] / texts[0][1]:.2f}x, torch / bf16 kernel device '
+                f'{texts[2][1] / texts[0][1]:.1f}x | bf16 == float32 kernel rounded once: {exact}; max |bf16 kernel - '
+                f'torch on bf16| {diff:.2e}')
+        print(f'    kernels of stream_align(keep_bf16=True): {dict(texts[0][2])}')
+
+
+def run_detector_bf16(iters):
+    import random
+
+    import torch
+    from time_bev_encoder import _wall
+    from time_detector import INPUT_SIZE, N_CAMS, reference_model
+    from ocrfdet_amd import detector
+    dev = torch.device('cuda:0')
+    torch.manual_seed(0)
+    det = detector.OcRFDet4D(**reference_model()).to(dev).eval()
+    frames = frames_of(SEQUENCE, 1, N_CAMS, INPUT_SIZE, dev)
+    clock = dict(a=0, b=0, c=0, sa=None, sb=None, sc=None)
+
+    def arm(key, **kw):
+        def step():
+            random.seed(0)
+            t = clock[key] % SEQUENCE
+            clock[key] += 1
+            out, clock['s' + key] = det.stream_step(frames[t], clock['s' + key], **kw)
+            return out
+        return step
+    a, b, plain = arm('a', bf16=True), arm('b'), arm('c')
+
+    def c():
+        with torch.autocast('cuda', dtype=torch.bfloat16):          # every switch at its default
+            return plain()
+    fns = [a, b, c]
+    for fn in fns:
+        for _ in range(SEQUENCE):
+            fn()
+    walls = _wall(fns, iters, blocks=3)
+    texts = [_arm(label, fn, wall, reps=SEQUENCE) for label, fn, wall in zip(
+        ('(a) stream_step(bf16=True)', '(b) float32 stream_step', '(c) stream_step under plain autocast'), fns, walls)]
+    print(f'OcRFDet4D, reference config, B = 1, a sequence of {SEQUENCE} frames: ' + ' | '.join(t[0] for t in texts)
+          + f' | (b) / (a) device {texts[1][1] / texts[0][1]:.2f}x, wall median {walls[1][1] / walls[0][1]:.2f}x | '
+            f'(c) / (a) device {texts[2][1] / texts[0][1]:.2f}x, wall median {walls[2][1] / walls[0][1]:.2f}x')
+    own = {k.split('(anonymous namespace)::', 1)[1].split('(')[0]: v for k, v in texts[0][2].items()
+           if 'anonymous namespace' in k}
+    print(f'    library kernels of {SEQUENCE} steps of (a): {own}')
+    # decode: the bfloat16 head outputs of a bf16 step, with and without the in-place read
+    head = det.pts_bbox_head
+    x, _, _ = a()
+    with torch.no_grad(), det.bf16_inference():
+        preds = head(x)
+    assert all(v.dtype == torch.bfloat16 for p in preds for v in p[0].values())
+
+    def decode(flag):
+        def fn():
+            head.fused_decode_bf16 = flag
+            with torch.no_grad(), torch.autocast('cuda', dtype=torch.bfloat16):
+                return head.get_bboxes_padded(preds)
+        return fn
+    on, off = decode(True), decode(False)
+    got, want = on(), off()
+    torch.cuda.synchronize()
+    same = all(bool(torch.equal(p, q)) for p, q in zip(got, want))
+    for fn in (on, off):
+        for _ in range(5):
+            fn()
+    walls = _wall([on, off], iters * 5)
+    texts = [_arm(label, fn, wall) for label, fn, wall in zip(
+        ('fused_decode_bf16 on', 'fused_decode_bf16 off (36 casts)'), (on, off), walls)]
+    del head.fused_decode_bf16
+    print(f'get_bboxes_padded, B = 1, {len(preds)} tasks on bf16 heads: ' + ' | '.join(t[0] for t in texts)
+          + f' | off / on device {texts[1][1] / texts[0][1]:.2f}x, wall median {walls[1][1] / walls[0][1]:.2f}x | '
+            f'same results: {same}')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--bf16', action='store_true', help='time bfloat16 streaming (see the module docstring)')
     ap.add_argument('--limit', type=int, default=300, help='seconds per case')
     ap.add_argument('--case', type=int, default=None, help='(internal) run this one case in this process')
     a = ap.parse_args()
@@ -183,22 +319,23 @@ def main():
         import torch
         assert torch.cuda.is_available(), 'timing needs the GPU: there is no CPU fallback for a measurement'
         if a.case == 0:
-            run_align(a.iters * 10)
+            (run_align_bf16 if a.bf16 else run_align)(a.iters * 10)
         else:
-            run_detector(SEQUENCE * max(a.iters // 10, 1))       # whole sequences per block
+            (run_detector_bf16 if a.bf16 else run_detector)(SEQUENCE * max(a.iters // 10, 1))   # whole sequences per block
         return 0
     lines = []
-    for k in range(len(CASES)):
+    cases = CASES_BF16 if a.bf16 else CASES
+    for k in range(len(cases)):
         try:
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), '--case', str(k), '--iters', str(a.iters)],
-                               stdout=subprocess.PIPE, text=True, timeout=a.limit)
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), '--case', str(k), '--iters', str(a.iters)]
+                               + (['--bf16'] if a.bf16 else []), stdout=subprocess.PIPE, text=True, timeout=a.limit)
         except subprocess.TimeoutExpired:
-            print(f'case {CASES[k]} ran out of its {a.limit} s: stopping', file=sys.stderr)
+            print(f'case {cases[k]} ran out of its {a.limit} s: stopping', file=sys.stderr)
             return 124
         sys.stdout.write(p.stdout)
         sys.stdout.flush()
         if p.returncode != 0:
-            print(f'case {CASES[k]} ended with status {p.returncode}: stopping', file=sys.stderr)
+            print(f'case {cases[k]} ended with status {p.returncode}: stopping', file=sys.stderr)
             return p.returncode or 1
         lines.append(p.stdout)
     if a.out:
