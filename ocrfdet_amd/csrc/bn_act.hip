@@ -57,28 +57,6 @@ constexpr int kWave = 64;
 constexpr int kWaves = kThreads / kWave;
 static_assert(kThreads == 256 && kPerThread == 16 && kWaves == 4, "the comments of this file state these values");
 
-template <int V>
-__device__ __forceinline__ void load_group(const float* p, float (&v)[V]) {
-  if constexpr (V == 4) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-  } else {
-    static_assert(V == 1, "a group of floats is 4 or 1");
-    v[0] = *p;
-  }
-}
-template <int V>
-__device__ __forceinline__ void load_group(const bf16_t* p, float (&v)[V]) {
-  if constexpr (V == 8) {
-    const uint4 t = *reinterpret_cast<const uint4*>(p);
-    v[0] = widen_lo(t.x), v[1] = widen_hi(t.x), v[2] = widen_lo(t.y), v[3] = widen_hi(t.y);
-    v[4] = widen_lo(t.z), v[5] = widen_hi(t.z), v[6] = widen_lo(t.w), v[7] = widen_hi(t.w);
-  } else {
-    static_assert(V == 1, "a group of bf16 is 8 or 1");
-    v[0] = widen(*p);
-  }
-}
-
 // The workgroup's (channel, chunk) and the walk over the chunk's segments.  one(off, q) handles the single element at
 // tensor offset `off`, value q of the chunk; wide(off, q) the V consecutive elements from there, `off` a multiple of V.
 struct Chunk {

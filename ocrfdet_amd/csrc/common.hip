@@ -152,6 +152,8 @@ const char* ocrf_kernel_name(int kernel_id) {
     case OCRF_K_CD_WRITE: return "cd_write_kernel";
     case OCRF_K_UPSAMPLE_CAT: return "upsample_cat_kernel<float, *>";
     case OCRF_K_UPSAMPLE_CAT_BWD: return "upsample_cat_backward_kernel<float>";
+    // ids 104-107 and 113-116 keep the names they were introduced under (profiles and tools list them by these); the
+    // symbols are binary_kernel<T, V, Op>, upsample_add_kernel<T, V> and upsample_add_backward_kernel<T> of resnet_fuse.hip
     case OCRF_K_ADD_RELU: return "binary_kernel<*, AddRelu>";
     case OCRF_K_ADD_RELU_BWD: return "binary_kernel<*, Threshold>";
     case OCRF_K_UPSAMPLE_ADD: return "upsample_add_kernel<*>";

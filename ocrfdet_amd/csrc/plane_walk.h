@@ -27,29 +27,6 @@ constexpr int kMaxBlocks = 2048;                   // 8 workgroups per CU; the r
 constexpr int kMaxAxisSum = 8192;                  // Hout + Wout: the tables take up to 8 bytes per entry of 64 KiB LDS
 constexpr long long kTwoGiB = 1LL << 31;
 
-template <int V>
-struct Vec;
-template <>
-struct Vec<4> {
-  using type = float4;
-};
-template <>
-struct Vec<1> {
-  using type = float;
-};
-
-// the same for 16-bit elements: 8 of them in one 16-byte access, or one
-template <int V>
-struct Vec16;
-template <>
-struct Vec16<8> {
-  using type = uint4;
-};
-template <>
-struct Vec16<1> {
-  using type = unsigned short;
-};
-
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // ---------------------------------------------------------------------------------------------- bf16 arithmetic
@@ -76,20 +53,37 @@ __device__ __forceinline__ float load_f32(const bf16_t* p) { return widen(*p); }
 __device__ __forceinline__ void store_f32(float* p, float v) { *p = v; }
 __device__ __forceinline__ void store_f32(bf16_t* p, float v) { *p = round_one(v); }
 
-// The same for a group of V consecutive elements, one access: 16 bytes for the wide form (4 floats, 8 bf16), one
-// element for V = 1.  kWide<T> is the wide form's V, GroupOf<T, V> the type that moves a group untouched.
+// The same for a group of V consecutive elements, one access (load_group / store_group): 16 bytes for the wide form
+// (4 floats, 8 bf16), one element for V = 1.  kWide<T> is the wide form's V, GroupOf<T, V> the type that moves a group
+// untouched.
 template <typename T>
 constexpr int kWide = 16 / (int)sizeof(T);
 template <typename T, int V>
-struct GroupOf;
-template <int V>
-struct GroupOf<float, V> {
-  using type = typename Vec<V>::type;
+struct GroupOf {
+  static_assert(V == 1, "a group is one 16-byte access or one element");
+  using type = T;
 };
-template <int V>
-struct GroupOf<bf16_t, V> {
-  using type = typename Vec16<V>::type;
+template <>
+struct GroupOf<float, 4> {
+  using type = float4;
 };
+template <>
+struct GroupOf<bf16_t, 8> {
+  using type = uint4;
+};
+
+// a group as it was loaded -> its V elements as float32
+__device__ __forceinline__ void unpack(float t, float (&v)[1]) { v[0] = t; }
+__device__ __forceinline__ void unpack(float4 t, float (&v)[4]) { v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w; }
+__device__ __forceinline__ void unpack(bf16_t t, float (&v)[1]) { v[0] = widen(t); }
+__device__ __forceinline__ void unpack(uint4 t, float (&v)[8]) {
+  v[0] = widen_lo(t.x), v[1] = widen_hi(t.x), v[2] = widen_lo(t.y), v[3] = widen_hi(t.y);
+  v[4] = widen_lo(t.z), v[5] = widen_hi(t.z), v[6] = widen_lo(t.w), v[7] = widen_hi(t.w);
+}
+template <int V, typename T>
+__device__ __forceinline__ void load_group(const T* p, float (&v)[V]) {
+  unpack(*reinterpret_cast<const typename GroupOf<T, V>::type*>(p), v);
+}
 
 template <int V>
 __device__ __forceinline__ void store_group(float* p, const float (&v)[V]) {

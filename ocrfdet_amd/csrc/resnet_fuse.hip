@@ -32,13 +32,15 @@
 // inside a row its run of columns, in ascending order into one float32 accumulator.  The lanes of a wave read
 // neighbouring runs of the same destination rows, so every fetched line is used in full.
 //
-// bfloat16 (the *_bf16 entry points, for the encoder under bf16 autocast).  The same four passes on bf16 data, passed as
-// unsigned short.  Arithmetic as torch's bf16 element-wise ops: widen both operands to float32 (a shift: exact), one
-// float32 addition, one rounding to bf16 to nearest even (the compiler's float -> __bf16 conversion: v_cvt_pk_bf16_f32
-// on gfx950, two values per instruction); the ReLU tests the rounded sum, the threshold is a select on grad_out's bits.
-// The layout is the same with the access width counted in bytes: a 16-byte group is V = 8 elements, the tail is n % 8
-// elements, the narrow form a 2-byte access; upsample_add's wide path needs P % 8 == 0.  A thread of the wide path
-// works on four 32-bit words of two bf16 each.  The backward keeps one thread per source pixel and one float32
+// bfloat16 (the *_bf16 entry points, for the encoder under bf16 autocast).  Every kernel is a template on the element
+// type, float or bf16 (as unsigned short), with ONE body: load_group / unpack / load_f32 widen the operands to float32 (a
+// shift: exact), the op is the float32 expression above, store_group / store_f32 round once to bf16 to nearest even (the
+// compiler's float -> __bf16 conversion: v_cvt_pk_bf16_f32 on gfx950, two values per instruction).  The ReLU tests the
+// float32 sum, whose sign is the rounded sum's: a sum of two bf16 values is a multiple of the smallest bf16 denormal,
+// so a negative one does not round to zero.  The threshold's result is an element of grad_out or zero and is stored as
+// that element's bits, never through the rounding (store_result).  The layout is the same with the access width
+// counted in bytes: a 16-byte group is V = 8 elements, the tail is n % 8 elements, the narrow form a 2-byte access;
+// upsample_add's wide path needs P % 8 == 0.  The backward keeps one thread per source pixel and one float32
 // accumulator, and rounds once.
 #include <hip/hip_runtime.h>
 
@@ -54,44 +56,52 @@ using namespace plane;
 //   constexpr int kThreads = 256;  constexpr int kGroups = 4;  constexpr int kMaxBlocks = 2048;
 static_assert(kThreads == 256 && kGroups == 4 && kMaxBlocks == 2048, "the comments of this file state these values");
 
-__device__ __forceinline__ float relu_of_sum(float a, float b) {
-  const float s = a + b;
-  return s < 0.0f ? 0.0f : s;                      // NaN < 0 is false: a NaN sum stays NaN
-}
-__device__ __forceinline__ float4 relu_of_sum(float4 a, float4 b) {
-  return make_float4(relu_of_sum(a.x, b.x), relu_of_sum(a.y, b.y), relu_of_sum(a.z, b.z), relu_of_sum(a.w, b.w));
-}
-__device__ __forceinline__ float threshold(float out, float g) {
-  return out <= 0.0f ? 0.0f : g;                   // NaN <= 0 is false: a NaN out passes the gradient
-}
-__device__ __forceinline__ float4 threshold(float4 o, float4 g) {
-  return make_float4(threshold(o.x, g.x), threshold(o.y, g.y), threshold(o.z, g.z), threshold(o.w, g.w));
-}
-
-struct AddRelu {
-  template <typename T>
-  __device__ __forceinline__ T operator()(T a, T b) const {
-    return relu_of_sum(a, b);
+// The ops of the element-wise passes, on float32 values.  kSelects: the result is the first operand or zero.
+struct AddRelu {                                   // (a, b) -> relu(a + b)
+  static constexpr bool kSelects = false;
+  __device__ __forceinline__ float operator()(float a, float b) const {
+    const float s = a + b;
+    return s < 0.0f ? 0.0f : s;                    // NaN < 0 is false: a NaN sum stays NaN
   }
 };
 struct Threshold {                                 // (grad_out, out) -> grad
-  template <typename T>
-  __device__ __forceinline__ T operator()(T g, T o) const {
-    return threshold(o, g);
+  static constexpr bool kSelects = true;
+  __device__ __forceinline__ float operator()(float g, float o) const {
+    return o <= 0.0f ? 0.0f : g;                   // NaN <= 0 is false: a NaN out passes the gradient
   }
 };
 
-// out[i] = op(p[i], q[i]) for i in [0, n): groups = n / V whole groups of type VT, chunks of kThreads * kGroups of them
-template <int V, typename VT, typename Op, typename T>
-__device__ __forceinline__ void binary_body(int n, int groups, int chunks, const T* __restrict__ p,
-                                            const T* __restrict__ q, T* __restrict__ out) {
+// A group of results to memory: rounded once, or, for an op that selects among widened bf16 operands, their upper
+// halves, which are the operands' bits (a rounding would quiet a signalling NaN).
+template <typename Op, int V>
+__device__ __forceinline__ void store_result(float* p, const float (&v)[V]) {
+  store_group<V>(p, v);
+}
+template <typename Op, int V>
+__device__ __forceinline__ void store_result(bf16_t* p, const float (&v)[V]) {
+  if constexpr (!Op::kSelects) {
+    store_group<V>(p, v);
+  } else if constexpr (V == 8) {
+    auto word = [](float lo, float hi) { return (__float_as_uint(lo) >> 16) | (__float_as_uint(hi) & 0xffff0000u); };
+    *reinterpret_cast<uint4*>(p) = make_uint4(word(v[0], v[1]), word(v[2], v[3]), word(v[4], v[5]), word(v[6], v[7]));
+  } else {
+    static_assert(V == 1, "a group of bf16 is 8 or 1");
+    *p = (bf16_t)(__float_as_uint(v[0]) >> 16);
+  }
+}
+
+// out[i] = op(p[i], q[i]) for i in [0, n): groups = n / V whole groups, chunks of kThreads * kGroups of them
+template <typename T, int V, typename Op>
+__global__ void __launch_bounds__(kThreads) binary_kernel(int n, int groups, int chunks, const T* __restrict__ p,
+                                                           const T* __restrict__ q, T* __restrict__ out) {
+  using VT = typename GroupOf<T, V>::type;
   const Op op;
   const VT* pv = reinterpret_cast<const VT*>(p);
   const VT* qv = reinterpret_cast<const VT*>(q);
   VT* ov = reinterpret_cast<VT*>(out);
   for (int c = blockIdx.x; c < chunks; c += gridDim.x) {
     const int first = c * (kThreads * kGroups) + (int)threadIdx.x;
-    VT x[kGroups], y[kGroups];
+    VT x[kGroups], y[kGroups];                     // as loaded: widened only where they are used
 #pragma unroll
     for (int g = 0; g < kGroups; ++g) {
       const int idx = first + g * kThreads;
@@ -103,54 +113,23 @@ __device__ __forceinline__ void binary_body(int n, int groups, int chunks, const
 #pragma unroll
     for (int g = 0; g < kGroups; ++g) {
       const int idx = first + g * kThreads;
-      if (idx < groups) ov[idx] = op(x[g], y[g]);
+      if (idx < groups) {
+        float a[V], b[V];
+        unpack(x[g], a);
+        unpack(y[g], b);
+#pragma unroll
+        for (int k = 0; k < V; ++k) a[k] = op(a[k], b[k]);
+        store_result<Op, V>(reinterpret_cast<T*>(ov + idx), a);
+      }
     }
   }
   if constexpr (V > 1) {                           // the n % V elements behind the last whole group
     const int i = groups * V + (int)threadIdx.x;
-    if (blockIdx.x == 0 && i < n) out[i] = op(p[i], q[i]);
+    if (blockIdx.x == 0 && i < n) {
+      const float r[1] = {op(load_f32(p + i), load_f32(q + i))};
+      store_result<Op, 1>(out + i, r);
+    }
   }
-}
-
-template <int V, typename Op>
-__global__ void __launch_bounds__(kThreads) binary_kernel(int n, int groups, int chunks, const float* __restrict__ p,
-                                                           const float* __restrict__ q, float* __restrict__ out) {
-  binary_body<V, typename Vec<V>::type, Op>(n, groups, chunks, p, q, out);
-}
-
-// ---------------------------------------------------------------------------------------------- bf16 arithmetic
-// bf16_t, widen / widen_lo / widen_hi and round_one / round_pair are plane_walk.h's
-struct AddReluBf16 {
-  __device__ __forceinline__ bf16_t operator()(bf16_t a, bf16_t b) const {
-    const bf16_t s = round_one(widen(a) + widen(b));
-    return widen(s) < 0.0f ? (bf16_t)0 : s;        // on the rounded sum; NaN < 0 is false
-  }
-  __device__ __forceinline__ unsigned operator()(unsigned a, unsigned b) const {
-    const unsigned s = round_pair(widen_lo(a) + widen_lo(b), widen_hi(a) + widen_hi(b));
-    return (widen_lo(s) < 0.0f ? 0u : s & 0xffffu) | (widen_hi(s) < 0.0f ? 0u : s & 0xffff0000u);
-  }
-  __device__ __forceinline__ uint4 operator()(uint4 a, uint4 b) const {
-    return make_uint4((*this)(a.x, b.x), (*this)(a.y, b.y), (*this)(a.z, b.z), (*this)(a.w, b.w));
-  }
-};
-struct ThresholdBf16 {                             // (grad_out, out) -> grad: grad_out's bits or zero
-  __device__ __forceinline__ bf16_t operator()(bf16_t g, bf16_t o) const {
-    return widen(o) <= 0.0f ? (bf16_t)0 : g;       // NaN <= 0 is false: a NaN out passes the gradient
-  }
-  __device__ __forceinline__ unsigned operator()(unsigned g, unsigned o) const {
-    return (widen_lo(o) <= 0.0f ? 0u : g & 0xffffu) | (widen_hi(o) <= 0.0f ? 0u : g & 0xffff0000u);
-  }
-  __device__ __forceinline__ uint4 operator()(uint4 g, uint4 o) const {
-    return make_uint4((*this)(g.x, o.x), (*this)(g.y, o.y), (*this)(g.z, o.z), (*this)(g.w, o.w));
-  }
-};
-
-template <int V, typename Op>
-__global__ void __launch_bounds__(kThreads) binary_bf16_kernel(int n, int groups, int chunks,
-                                                                const bf16_t* __restrict__ p,
-                                                                const bf16_t* __restrict__ q,
-                                                                bf16_t* __restrict__ out) {
-  binary_body<V, typename Vec16<V>::type, Op>(n, groups, chunks, p, q, out);
 }
 
 // torch's mode='nearest' source index of destination index d
@@ -159,11 +138,10 @@ __device__ __forceinline__ int nearest_index(int d, int in, int out) {
   return min((int)floorf((float)d * scale), in - 1);
 }
 
-template <int V>
+template <typename T, int V>
 __global__ void __launch_bounds__(kThreads) upsample_add_kernel(int Hin, int Win, int Hout, int Wout, int chunks,
-                                                                 int units, const float* __restrict__ dst,
-                                                                 const float* __restrict__ src,
-                                                                 float* __restrict__ out) {
+                                                                 int units, const T* __restrict__ dst,
+                                                                 const T* __restrict__ src, T* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   int* tab_y = reinterpret_cast<int*>(lds_raw);    // [0, Hout): source row times Win; [Hout, Hout + Wout): source column
   int* tab_x = tab_y + Hout;
@@ -171,62 +149,30 @@ __global__ void __launch_bounds__(kThreads) upsample_add_kernel(int Hin, int Win
     tab_y[i] = i < Hout ? nearest_index(i, Hin, Hout) * Win : nearest_index(i - Hout, Win, Wout);
   }
   __syncthreads();
-  using VT = typename Vec<V>::type;
   const int P = Hout * Wout, Pin = Hin * Win;
   const Walk<V> walk(Wout);
   for (int u = blockIdx.x; u < units; u += gridDim.x) {
     const int plane = u / chunks, chunk = u - plane * chunks;
     const int first = walk.first(chunk);
-    const float* d = dst + (size_t)plane * P;
-    const float* s = src + (size_t)plane * Pin;
-    float* o = out + (size_t)plane * P;
-    walk.groups(first, P, [&](int idx, int y, int x) {
-      const VT dv = *reinterpret_cast<const VT*>(d + idx);
-      float v[V];
-      walk.values(v, y, x, [&](int yy, int xx) { return s[tab_y[yy] + tab_x[xx]]; });
-      if constexpr (V == 4) {
-        *reinterpret_cast<float4*>(o + idx) = make_float4(dv.x + v[0], dv.y + v[1], dv.z + v[2], dv.w + v[3]);
-      } else {
-        o[idx] = dv + v[0];
-      }
-    });
-  }
-}
-
-// the same walk over bf16 planes: V = 8 is one 16-byte access of four words
-template <int V>
-__global__ void __launch_bounds__(kThreads) upsample_add_bf16_kernel(int Hin, int Win, int Hout, int Wout, int chunks,
-                                                                      int units, const bf16_t* __restrict__ dst,
-                                                                      const bf16_t* __restrict__ src,
-                                                                      bf16_t* __restrict__ out) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-  int* tab_y = reinterpret_cast<int*>(lds_raw);    // as in upsample_add_kernel
-  int* tab_x = tab_y + Hout;
-  for (int i = threadIdx.x; i < Hout + Wout; i += kThreads) {
-    tab_y[i] = i < Hout ? nearest_index(i, Hin, Hout) * Win : nearest_index(i - Hout, Win, Wout);
-  }
-  __syncthreads();
-  const int P = Hout * Wout, Pin = Hin * Win;
-  const Walk<V> walk(Wout);
-  for (int u = blockIdx.x; u < units; u += gridDim.x) {
-    const int plane = u / chunks, chunk = u - plane * chunks;
-    const int first = walk.first(chunk);
-    const bf16_t* d = dst + (size_t)plane * P;
-    const bf16_t* s = src + (size_t)plane * Pin;
-    bf16_t* o = out + (size_t)plane * P;
+    const T* d = dst + (size_t)plane * P;
+    const T* s = src + (size_t)plane * Pin;
+    T* o = out + (size_t)plane * P;
     walk.groups(first, P, [&](int idx, int y, int x) {
       float v[V];
-      if constexpr (V == 8) {
+      if constexpr (V == 8) {                      // word by word: timed faster than adding in a widened group
         const uint4 dv = *reinterpret_cast<const uint4*>(d + idx);
-        walk.values(v, y, x, [&](int yy, int xx) { return widen(s[tab_y[yy] + tab_x[xx]]); });
+        walk.values(v, y, x, [&](int yy, int xx) { return load_f32(s + (tab_y[yy] + tab_x[xx])); });
         *reinterpret_cast<uint4*>(o + idx) = make_uint4(round_pair(widen_lo(dv.x) + v[0], widen_hi(dv.x) + v[1]),
                                                         round_pair(widen_lo(dv.y) + v[2], widen_hi(dv.y) + v[3]),
                                                         round_pair(widen_lo(dv.z) + v[4], widen_hi(dv.z) + v[5]),
                                                         round_pair(widen_lo(dv.w) + v[6], widen_hi(dv.w) + v[7]));
       } else {
-        const bf16_t dv = d[idx];
-        walk.values(v, y, x, [&](int yy, int xx) { return widen(s[tab_y[yy] + tab_x[xx]]); });
-        o[idx] = round_one(widen(dv) + v[0]);
+        float dv[V];
+        load_group<V>(d + idx, dv);
+        walk.values(v, y, x, [&](int yy, int xx) { return load_f32(s + (tab_y[yy] + tab_x[xx])); });
+#pragma unroll
+        for (int k = 0; k < V; ++k) v[k] = dv[k] + v[k];
+        store_group<V>(o + idx, v);
       }
     });
   }
@@ -243,8 +189,9 @@ __device__ __forceinline__ void build_starts(int* start, int in, int out) {
 }
 
 template <typename T>
-__device__ __forceinline__ void upsample_add_backward_body(int Hin, int Win, int Hout, int Wout, int total,
-                                                           const T* __restrict__ grad_out, T* __restrict__ grad_src) {
+__global__ void __launch_bounds__(kThreads) upsample_add_backward_kernel(int Hin, int Win, int Hout, int Wout,
+                                                                          int total, const T* __restrict__ grad_out,
+                                                                          T* __restrict__ grad_src) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   int* start_y = reinterpret_cast<int*>(lds_raw);  // Hin + 1 entries
   int* start_x = start_y + Hin + 1;                // Win + 1 entries
@@ -262,49 +209,34 @@ __device__ __forceinline__ void upsample_add_backward_body(int Hin, int Win, int
       const T* row = g + oy * Wout;
       for (int ox = x0; ox < x1; ++ox) acc += load_f32(row + ox);
     }
-    store_f32(grad_src + i, acc);
+    store_f32(grad_src + i, acc);                  // bf16: the one rounding
   }
 }
 
-__global__ void __launch_bounds__(kThreads) upsample_add_backward_kernel(int Hin, int Win, int Hout, int Wout,
-                                                                          int total,
-                                                                          const float* __restrict__ grad_out,
-                                                                          float* __restrict__ grad_src) {
-  upsample_add_backward_body(Hin, Win, Hout, Wout, total, grad_out, grad_src);
-}
-
-__global__ void __launch_bounds__(kThreads) upsample_add_backward_bf16_kernel(int Hin, int Win, int Hout, int Wout,
-                                                                               int total,
-                                                                               const bf16_t* __restrict__ grad_out,
-                                                                               bf16_t* __restrict__ grad_src) {
-  upsample_add_backward_body(Hin, Win, Hout, Wout, total, grad_out, grad_src);
-}
-
-// `wide`: the kernel with groups of kWide elements (16 bytes), `narrow`: the same with one element per access
-template <int kWide, typename T, typename Kernel>
-int launch_binary(int kernel_id, Kernel wide, Kernel narrow, long long n, const T* p, const T* q, T* out,
-                  ocrf_stream_t stream) {
+// the wide form (groups of kWide<T> elements, 16 bytes) when every pointer allows it, else one element per access
+template <typename Op, typename T>
+int binary(int kernel_id, long long n, const T* p, const T* q, T* out, ocrf_stream_t stream) {
   // every operand below 2 GiB: the kernels index with int
   if (n <= 0 || n * (long long)sizeof(T) >= kTwoGiB) return (int)hipErrorInvalidValue;
   if (!p || !q || !out) return (int)hipErrorInvalidValue;
   const bool vec = aligned16(p) && aligned16(q) && aligned16(out);
-  const int V = vec ? kWide : 1;
+  const int V = vec ? kWide<T> : 1;
   const int groups = (int)(n / V);
   const int per_chunk = kThreads * kGroups;
   const int chunks = (groups + per_chunk - 1) / per_chunk;         // 0 for n < V on the wide path: the tail lanes alone
   const unsigned grid = capped_grid(chunks < 1 ? 1 : chunks);
   if (vec) {
-    ocrf::launch(kernel_id, wide, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, (int)n, groups, chunks, p, q, out);
+    ocrf::launch(kernel_id, binary_kernel<T, kWide<T>, Op>, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, (int)n,
+                 groups, chunks, p, q, out);
   } else {
-    ocrf::launch(kernel_id, narrow, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, (int)n, groups, chunks, p, q,
-                 out);
+    ocrf::launch(kernel_id, binary_kernel<T, 1, Op>, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, (int)n, groups,
+                 chunks, p, q, out);
   }
   return (int)hipGetLastError();
 }
 
 // the shapes the upsample_add entry points accept; *P / *Pin: elements (of elem_bytes) per destination / source plane
-bool shapes_ok(int B, int C, int Hin, int Win, int Hout, int Wout, long long* P, long long* Pin,
-               long long elem_bytes = sizeof(float)) {
+bool shapes_ok(int B, int C, int Hin, int Win, int Hout, int Wout, long long elem_bytes, long long* P, long long* Pin) {
   if (B <= 0 || C <= 0 || Hin <= 0 || Win <= 0 || Hout < Hin || Wout < Win) return false;
   if (!planes_ok((long long)B * C, Hout, Wout, elem_bytes)) return false;
   *P = (long long)Hout * Wout;
@@ -312,94 +244,82 @@ bool shapes_ok(int B, int C, int Hin, int Win, int Hout, int Wout, long long* P,
   return true;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ocrf_add_relu_forward(long long n, const float* a, const float* b, float* out, ocrf_stream_t stream) {
-  return launch_binary<4>(OCRF_K_ADD_RELU, binary_kernel<4, AddRelu>, binary_kernel<1, AddRelu>, n, a, b, out, stream);
-}
-
-int ocrf_add_relu_backward(long long n, const float* grad_out, const float* out, float* grad, ocrf_stream_t stream) {
-  return launch_binary<4>(OCRF_K_ADD_RELU_BWD, binary_kernel<4, Threshold>, binary_kernel<1, Threshold>, n, grad_out, out,
-                          grad, stream);
-}
-
-int ocrf_upsample_add_forward(int B, int C, int Hin, int Win, int Hout, int Wout, const float* dst, const float* src,
-                              float* out, ocrf_stream_t stream) {
+template <typename T>
+int upsample_add_forward(int kernel_id, int B, int C, int Hin, int Win, int Hout, int Wout, const T* dst, const T* src,
+                         T* out, ocrf_stream_t stream) {
   long long P, Pin;
-  if (!shapes_ok(B, C, Hin, Win, Hout, Wout, &P, &Pin)) return (int)hipErrorInvalidValue;
+  if (!shapes_ok(B, C, Hin, Win, Hout, Wout, sizeof(T), &P, &Pin)) return (int)hipErrorInvalidValue;
   if (!dst || !src || !out) return (int)hipErrorInvalidValue;
+  constexpr int W = kWide<T>;
   const size_t lds = (size_t)(Hout + Wout) * sizeof(int);
-  const bool vec = P % 4 == 0 && aligned16(dst) && aligned16(out);
-  const Units n = units_of((long long)B * C, P, vec ? 4 : 1);
+  const bool vec = P % W == 0 && aligned16(dst) && aligned16(out);
+  const Units n = units_of((long long)B * C, P, vec ? W : 1);
   if (n.units >= kTwoGiB) return (int)hipErrorInvalidValue;
   if (vec) {
-    ocrf::launch(OCRF_K_UPSAMPLE_ADD, upsample_add_kernel<4>, dim3(n.grid), dim3(kThreads), lds, (hipStream_t)stream,
-                 Hin, Win, Hout, Wout, n.chunks, (int)n.units, dst, src, out);
+    ocrf::launch(kernel_id, upsample_add_kernel<T, W>, dim3(n.grid), dim3(kThreads), lds, (hipStream_t)stream, Hin, Win,
+                 Hout, Wout, n.chunks, (int)n.units, dst, src, out);
   } else {
-    ocrf::launch(OCRF_K_UPSAMPLE_ADD, upsample_add_kernel<1>, dim3(n.grid), dim3(kThreads), lds, (hipStream_t)stream,
-                 Hin, Win, Hout, Wout, n.chunks, (int)n.units, dst, src, out);
+    ocrf::launch(kernel_id, upsample_add_kernel<T, 1>, dim3(n.grid), dim3(kThreads), lds, (hipStream_t)stream, Hin, Win,
+                 Hout, Wout, n.chunks, (int)n.units, dst, src, out);
   }
   return (int)hipGetLastError();
 }
 
-int ocrf_upsample_add_backward(int B, int C, int Hin, int Win, int Hout, int Wout, const float* grad_out,
-                               float* grad_src, ocrf_stream_t stream) {
+template <typename T>
+int upsample_add_backward(int kernel_id, int B, int C, int Hin, int Win, int Hout, int Wout, const T* grad_out,
+                          T* grad_src, ocrf_stream_t stream) {
   long long P, Pin;
-  if (!shapes_ok(B, C, Hin, Win, Hout, Wout, &P, &Pin)) return (int)hipErrorInvalidValue;
+  if (!shapes_ok(B, C, Hin, Win, Hout, Wout, sizeof(T), &P, &Pin)) return (int)hipErrorInvalidValue;
   if (!grad_out || !grad_src) return (int)hipErrorInvalidValue;
   // Hin <= Hout and Win <= Wout (shapes_ok), so this is at most (kMaxAxisSum + 2) ints: within the forward's LDS limit
   const size_t lds = (size_t)(Hin + Win + 2) * sizeof(int);
   const long long total = (long long)B * C * Pin;                 // <= B C P < 2^29
   const unsigned grid = capped_grid((total + kThreads - 1) / kThreads);
-  ocrf::launch(OCRF_K_UPSAMPLE_ADD_BWD, upsample_add_backward_kernel, dim3(grid), dim3(kThreads), lds,
-               (hipStream_t)stream, Hin, Win, Hout, Wout, (int)total, grad_out, grad_src);
+  ocrf::launch(kernel_id, upsample_add_backward_kernel<T>, dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, Hin,
+               Win, Hout, Wout, (int)total, grad_out, grad_src);
   return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" {
+
+int ocrf_add_relu_forward(long long n, const float* a, const float* b, float* out, ocrf_stream_t stream) {
+  return binary<AddRelu>(OCRF_K_ADD_RELU, n, a, b, out, stream);
+}
+
+int ocrf_add_relu_backward(long long n, const float* grad_out, const float* out, float* grad, ocrf_stream_t stream) {
+  return binary<Threshold>(OCRF_K_ADD_RELU_BWD, n, grad_out, out, grad, stream);
+}
+
+int ocrf_upsample_add_forward(int B, int C, int Hin, int Win, int Hout, int Wout, const float* dst, const float* src,
+                              float* out, ocrf_stream_t stream) {
+  return upsample_add_forward(OCRF_K_UPSAMPLE_ADD, B, C, Hin, Win, Hout, Wout, dst, src, out, stream);
+}
+
+int ocrf_upsample_add_backward(int B, int C, int Hin, int Win, int Hout, int Wout, const float* grad_out,
+                               float* grad_src, ocrf_stream_t stream) {
+  return upsample_add_backward(OCRF_K_UPSAMPLE_ADD_BWD, B, C, Hin, Win, Hout, Wout, grad_out, grad_src, stream);
 }
 
 int ocrf_add_relu_forward_bf16(long long n, const unsigned short* a, const unsigned short* b, unsigned short* out,
                                ocrf_stream_t stream) {
-  return launch_binary<8>(OCRF_K_ADD_RELU_BF16, binary_bf16_kernel<8, AddReluBf16>, binary_bf16_kernel<1, AddReluBf16>, n,
-                          a, b, out, stream);
+  return binary<AddRelu>(OCRF_K_ADD_RELU_BF16, n, a, b, out, stream);
 }
 
 int ocrf_add_relu_backward_bf16(long long n, const unsigned short* grad_out, const unsigned short* out,
                                 unsigned short* grad, ocrf_stream_t stream) {
-  return launch_binary<8>(OCRF_K_ADD_RELU_BWD_BF16, binary_bf16_kernel<8, ThresholdBf16>,
-                          binary_bf16_kernel<1, ThresholdBf16>, n, grad_out, out, grad, stream);
+  return binary<Threshold>(OCRF_K_ADD_RELU_BWD_BF16, n, grad_out, out, grad, stream);
 }
 
 int ocrf_upsample_add_forward_bf16(int B, int C, int Hin, int Win, int Hout, int Wout, const unsigned short* dst,
                                    const unsigned short* src, unsigned short* out, ocrf_stream_t stream) {
-  long long P, Pin;
-  if (!shapes_ok(B, C, Hin, Win, Hout, Wout, &P, &Pin, sizeof(bf16_t))) return (int)hipErrorInvalidValue;
-  if (!dst || !src || !out) return (int)hipErrorInvalidValue;
-  const size_t lds = (size_t)(Hout + Wout) * sizeof(int);
-  const bool vec = P % 8 == 0 && aligned16(dst) && aligned16(out);
-  const Units n = units_of((long long)B * C, P, vec ? 8 : 1);
-  if (n.units >= kTwoGiB) return (int)hipErrorInvalidValue;
-  if (vec) {
-    ocrf::launch(OCRF_K_UPSAMPLE_ADD_BF16, upsample_add_bf16_kernel<8>, dim3(n.grid), dim3(kThreads), lds,
-                 (hipStream_t)stream, Hin, Win, Hout, Wout, n.chunks, (int)n.units, dst, src, out);
-  } else {
-    ocrf::launch(OCRF_K_UPSAMPLE_ADD_BF16, upsample_add_bf16_kernel<1>, dim3(n.grid), dim3(kThreads), lds,
-                 (hipStream_t)stream, Hin, Win, Hout, Wout, n.chunks, (int)n.units, dst, src, out);
-  }
-  return (int)hipGetLastError();
+  return upsample_add_forward(OCRF_K_UPSAMPLE_ADD_BF16, B, C, Hin, Win, Hout, Wout, dst, src, out, stream);
 }
 
 int ocrf_upsample_add_backward_bf16(int B, int C, int Hin, int Win, int Hout, int Wout, const unsigned short* grad_out,
                                     unsigned short* grad_src, ocrf_stream_t stream) {
-  long long P, Pin;
-  if (!shapes_ok(B, C, Hin, Win, Hout, Wout, &P, &Pin, sizeof(bf16_t))) return (int)hipErrorInvalidValue;
-  if (!grad_out || !grad_src) return (int)hipErrorInvalidValue;
-  const size_t lds = (size_t)(Hin + Win + 2) * sizeof(int);       // as in ocrf_upsample_add_backward
-  const long long total = (long long)B * C * Pin;
-  const unsigned grid = capped_grid((total + kThreads - 1) / kThreads);
-  ocrf::launch(OCRF_K_UPSAMPLE_ADD_BWD_BF16, upsample_add_backward_bf16_kernel, dim3(grid), dim3(kThreads), lds,
-               (hipStream_t)stream, Hin, Win, Hout, Wout, (int)total, grad_out, grad_src);
-  return (int)hipGetLastError();
+  return upsample_add_backward(OCRF_K_UPSAMPLE_ADD_BWD_BF16, B, C, Hin, Win, Hout, Wout, grad_out, grad_src, stream);
 }
 
 }  // extern "C"

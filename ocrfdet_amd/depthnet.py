@@ -167,15 +167,15 @@ def _split(metas):
     prev, curr = metas['cv_feat_list']
     D, H, W, _ = metas['frustum'].shape
     B, N, _ = metas['post_trans'].shape
-    return prev.reshape(B * N, -1, H, W), curr.reshape(B * N, -1, H, W), D, H, W
+    prev, curr = prev.reshape(B * N, -1, H, W), curr.reshape(B * N, -1, H, W)
+    return prev, curr, B * N, curr.shape[1], D, H, W
 
 
 def stereo_cost_volume_torch(metas, bias, raw=False):
     """Torch formulation: per group of 4 channels one ``grid_sample`` (align_corners, zeros padding) of ``prev`` and
     the absolute difference to ``curr`` summed over the group, the group sums added; ``bias`` where the warp of
     channel 4 (C // 4 - 1) is exactly 0.  Returns softmax_D(raw), or raw = -(cost + bias [warp == 0])."""
-    prev, curr, D, H, W = _split(metas)
-    BN, C = curr.shape[:2]
+    prev, curr, BN, C, D, H, W = _split(metas)
     G = C // GROUP
     if G < 1:
         raise ValueError(f'the stereo cost volume needs at least {GROUP} channels, got {C}')
@@ -192,28 +192,38 @@ def stereo_cost_volume_torch(metas, bias, raw=False):
     return raw_cost if raw else raw_cost.softmax(1)
 
 
-def stereo_cost_volume_hip(metas, bias, raw=False):
-    """``stereo_cost_volume_torch`` by ``ocrf_stereo_cost_volume``: one launch, forward only, deterministic.  The
-    frustum axes are passed as strided views of ``metas['frustum']``; the small calibration tensors are moved to the
-    features' device if they are elsewhere."""
-    prev, curr, D, H, W = _split(metas)
-    BN, C = curr.shape[:2]
+def _checked_split(metas):
+    """``_split`` for features that both kernels take: one channel count, a group or more."""
+    prev, curr, BN, C, D, H, W = _split(metas)
     if C < GROUP or prev.shape[1] != C:
         raise ValueError(f'stereo features must have the same channel count >= {GROUP}: {prev.shape} vs {curr.shape}')
-    if C * H * W * 4 > PLANE_BYTES_MAX or D * H * W >= 2 ** 31:
-        raise ValueError(f'stereo cost volume: C * H * W * 4 = {C * H * W * 4} bytes per camera must be at most '
-                         f'2^32 - 1 (32-bit plane addressing) and D * H * W = {D * H * W} below 2^31')
-    _lib.require_cuda(prev, curr)
+    return prev, curr, BN, C, D, H, W
+
+
+def _launch_cost_volume(entry, metas, bias, raw, prev, curr, BN, C, D, H, W):
+    """One launch of ``entry`` on the features as its kernel reads them.  The frustum axes are passed as strided views of
+    ``metas['frustum']``; the small calibration tensors are moved to the features' device if they are elsewhere."""
     dev = curr.device
-    prev, curr = prev.detach().float().contiguous(), curr.detach().float().contiguous()
     cal = [metas[k].detach().to(dev, torch.float32).reshape(BN, -1).contiguous()
            for k in ('k2s_sensor', 'intrins', 'post_rots', 'post_trans')]
     fr = metas['frustum'].detach().to(dev, torch.float32)
     u, v, d = fr[0, 0, :, 0], fr[0, :, 0, 1], fr[:, 0, 0, 2]
     out = torch.empty(BN, D, H, W, device=dev)
-    _lib.launch('ocrf_stereo_cost_volume', dev, BN, C, H, W, D, prev, curr, u, u.stride(0), v, v.stride(0), d, d.stride(0),
-                *cal, float(bias), 1 if raw else 0, out)
+    _lib.launch(entry, dev, BN, C, H, W, D, prev, curr, u, u.stride(0), v, v.stride(0), d, d.stride(0), *cal,
+                float(bias), 1 if raw else 0, out)
     return out
+
+
+def stereo_cost_volume_hip(metas, bias, raw=False):
+    """``stereo_cost_volume_torch`` by ``ocrf_stereo_cost_volume``: one launch, forward only, deterministic, on the
+    features cast to float32."""
+    prev, curr, BN, C, D, H, W = _checked_split(metas)
+    if C * H * W * 4 > PLANE_BYTES_MAX or D * H * W >= 2 ** 31:
+        raise ValueError(f'stereo cost volume: C * H * W * 4 = {C * H * W * 4} bytes per camera must be at most '
+                         f'2^32 - 1 (32-bit plane addressing) and D * H * W = {D * H * W} below 2^31')
+    _lib.require_cuda(prev, curr)
+    prev, curr = prev.detach().float().contiguous(), curr.detach().float().contiguous()
+    return _launch_cost_volume('ocrf_stereo_cost_volume', metas, bias, raw, prev, curr, BN, C, D, H, W)
 
 
 def packed_blocks(C):
@@ -270,10 +280,7 @@ def stereo_cost_volume_hip_bf16(metas, bias, raw=False):
     ``metas['cv_feat_packed'] = [prev_packed | None, curr_packed | None]`` (optional): features the caller has packed
     already (``stereo_pack_bf16``; a streaming step keeps the previous frame's).  An entry that is given is not packed
     again; one of another shape, dtype or device raises ``ValueError`` before anything is launched."""
-    prev, curr, D, H, W = _split(metas)
-    BN, C = curr.shape[:2]
-    if C < GROUP or prev.shape[1] != C:
-        raise ValueError(f'stereo features must have the same channel count >= {GROUP}: {prev.shape} vs {curr.shape}')
+    prev, curr, BN, C, D, H, W = _checked_split(metas)
     if prev.dtype != torch.bfloat16 or curr.dtype != torch.bfloat16:
         raise ValueError(f'stereo_cost_volume_hip_bf16 takes bfloat16 features, got {prev.dtype} and {curr.dtype}')
     packed = packed_blocks(C) * H * W * PACK * 2
@@ -288,16 +295,8 @@ def stereo_cost_volume_hip_bf16(metas, bias, raw=False):
     given = [None if e is None else _checked_packed(e, name, x, BN, C, H, W)
              for e, name, x in zip(given, ('prev', 'curr'), (prev, curr))]
     _lib.require_cuda(prev, curr)
-    dev = curr.device
     prev, curr = (stereo_pack_bf16(x) if e is None else e for e, x in zip(given, (prev, curr)))
-    cal = [metas[k].detach().to(dev, torch.float32).reshape(BN, -1).contiguous()
-           for k in ('k2s_sensor', 'intrins', 'post_rots', 'post_trans')]
-    fr = metas['frustum'].detach().to(dev, torch.float32)
-    u, v, d = fr[0, 0, :, 0], fr[0, :, 0, 1], fr[:, 0, 0, 2]
-    out = torch.empty(BN, D, H, W, device=dev)
-    _lib.launch('ocrf_stereo_cost_volume_bf16', dev, BN, C, H, W, D, prev, curr, u, u.stride(0), v, v.stride(0), d,
-                d.stride(0), *cal, float(bias), 1 if raw else 0, out)
-    return out
+    return _launch_cost_volume('ocrf_stereo_cost_volume_bf16', metas, bias, raw, prev, curr, BN, C, D, H, W)
 
 
 def stereo_cost_volume(metas, bias, fused=True, raw=False, keep_bf16=False):

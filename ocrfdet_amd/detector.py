@@ -26,22 +26,12 @@ from torch import nn
 
 from . import _lib, temporal
 from .blocks import build
+from .temporal import _affine_inverse
 
 LOSS_KEYS_NECK = ('loss_depth', 'loss_ce_semantic', 'loss_gs_color', 'loss_gs_ssim', 'loss_render_depth')
 
 
 # ------------------------------------------------------------------------------------------------ frame poses
-def _affine_inverse(m):
-    """Inverse of (..., 4, 4) float64 affine maps [R t; 0 0 0 1] in closed form: inv(R) from the adjugate, -inv(R) t."""
-    lead = m.shape[:-2]
-    rinv = temporal._inverse3(m[..., :3, :3].reshape(-1, 3, 3)).view(*lead, 3, 3)
-    t = -(rinv * m[..., None, :3, 3]).sum(-1)
-    top = torch.cat([rinv, t[..., None]], -1)
-    last = torch.zeros_like(m[..., 3:, :])
-    last[..., 0, 3] = 1.0
-    return torch.cat([top, last], -2)
-
-
 def mlp_input_torch(rots, trans, intrins, post_rots, post_trans, bda):
     """(F, B, N, 27): for every frame f what ``get_mlp_input(rots[:, 0], trans[:, 0], intrins[:, f], post_rots[:, f],
     post_trans[:, f], bda)`` returns (view_transformer.py:696-722), from (B, F, N, ...) inputs.  Copies only."""
@@ -125,6 +115,16 @@ def _frames(t):
     return list(t.unbind(1))
 
 
+def frame_split(inputs, num_frame):
+    """(B, N) of a 12-entry ``img_inputs`` whose images (B, N * num_frame, ...) are ``num_frame`` frames of N cameras."""
+    if len(inputs) != 12:
+        raise ValueError(f'img_inputs has 12 entries, got {len(inputs)}')
+    B, NF = inputs[0].shape[:2]
+    if NF % num_frame:
+        raise ValueError(f'{NF} images are not {num_frame} frames of the same cameras')
+    return B, NF // num_frame
+
+
 def prepare_inputs(inputs, num_frame, temporal_frame, extra_ref_frames, stereo=True, fused=True):
     """``BEVDet4D.prepare_inputs`` (bevdet.py:412-476) for the 12-entry ``img_inputs`` = (imgs (B, N * num_frame, C, H,
     W), rots, trans, intrins, post_rots, post_trans, bda, sensor2egos, ego2globals, imgs_wo_norm, imgs_wo_aug, c2w).
@@ -137,12 +137,8 @@ def prepare_inputs(inputs, num_frame, temporal_frame, extra_ref_frames, stereo=T
     * the list over the frames of ``mlp_input`` (B, N, 27), what ``extract_img_feat`` gets from ``get_mlp_input``.
 
     The poses come from ``frame_poses(..., fused=fused)``."""
-    if len(inputs) != 12:
-        raise ValueError(f'img_inputs has 12 entries, got {len(inputs)}')
-    B, N, C, H, W = inputs[0].shape
-    if N % num_frame:
-        raise ValueError(f'{N} images are not {num_frame} frames of the same cameras')
-    N = N // num_frame
+    B, N = frame_split(inputs, num_frame)
+    C, H, W = inputs[0].shape[2:]
     imgs = _frames(inputs[0].view(B, N, num_frame, C, H, W).transpose(1, 2))
     rots, trans, intrins, post_rots, post_trans, bda, sensor2egos, ego2globals = inputs[1:9]
     imgs_wo_norm = _frames(inputs[9].view(B, N, num_frame, 3, H, W).transpose(1, 2))
@@ -340,17 +336,41 @@ class OcRFDet4D(nn.Module):
         the step, the head and the decode run inside ``bf16_inference()``; the results are float32 as without it."""
         (img_feats, _, _), state = self.stream_step(img_inputs, state=state, new_sequence=new_sequence,
                                                     multi_frame=multi_frame, bf16=bf16)
-        if img_metas is None:
-            img_metas = [dict() for _ in range(img_inputs[0].shape[0])]
         with torch.no_grad(), (self.bf16_inference() if bf16 else contextlib.nullcontext()):
-            pts = self.simple_test_pts(img_feats, img_metas, rescale=rescale)
-        return [dict(pts_bbox=pts_bbox) for pts_bbox in pts], state
+            return self.pts_results(img_feats, img_metas, img_inputs[0].shape[0], rescale), state
+
+    # ---------------------------------------------------------------- what a subclass overrides
+    def frame_args(self, key_frame):
+        """Hook of the frame loop: the positional arguments of this class's ``prepare_bev_feat`` behind the sixteen of
+        ``OcRFDet4D``'s, for one frame.  What ``prepare_bev_feat`` returns behind its five results for the key frame
+        is returned behind ``extras`` by a training ``extract_img_feat`` and handed to ``losses_after_neck``."""
+        return ()
+
+    def losses_after_neck(self, *rest):
+        """Hook of ``forward_train``: the losses that go right behind the neck's five, from what a training
+        ``extract_img_feat`` returned behind ``extras``."""
+        return {}
+
+    def cat_history(self, bev_feat_list, sensor2keyegos=None, bda=None):
+        """The BEV encoder's input from the frames' BEV maps, oldest first, key frame last.  ``with_prev=False``: the
+        list holds the key frame alone, and the adjacent groups are zeros."""
+        if not self.with_prev:
+            key, n_adj = bev_feat_list[0], self.num_frame - self.extra_ref_frames - 1
+            zeros = key.new_zeros((key.shape[0], key.shape[1] * n_adj) + tuple(key.shape[2:]))
+            return torch.cat([zeros, key], dim=1)                # a warp of zeros is zeros: nothing to align
+        if self.align_after_view_transfromation:
+            vt = self.img_view_transformer
+            frame_ids = [self.num_frame - 2 - k for k in range(self.num_frame - 2)] + [0]
+            return temporal.align_and_cat(bev_feat_list, frame_ids, sensor2keyegos, bda, vt.grid_interval,
+                                          vt.grid_lower_bound, fused=self.fused_align)
+        return torch.cat(bev_feat_list, dim=1)
 
     # ---------------------------------------------------------------- ocrfdet.py:206-279
     def extract_img_feat(self, img, img_metas=None, pred_prev=False, sequential=False, **kwargs):
         """Frames ``num_frame - 1 ... 0``: the extra reference frame yields only the stereo feature, adjacent frames run
-        under ``no_grad``, the key frame with gradients; the BEV features are concatenated oldest first, key frame last.
-        Returns ``([x], depth, bev_mask, extras)`` in training and ``([x], depth, bev_mask)`` otherwise."""
+        under ``no_grad``, the key frame with gradients; the BEV features are concatenated oldest first, key frame last
+        (``cat_history``).  Returns ``([x], depth, bev_mask, extras, ...)`` in training, with whatever the class's
+        ``prepare_bev_feat`` returns behind ``extras``, and ``([x], depth, bev_mask)`` otherwise."""
         if sequential:
             return self.extract_img_feat_sequential(img, **kwargs)
         if pred_prev:
@@ -358,7 +378,6 @@ class OcRFDet4D(nn.Module):
         (imgs, rots, trans, intrins, post_rots, post_trans, bda, sensor2keyegos, ego2globals, curr2adjsensor,
          imgs_wo_norm, imgs_wo_aug, c2ws), mlp_inputs = self.prepare_inputs(img, stereo=True)
         bev_feat_list = []
-        depth_key_frame = bev_mask_key_frame = extras = None
         feat_prev_iv = None
         for fid in range(self.num_frame - 1, -1, -1):
             key_frame = fid == 0
@@ -370,30 +389,18 @@ class OcRFDet4D(nn.Module):
                 sensor2keyego, ego2global = sensor2keyegos[0], ego2globals[0]
             inputs_curr = (imgs[fid], rots[fid], trans[fid], sensor2keyego, ego2global, intrins[fid], post_rots[fid],
                            post_trans[fid], bda, mlp_inputs[fid], feat_prev_iv, curr2adjsensor[fid], extra_ref_frame,
-                           imgs_wo_norm[fid], imgs_wo_aug[fid], c2ws[fid])
+                           imgs_wo_norm[fid], imgs_wo_aug[fid], c2ws[fid], *self.frame_args(key_frame))
             if key_frame:
-                bev_feat, depth_key_frame, bev_mask_key_frame, feat_curr_iv, extras = self.prepare_bev_feat(*inputs_curr)
+                bev_feat, depth_key_frame, bev_mask_key_frame, feat_curr_iv, *rest = self.prepare_bev_feat(*inputs_curr)
             else:
                 with torch.no_grad():
-                    bev_feat, _, _, feat_curr_iv, _ = self.prepare_bev_feat(*inputs_curr)
+                    bev_feat, _, _, feat_curr_iv, *_ = self.prepare_bev_feat(*inputs_curr)
             if not extra_ref_frame:
                 bev_feat_list.append(bev_feat)
             feat_prev_iv = feat_curr_iv
-        n_adj = self.num_frame - self.extra_ref_frames - 1
-        if not self.with_prev:
-            key = bev_feat_list[0]
-            zeros = key.new_zeros((key.shape[0], key.shape[1] * n_adj) + tuple(key.shape[2:]))
-            bev_feat = torch.cat([zeros, key], dim=1)            # a warp of zeros is zeros: nothing to align
-        elif self.align_after_view_transfromation:
-            vt = self.img_view_transformer
-            frame_ids = [self.num_frame - 2 - k for k in range(self.num_frame - 2)] + [0]
-            bev_feat = temporal.align_and_cat(bev_feat_list, frame_ids, sensor2keyegos, bda, vt.grid_interval,
-                                              vt.grid_lower_bound, fused=self.fused_align)
-        else:
-            bev_feat = torch.cat(bev_feat_list, dim=1)
-        x = self.bev_encoder(bev_feat)
+        x = self.bev_encoder(self.cat_history(bev_feat_list, sensor2keyegos, bda))
         if self.training:
-            return [x], depth_key_frame, bev_mask_key_frame, extras
+            return [x], depth_key_frame, bev_mask_key_frame, *rest
         return [x], depth_key_frame, bev_mask_key_frame
 
     def extract_feat(self, points, img, img_metas=None, **kwargs):
@@ -410,7 +417,8 @@ class OcRFDet4D(nn.Module):
     def forward_train(self, points=None, img_metas=None, gt_bboxes_3d=None, gt_labels_3d=None, gt_labels=None,
                       gt_bboxes=None, img_inputs=None, proposals=None, gt_bboxes_ignore=None, **kwargs):
         gt_depth, gt_semantic, gt_bev_mask = kwargs.pop('gt_depth'), kwargs.pop('gt_semantic'), kwargs.pop('gt_bev_mask')
-        img_feats, _, depth, bev_mask, extras = self.extract_feat(points, img=img_inputs, img_metas=img_metas, **kwargs)
+        img_feats, _, depth, bev_mask, extras, *rest = self.extract_feat(points, img=img_inputs, img_metas=img_metas,
+                                                                         **kwargs)
         (render_imgs, gt_images, render_image_G_all, render_image_N_all, opacity_alpha_view, cam_idx_list, render_depth,
          render_depth_G_all, render_depth_N_all) = extras
         vt = self.img_view_transformer
@@ -418,6 +426,7 @@ class OcRFDet4D(nn.Module):
                              render_image_G_all, render_image_N_all, render_depth, render_depth_G_all,
                              render_depth_N_all)
         losses = dict(zip(LOSS_KEYS_NECK, values))
+        losses.update(self.losses_after_neck(*rest))
         if opacity_alpha_view is not None:
             losses.update(vt.prob.get_bev_opacity_loss(gt_bev_mask, opacity_alpha_view.squeeze(1)))
         losses.update(vt.prob.get_bev_mask_loss(gt_bev_mask, bev_mask[0]))
@@ -431,14 +440,19 @@ class OcRFDet4D(nn.Module):
         return [dict(boxes_3d=boxes.to('cpu'), scores_3d=scores.cpu(), labels_3d=labels.cpu())
                 for boxes, scores, labels in bbox_list]
 
+    def pts_results(self, img_feats, img_metas, B, rescale):
+        """The result of ``simple_test`` / ``simple_test_stream`` for B samples: ``img_metas`` None is one empty dict
+        per sample, and every sample's ``simple_test_pts`` dict goes under ``pts_bbox``."""
+        if img_metas is None:
+            img_metas = [dict() for _ in range(B)]
+        return [dict(pts_bbox=pts_bbox) for pts_bbox in self.simple_test_pts(img_feats, img_metas, rescale=rescale)]
+
     def simple_test(self, points=None, img_metas=None, img=None, rescale=False, img_inputs=None, **kwargs):
         """ocrfdet.py:48-63: a list over the samples of ``dict(pts_bbox=dict(boxes_3d, scores_3d, labels_3d))``.
         ``img_metas``: a list of per-sample dicts, or None (then one empty dict per sample)."""
         img = img_inputs if img is None else img
         img_feats = self.extract_feat(points, img=img, img_metas=img_metas, **kwargs)[0]
-        if img_metas is None:
-            img_metas = [dict() for _ in range(img[0].shape[0])]
-        return [dict(pts_bbox=pts_bbox) for pts_bbox in self.simple_test_pts(img_feats, img_metas, rescale=rescale)]
+        return self.pts_results(img_feats, img_metas, img[0].shape[0], rescale)
 
     def forward_dummy(self, points=None, img_metas=None, img_inputs=None, **kwargs):
         img_feats = self.extract_feat(points, img=img_inputs, img_metas=img_metas, **kwargs)[0]
@@ -540,77 +554,15 @@ class OcRFDet4DVGGT(OcRFDet4D):
                                                              imgs_wo_aug, c2w)
         return bev_feat, depth, bev_mask, stereo_feat, extras, F_ts
 
-    # ---------------------------------------------------------------- ocrfdet_vggt.py:328-401
-    def extract_img_feat(self, img, img_metas=None, pred_prev=False, sequential=False, **kwargs):
-        """``OcRFDet4D.extract_img_feat`` with the key frame marked for ``prepare_bev_feat``; in training the result
-        carries ``F_ts = [cost_volume_t, cost_volume_s]`` as a last element."""
-        if sequential:
-            return self.extract_img_feat_sequential(img, **kwargs)
-        if pred_prev:
-            raise NotImplementedError('pred_prev: the reference asserts False here')
-        (imgs, rots, trans, intrins, post_rots, post_trans, bda, sensor2keyegos, ego2globals, curr2adjsensor,
-         imgs_wo_norm, imgs_wo_aug, c2ws), mlp_inputs = self.prepare_inputs(img, stereo=True)
-        bev_feat_list = []
-        depth_key_frame = bev_mask_key_frame = extras = F_ts = None
-        feat_prev_iv = None
-        for fid in range(self.num_frame - 1, -1, -1):
-            key_frame = fid == 0
-            extra_ref_frame = fid == self.num_frame - self.extra_ref_frames
-            if not (key_frame or self.with_prev):
-                continue
-            sensor2keyego, ego2global = sensor2keyegos[fid], ego2globals[fid]
-            if self.align_after_view_transfromation:
-                sensor2keyego, ego2global = sensor2keyegos[0], ego2globals[0]
-            inputs_curr = (imgs[fid], rots[fid], trans[fid], sensor2keyego, ego2global, intrins[fid], post_rots[fid],
-                           post_trans[fid], bda, mlp_inputs[fid], feat_prev_iv, curr2adjsensor[fid], extra_ref_frame,
-                           imgs_wo_norm[fid], imgs_wo_aug[fid], c2ws[fid], key_frame)
-            if key_frame:
-                bev_feat, depth_key_frame, bev_mask_key_frame, feat_curr_iv, extras, F_ts = \
-                    self.prepare_bev_feat(*inputs_curr)
-            else:
-                with torch.no_grad():
-                    bev_feat, _, _, feat_curr_iv, _, _ = self.prepare_bev_feat(*inputs_curr)
-            if not extra_ref_frame:
-                bev_feat_list.append(bev_feat)
-            feat_prev_iv = feat_curr_iv
-        n_adj = self.num_frame - self.extra_ref_frames - 1
-        if not self.with_prev:
-            key = bev_feat_list[0]
-            zeros = key.new_zeros((key.shape[0], key.shape[1] * n_adj) + tuple(key.shape[2:]))
-            bev_feat = torch.cat([zeros, key], dim=1)
-        elif self.align_after_view_transfromation:
-            vt = self.img_view_transformer
-            frame_ids = [self.num_frame - 2 - k for k in range(self.num_frame - 2)] + [0]
-            bev_feat = temporal.align_and_cat(bev_feat_list, frame_ids, sensor2keyegos, bda, vt.grid_interval,
-                                              vt.grid_lower_bound, fused=self.fused_align)
-        else:
-            bev_feat = torch.cat(bev_feat_list, dim=1)
-        x = self.bev_encoder(bev_feat)
-        if self.training:
-            return [x], depth_key_frame, bev_mask_key_frame, extras, F_ts
-        return [x], depth_key_frame, bev_mask_key_frame
+    # ---------------------------------------------------------------- ocrfdet_vggt.py:328-401, 436-498
+    def frame_args(self, key_frame):
+        """The key frame is marked for ``prepare_bev_feat``, whose sixth result, ``F_ts = [cost_volume_t,
+        cost_volume_s]``, a training ``extract_img_feat`` therefore returns as its last element."""
+        return (key_frame,)
 
-    # ---------------------------------------------------------------- ocrfdet_vggt.py:436-498
-    def forward_train(self, points=None, img_metas=None, gt_bboxes_3d=None, gt_labels_3d=None, gt_labels=None,
-                      gt_bboxes=None, img_inputs=None, proposals=None, gt_bboxes_ignore=None, **kwargs):
-        """``OcRFDet4D.forward_train``'s dict with ``loss_Smoothl1_KD`` and ``loss_cos_KD`` after the neck's five, where
-        the reference puts them."""
+    def losses_after_neck(self, F_ts):
+        """``loss_Smoothl1_KD`` and ``loss_cos_KD``, where the reference puts them.  The reference calls
+        ``smooth_l1_loss(F_ts[0], F_ts[1])``: both losses are symmetric in their operands, and the student's volume,
+        ``F_ts[1]``, is the one a gradient flows into."""
         from .distill import kd_losses
-        gt_depth, gt_semantic, gt_bev_mask = kwargs.pop('gt_depth'), kwargs.pop('gt_semantic'), kwargs.pop('gt_bev_mask')
-        img_feats, _, depth, bev_mask, extras, F_ts = self.extract_feat(points, img=img_inputs, img_metas=img_metas,
-                                                                        **kwargs)
-        (render_imgs, gt_images, render_image_G_all, render_image_N_all, opacity_alpha_view, cam_idx_list, render_depth,
-         render_depth_G_all, render_depth_N_all) = extras
-        vt = self.img_view_transformer
-        values = vt.get_loss(depth, bev_mask[1], gt_depth, gt_semantic, gt_bboxes, cam_idx_list, render_imgs, gt_images,
-                             render_image_G_all, render_image_N_all, render_depth, render_depth_G_all,
-                             render_depth_N_all)
-        losses = dict(zip(LOSS_KEYS_NECK, values))
-        # the reference calls smooth_l1_loss(F_ts[0], F_ts[1]): both losses are symmetric in their operands, and the
-        # student's volume, F_ts[1], is the one a gradient flows into
-        losses.update(zip(LOSS_KEYS_KD, kd_losses(F_ts[1], F_ts[0], fused=self.fused_distill)))
-        if opacity_alpha_view is not None:
-            losses.update(vt.prob.get_bev_opacity_loss(gt_bev_mask, opacity_alpha_view.squeeze(1)))
-        losses.update(vt.prob.get_bev_mask_loss(gt_bev_mask, bev_mask[0]))
-        losses.update(self.forward_pts_train(img_feats, gt_bboxes_3d, gt_labels_3d, img_metas, gt_bboxes_ignore))
-        return losses
+        return dict(zip(LOSS_KEYS_KD, kd_losses(F_ts[1], F_ts[0], fused=self.fused_distill)))

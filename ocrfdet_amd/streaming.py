@@ -31,19 +31,14 @@ import contextlib
 import torch
 
 from . import depthnet, temporal
-from .detector import frame_poses
+from .detector import frame_poses, frame_split
 
 
 def key_frame_inputs(img_inputs, num_frame):
     """The 12-entry list of ONE frame from the multi-frame ``img_inputs`` (images (B, N * num_frame, C, H, W)
     camera-major, poses (B, num_frame * N, ...) frame-major): frame 0 of each entry, views as ``prepare_inputs`` makes
     them, ``bda`` as it is."""
-    if len(img_inputs) != 12:
-        raise ValueError(f'img_inputs has 12 entries, got {len(img_inputs)}')
-    B, NF = img_inputs[0].shape[:2]
-    if NF % num_frame:
-        raise ValueError(f'{NF} images are not {num_frame} frames of the same cameras')
-    N = NF // num_frame
+    B, N = frame_split(img_inputs, num_frame)
     image = lambda t: t.view(B, N, num_frame, *t.shape[2:])[:, :, 0]          # noqa: E731
     pose = lambda t: t.view(B, num_frame, N, *t.shape[2:])[:, 0]              # noqa: E731
     (imgs, rots, trans, intrins, post_rots, post_trans, bda, sensor2egos, ego2globals, imgs_wo_norm, imgs_wo_aug,
@@ -185,7 +180,7 @@ def stream_step(det, img_inputs, state=None, new_sequence=None, multi_frame=Fals
     K = det.num_frame - det.extra_ref_frames - 1
     with torch.no_grad(), (det.bf16_inference() if bf16 else contextlib.nullcontext()):
         if not det.with_prev:
-            return _step_without_history(det, img_inputs, K), None
+            return _step_without_history(det, img_inputs), None
         fresh = state is None or state.num_adj != K or state.ring is None or state.ring.shape[1] != B \
             or state.sensor2egos.shape != sensor2egos.shape or state.bf16 != bf16
         if fresh:
@@ -249,10 +244,10 @@ def stream_step(det, img_inputs, state=None, new_sequence=None, multi_frame=Fals
     return ([out], depth, bev_mask), state
 
 
-def _step_without_history(det, img_inputs, K):
+def _step_without_history(det, img_inputs):
     """``with_prev=False``: the batch forward skips every frame but the key frame, hands the view transformer no previous
-    stereo feature and fills the adjacent groups with zeros.  ``k2s_sensor`` is the key frame onto itself: the step knows
-    no other frame (the stereo DepthNet does not read it without a previous feature)."""
+    stereo feature and fills the adjacent groups with zeros (``det.cat_history``).  ``k2s_sensor`` is the key frame onto
+    itself: the step knows no other frame (the stereo DepthNet does not read it without a previous feature)."""
     (imgs, rots, trans, intrins, post_rots, post_trans, bda, sensor2egos, ego2globals, imgs_wo_norm, imgs_wo_aug,
      c2w) = img_inputs
     pair = lambda a: torch.stack([a, a], 1)                       # noqa: E731
@@ -261,5 +256,4 @@ def _step_without_history(det, img_inputs, K):
     x, stereo_feat = det.image_encoder(imgs, stereo=True)
     key, depth, bev_mask, _ = det.lift_to_bev(x, stereo_feat, imgs, rots, trans, intrins, post_rots, post_trans, bda,
                                                  mlp_input[0], None, curr2adj[:, 0], imgs_wo_norm, imgs_wo_aug, c2w)
-    zeros = key.new_zeros((key.shape[0], key.shape[1] * K) + tuple(key.shape[2:]))
-    return [det.bev_encoder(torch.cat([zeros, key], dim=1))], depth, bev_mask
+    return [det.bev_encoder(det.cat_history([key]))], depth, bev_mask

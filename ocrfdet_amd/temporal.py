@@ -61,6 +61,17 @@ def _inverse3(m):
     return cof.transpose(1, 2) / det[:, None, None]
 
 
+def _affine_inverse(m):
+    """Inverse of (..., 4, 4) float64 affine maps [R t; 0 0 0 1] in closed form: inv(R) from the adjugate, -inv(R) t."""
+    lead = m.shape[:-2]
+    rinv = _inverse3(m[..., :3, :3].reshape(-1, 3, 3)).view(*lead, 3, 3)
+    t = -(rinv * m[..., None, :3, 3]).sum(-1)
+    top = torch.cat([rinv, t[..., None]], -1)
+    last = torch.zeros_like(m[..., 3:, :])
+    last[..., 0, 3] = 1.0
+    return torch.cat([top, last], -2)
+
+
 def _pair(values, like):
     """The first two entries of ``grid_interval`` / ``grid_lower_bound`` as float64: Python floats from a sequence or
     a CPU tensor (the view transformer's attributes), 0-dim tensors of a device tensor (no host read)."""
@@ -173,10 +184,11 @@ def _gather_from(grad, tf32, shape):
     return grad_x
 
 
-def _sliceable(dst, like):
-    """``dst`` can take the warp of ``like``: same shape, dtype and device, contiguous (c, h, w) blocks."""
-    n, c, h, w = like.shape
-    return (dst.shape == like.shape and dst.dtype == like.dtype and dst.device == like.device
+def _sliceable(dst, shape, dtype, device):
+    """The ``out=`` contract: ``dst`` is an (n, c, h, w) = ``shape`` view of ``dtype`` on ``device`` with contiguous
+    (c, h, w) blocks, such as a channel slice of a wider concatenation."""
+    n, c, h, w = shape
+    return (tuple(dst.shape) == (n, c, h, w) and dst.dtype == dtype and dst.device == device
             and dst.stride()[1:] == (h * w, w, 1) and (n == 1 or dst.stride(0) >= c * h * w))
 
 
@@ -190,37 +202,25 @@ def _check_bf16_grad(grad_out):
 
 
 class _ShiftFeature(torch.autograd.Function):
-    @staticmethod
-    @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
-    def forward(ctx, input, tf32):
-        out = torch.empty_like(input)
-        _warp_into(input, tf32, out)
-        ctx.save_for_backward(tf32)
-        ctx.shape = tuple(input.shape)
-        return out
+    """The warp of a float32 or bfloat16 map, the result and the gradient in the map's dtype.
 
-    @staticmethod
-    @torch.amp.custom_bwd(device_type='cuda')
-    def backward(ctx, grad_out):
-        tf32, = ctx.saved_tensors
-        return _gather_from(grad_out.contiguous(), tf32, ctx.shape), None
-
-
-class _ShiftFeatureBf16(torch.autograd.Function):
-    """``_ShiftFeature`` on a bfloat16 map that stays bfloat16: no cast of the inputs, the ``_bf16`` kernels."""
+    No ``custom_fwd`` / ``custom_bwd``: ``shift_feature`` is the only caller and hands over a map it has cast already
+    (float32, or bfloat16 under ``keep_bf16``) and a float32 ``tf32``, so ``cast_inputs`` has nothing to cast; forward
+    and backward consist of ``empty``, ``contiguous`` and the library's launches, none of which autocast changes."""
 
     @staticmethod
     def forward(ctx, input, tf32):
         out = torch.empty_like(input)
         _warp_into(input, tf32, out)
         ctx.save_for_backward(tf32)
-        ctx.shape = tuple(input.shape)
+        ctx.shape, ctx.dtype = tuple(input.shape), input.dtype
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         tf32, = ctx.saved_tensors
-        _check_bf16_grad(grad_out)
+        if ctx.dtype == torch.bfloat16:
+            _check_bf16_grad(grad_out)
         return _gather_from(grad_out.contiguous(), tf32, ctx.shape), None
 
 
@@ -245,10 +245,10 @@ def shift_feature(input, tf, out=None, keep_bf16=False):
         input = _cast(input)
     tf32 = _tf32(tf, input)
     if out is None:
-        return (_ShiftFeatureBf16 if keep else _ShiftFeature).apply(input, tf32)
+        return _ShiftFeature.apply(input, tf32)
     if torch.is_grad_enabled() and input.requires_grad:
         raise _lib.OcrfHipError('shift_feature(out=...) records no gradient: detach the input, or use align_and_cat')
-    if not _sliceable(out, input):
+    if not _sliceable(out, input.shape, input.dtype, input.device):
         raise _lib.OcrfHipError(f'out must be a {"bfloat16" if keep else "float32"} (n, c, h, w) view with contiguous '
                                 '(c, h, w) blocks on the device of the input')
     _warp_into(input, tf32, out)
@@ -283,40 +283,24 @@ def _align_grads(ctx, grad_out):
 
 class _AlignCat(torch.autograd.Function):
     """``tfs[k]`` None: ``feats[k]`` is copied; else warped with it.  One launch per warped frame, each into its channels
-    of the result."""
+    of the result.  The maps are all float32 or all bfloat16; the concatenation and the gradients are of their dtype.
+
+    No ``custom_fwd`` / ``custom_bwd``, for ``_ShiftFeature``'s reason: ``align_and_cat`` is the only caller and casts
+    before ``apply``, and ``copy_``, slicing and the launches are not autocast's."""
 
     @staticmethod
-    @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
     def forward(ctx, tfs, *feats):
         B, C, H, W = feats[0].shape
-        out = torch.empty(B, len(feats) * C, H, W, dtype=torch.float32, device=feats[0].device)
+        out = torch.empty(B, len(feats) * C, H, W, dtype=feats[0].dtype, device=feats[0].device)
         _align_into(out, tfs, feats)
         ctx.tfs = tfs                                # float32 tensors without a gradient, none of them an input
-        ctx.shape = (B, C, H, W)
-        return out
-
-    @staticmethod
-    @torch.amp.custom_bwd(device_type='cuda')
-    def backward(ctx, grad_out):
-        return _align_grads(ctx, grad_out)
-
-
-class _AlignCatBf16(torch.autograd.Function):
-    """``_AlignCat`` on bfloat16 maps that stay bfloat16: no cast of the inputs, the ``_bf16`` kernels, a bfloat16
-    concatenation and bfloat16 gradients."""
-
-    @staticmethod
-    def forward(ctx, tfs, *feats):
-        B, C, H, W = feats[0].shape
-        out = torch.empty(B, len(feats) * C, H, W, dtype=torch.bfloat16, device=feats[0].device)
-        _align_into(out, tfs, feats)
-        ctx.tfs = tfs
-        ctx.shape = (B, C, H, W)
+        ctx.shape, ctx.dtype = (B, C, H, W), out.dtype
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        _check_bf16_grad(grad_out)
+        if ctx.dtype == torch.bfloat16:
+            _check_bf16_grad(grad_out)
         return _align_grads(ctx, grad_out)
 
 
@@ -358,8 +342,7 @@ def align_and_cat(feats, frame_ids, sensor2keyegos, bda, grid_interval, grid_low
     if (FUSED_ALIGN_DEFAULT if fused is None else fused) and align_fusable(feats, tfs):
         if not keep:
             feats = [_cast(x) for x in feats]
-        return (_AlignCatBf16 if keep else _AlignCat).apply(
-            tuple(None if tf is None else _tf32(tf, feats[0]) for tf in tfs), *feats)
+        return _AlignCat.apply(tuple(None if tf is None else _tf32(tf, feats[0]) for tf in tfs), *feats)
     if keep:
         return torch.cat([x if tf is None else _shift_feature_torch_bf16(x, tf) for x, tf in zip(feats, tfs)], dim=1)
     return torch.cat([x if tf is None else shift_feature_torch(_cast(x), tf) for x, tf in zip(feats, tfs)], dim=1)
@@ -381,9 +364,7 @@ def _check_stream_operands(ring, head, valid, sensor2ego0, ego2global0, bda, out
             raise ValueError(f'{name} is on {got[name].device}, the ring on {ring.device}')
     if valid.dtype.is_floating_point or valid.dtype == torch.bool:
         raise ValueError(f'valid must be an integer tensor, got {valid.dtype}')
-    if out is not None and not (tuple(out.shape) == (B, S * C, H, W) and out.dtype == ring.dtype
-                                and out.device == ring.device and out.stride()[1:] == (H * W, W, 1)
-                                and (B == 1 or out.stride(0) >= S * C * H * W)):
+    if out is not None and not _sliceable(out, (B, S * C, H, W), ring.dtype, ring.device):
         raise ValueError(f'out must be a {ring.dtype} (B, S * C, H, W) = ({B}, {S * C}, {H}, {W}) view with contiguous '
                          '(S * C, H, W) blocks on the device of the ring')
     return S, B, C, H, W
@@ -411,6 +392,7 @@ def stream_align_torch(ring, head, valid, sensor2ego0, ego2global0, bda, grid_in
     with torch.no_grad():
         rows = torch.arange(B, device=dev)
         e2g, s2e = ego2global0.double(), sensor2ego0.double()
+        # not _affine_inverse: its -(rinv * t).sum(-1) and this einsum differ in float64 bits on the GPU
         head2global = e2g[head]
         rinv = _inverse3(head2global[:, :3, :3])
         global2head = torch.zeros_like(head2global)

@@ -298,3 +298,45 @@ def strided_copy(t):
     out = t.permute(0, 1, 3, 2).contiguous().permute(0, 1, 3, 2)
     assert not out.is_contiguous() and torch.equal(out, t)
     return out
+
+
+@pytest.mark.parametrize('shape', [(2, 3, 5, 7), (1, 2, 4, 8)])
+@pytest.mark.parametrize('half', [torch.float16, torch.bfloat16])
+def test_half_maps_under_their_autocast_are_the_float32_call(cuda, monkeypatch, shape, half):
+    """float16 maps under fp16 autocast, bfloat16 maps under bf16 autocast without ``keep_bf16``: ``shift_feature`` and
+    ``align_and_cat`` (one warped, one copied frame) run the float32 kernels forward and backward and give, bit for
+    bit, what they give outside autocast on the maps cast by hand; (2, 3, 5, 7) has an odd plane and takes the narrow
+    path, (1, 2, 4, 8) the 16-byte one."""
+    f = fixture()
+    n, c, h, w = shape
+    t = lambda k: torch.from_numpy(f[k][:n]).to(cuda)                                # noqa: E731
+    s2k = [t('b.curr'), t('b.adj')]
+    extra = (t('b.bda'), torch.from_numpy(f['b.grid_interval']), torch.from_numpy(f['b.grid_lower_bound']))
+    tf = temporal.feature_transform(s2k, *extra)
+    gen = torch.Generator().manual_seed(sum(shape))
+    maps = [torch.randn(shape, generator=gen).to(cuda).to(half).requires_grad_(True) for _ in range(2)]
+    wide = [m.detach().float().requires_grad_(True) for m in maps]
+    r = torch.randn(n, 2 * c, h, w, generator=gen).to(cuda)
+    want_cat = temporal.align_and_cat(wide, [1, 0], s2k, *extra, fused=True)
+    want_one = temporal.shift_feature(wide[0], tf)
+    (want_cat * r).sum().backward()
+    want_grads = [m.grad.clone() for m in wide]
+    wide[0].grad = None
+    (want_one * r[:, :c]).sum().backward()
+    calls = []
+    real = _lib.launch
+    monkeypatch.setattr(temporal._lib, 'launch', lambda name, *a, **k: calls.append(name) or real(name, *a, **k))
+    with torch.autocast('cuda', dtype=half):
+        got_cat = temporal.align_and_cat(maps, [1, 0], s2k, *extra, fused=True)
+        got_one = temporal.shift_feature(maps[0], tf)
+    assert calls == ['ocrf_bev_align_forward'] * 2
+    assert got_cat.dtype == got_one.dtype == torch.float32
+    assert torch.equal(got_cat, want_cat) and torch.equal(got_one, want_one)
+    assert torch.equal(got_cat[:, c:], maps[1].detach().float())                     # the key frame: a copy
+    (got_cat * r).sum().backward()
+    assert calls[2:] == ['ocrf_bev_align_backward']                                  # the float32 gather
+    # the float32 gradient, rounded once by the backward of the cast
+    assert all(m.grad.dtype == half and torch.equal(m.grad, g.to(half)) for m, g in zip(maps, want_grads))
+    maps[0].grad = None
+    (got_one * r[:, :c]).sum().backward()
+    assert calls[3:] == ['ocrf_bev_align_backward'] and torch.equal(maps[0].grad, wide[0].grad.to(half))

@@ -6,6 +6,9 @@ torch's bf16 element-wise ops widen to float32, add once and round once to neare
   specified); the backward is ``torch.where(out <= 0, 0, grad_out)`` bit for bit, NaN gradients included (a select).
   The pairs below do not hold -0 + -0: the kernels' ``s < 0 ? 0 : s`` keeps the sum's -0, as the float32 kernels do,
   where torch's ``relu`` on this device returns +0 (the float32 test counts signed zeros as equal for the same reason).
+  The kernel tests the float32 sum where torch tests the rounded one; the two have one sign, because a sum of two bf16
+  values is a multiple of the smallest bf16 denormal, 2^-133, and so does not round to zero.  The denormal pairs below,
+  (-1e-40, 3e-41) and (-2e-40, 1e-40) with their small negative sums among them, are the cases that would show otherwise.
 * ``upsample_add`` forward is ``dst + F.interpolate(src, mode='nearest')`` on bf16 tensors bit for bit, with the index
   maps of the float32 kernel (``rule``); a bf16 plane holds the codes 0..256 exactly.
 * ``upsample_add`` backward adds the k destinations of a source pixel sequentially in float32 and rounds once to bf16
