@@ -1493,6 +1493,56 @@ int ocrf_kd_losses_backward(int B, long long n, const float *s, const float *t, 
                             const float *grad_smooth, const float *grad_cos, float *grad_s, ocrf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Streaming object tracking (csrc/track_assoc.hip): one step of greedy closest-centre association (the scheme of
+ * CenterPoint's nuScenes tracker) for all B samples in ONE launch, on the padded output of the fused decode
+ * (CenterHead.get_bboxes_padded).  No host reads, no atomics, no workspace; reruns are bit-identical.
+ *
+ * Inputs (device): boxes (B, M, D) f32, D = 9 or 7 (bottom-centre z; D = 7: zero velocity); scores (B, M) f32; labels
+ *   (B, M) int32; counts (B) int32, clamped to [0, M] by the kernel; ego2global (B, 4, 4) f32, key ego -> global;
+ *   time_lag (B) f32, seconds since that sample's previous frame; new_sequence (B) bytes or NULL; max_dist (n_classes)
+ *   f32.  Host scalars: n_classes in [1, OCRF_TRACK_MAX_CLASSES], max_age >= 1, min_score, cap = max_age * M.
+ * State, double-buffered (`*_in` is read, `*_out` fully written: all cap slots, the ones past the new count with zeros;
+ *   no `_in` array may be its `_out` array): per track pos (2) f64 and vel (2) f64 in the global frame, label, id,
+ *   misses, hits int32, each (B, cap); per sample count (B) and next_id (B) int32.  count_in is clamped to [0, cap].
+ * Outputs: ids (B, M) and hits (B, M) int32; rows past counts[b] and untracked rows get id -1 and hits 0.
+ *
+ * A detection is untracked when its label is outside [0, n_classes), when max_dist[label] is not > 0, when
+ * score < min_score, or when its centre, z or (D = 9) velocity is not finite.
+ * Per tracked detection, in f64, one operation at a time in the order written, without contraction (E the widened
+ * ego2global, (x, y, z) = boxes[..., 0:3] as stored, dt the widened time_lag[b]):
+ *     gx = ((E00 x + E01 y) + E02 z) + E03,  gy likewise with row 1;
+ *     vgx = E00 vx + E01 vy,  vgy = E10 vx + E11 vy;      px = gx - vgx dt,  py = gy - vgy dt;
+ *     d2 = (tx - px) (tx - px) + (ty - py) (ty - py) against a stored track (tx, ty).
+ * A track is a candidate when it has the detection's label, is unclaimed and d2 <= r r, r the widened max_dist[label]
+ * (equality matches; no square root).  Matching is greedy in row order: each tracked detection takes the candidate of
+ * smallest d2, ties to the lowest slot, and claims it.  Only equal labels match, so the classes are independent.
+ * A matched detection keeps the track's id, hits = old hits + 1.  An unmatched one gets id = next_id[b] + rank (its
+ * position among the sample's unmatched tracked detections in row order) and hits = 1; next_id grows by their number
+ * (int32, no wrap-around handling).  An unmatched old track gets misses + 1, hits = 0 and pos += vel dt (a product, then
+ * a sum), and is kept iff its new misses < max_age.
+ * New state: first the tracked detections in row order (pos = (gx, gy), vel = (vgx, vgy), misses 0), then the kept old
+ * tracks in old slot order; a slot beyond cap is dropped (it cannot occur with a state this kernel wrote).
+ * A sample with new_sequence[b] != 0 starts from count 0 and keeps its next_id.
+ *
+ * Shape: one workgroup per sample, one wavefront per class (at least two, classes round-robin over the waves).  Each
+ * wave gathers its class's tracks in slot order into LDS, runs its greedy loop alone (the argmin is a cross-lane
+ * reduction over (d2, slot)), then one wave ranks the rows and one the old slots by ballot scans, and all threads write.
+ * ocrf_track_step_lds_bytes(M, cap): the dynamic LDS of the launch (32 M + 24 cap bytes), 0 for sizes that are not
+ * positive.  Limits: B in [1, 65535], M >= 1, cap == max_age * M, dynamic LDS <= OCRF_TRACK_MAX_LDS (64 KiB less the static words; M <= 627 at max_age 3),
+ * no NULL operand but new_sequence; anything else returns hipErrorInvalidValue and launches nothing.
+ */
+#define OCRF_TRACK_MAX_CLASSES 16
+#define OCRF_TRACK_MAX_LDS 65280
+size_t ocrf_track_step_lds_bytes(int M, int cap);
+int ocrf_track_step(int B, int M, int D, int n_classes, int max_age, float min_score, int cap, const float *boxes,
+                    const float *scores, const int *labels, const int *counts, const float *ego2global,
+                    const float *time_lag, const unsigned char *new_sequence, const float *max_dist,
+                    const double *pos_in, const double *vel_in, const int *label_in, const int *id_in,
+                    const int *misses_in, const int *hits_in, const int *count_in, const int *next_id_in,
+                    double *pos_out, double *vel_out, int *label_out, int *id_out, int *misses_out, int *hits_out,
+                    int *count_out, int *next_id_out, int *ids, int *hits, ocrf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-kernel device timer (measurement aid for bench.py; not part of the reference's surface)
  * ------------------------------------------------------------------------------------------
  * While a timer is armed for kernel id K, every launch of K inside the library is bracketed by
@@ -1629,7 +1679,8 @@ enum {
   OCRF_K_HOA1_WEIGHT_SUM = 154,       /* hoa1_weight_sum_kernel */
   OCRF_K_BEV_STREAM_ALIGN = 155,      /* bev_stream_align_kernel<float, V> */
   OCRF_K_BEV_STREAM_ALIGN_BF16 = 156, /* bev_stream_align_kernel<unsigned short, V> */
-  OCRF_K_CD_SELECT_BF16 = 157         /* cd_select_kernel<unsigned short> */
+  OCRF_K_CD_SELECT_BF16 = 157,        /* cd_select_kernel<unsigned short> */
+  OCRF_K_TRACK_STEP = 158             /* track_step_kernel */
 };
 const char *ocrf_kernel_name(int kernel_id);           /* symbol as rocprofv3 prints it */
 /* Diagnostic: a one-thread kernel that stores the device's constant-rate clock (wall_clock64, 100 MHz)

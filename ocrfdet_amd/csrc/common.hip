@@ -208,6 +208,7 @@ const char* ocrf_kernel_name(int kernel_id) {
     case OCRF_K_BEV_STREAM_ALIGN: return "bev_stream_align_kernel<*>";
     case OCRF_K_BEV_STREAM_ALIGN_BF16: return "bev_stream_align_kernel<unsigned short, *>";
     case OCRF_K_CD_SELECT_BF16: return "cd_select_kernel<unsigned short>";
+    case OCRF_K_TRACK_STEP: return "track_step_kernel";
     default: return "";
   }
 }

@@ -339,6 +339,17 @@ class OcRFDet4D(nn.Module):
         with torch.no_grad(), (self.bf16_inference() if bf16 else contextlib.nullcontext()):
             return self.pts_results(img_feats, img_metas, img_inputs[0].shape[0], rescale), state
 
+    def track_stream(self, img_inputs, state=None, tracks=None, time_lag=0.5, new_sequence=None, multi_frame=False,
+                     bf16=False, track_cfg=None):
+        """Streaming detection with identities: ``stream_step``, the head, ``get_bboxes_padded`` and one
+        ``tracking.track_step`` launch with camera 0's ``ego2global`` of the frame.  Returns ``(dict(boxes, scores,
+        labels, counts, ids, hits), state, tracks)``, everything on the device and padded (``tracking.results_to_host``
+        is the read-back); ``tracks`` is the ``tracking.TrackState`` to hand to the next step, ``time_lag`` the seconds
+        since the previous frame.  Takes the BEV augmentation as the identity, as at test time."""
+        from .tracking import track_stream
+        return track_stream(self, img_inputs, state=state, tracks=tracks, time_lag=time_lag, new_sequence=new_sequence,
+                            multi_frame=multi_frame, bf16=bf16, track_cfg=track_cfg)
+
     # ---------------------------------------------------------------- what a subclass overrides
     def frame_args(self, key_frame):
         """Hook of the frame loop: the positional arguments of this class's ``prepare_bev_feat`` behind the sixteen of
