@@ -335,7 +335,9 @@ class MfmaPoolPlan:
     unit list (a tile's panels in groups of at most ``group``; heaviest units first; tiles of several units reduce
     through slabs).  Built once per calibration from the rank vectors with device-side torch index algebra (sort /
     unique / searchsorted — plan time, not step time); every point of the rank vectors is pooled into
-    ``ranks_bev[p]`` (what the reference's intervals amount to when they cover the point list: bev_pool.py:40-57)."""
+    ``ranks_bev[p]`` (what the reference's intervals amount to when they cover the point list: bev_pool.py:40-57).
+    A non-finite value in a REFERENCED feature row or depth entry spreads over its whole tile in the dense W . F form
+    (0 * inf = NaN), by construction; rows and entries that no kept point references are never read into a sum."""
 
     def __init__(self, ranks_depth, ranks_feat, ranks_bev, bev_feat_shape, group=4, unit_cost=None):
         _lib.require_cuda(ranks_depth, ranks_feat, ranks_bev)
