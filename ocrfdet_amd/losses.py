@@ -153,9 +153,12 @@ def depth_semantic_loss(depth_labels, depth_preds, semantic_labels, semantic_pre
 # --------------------------------------------------------------------------------------------- box mask
 def box_bounds(boxes, W, H):
     """Box2dtoMask's slices of (n,4) boxes for an image of W x H: (y0, y1, x0, x1) long tensors after the float32
-    scaling by W / 1600 (the y coordinates too), int() truncation, the -158 shift of y and Python's slice rules."""
+    scaling by W / 1600 (the y coordinates too), int() truncation, the -158 shift of y and Python's slice rules.
+    NaN and anything below -9e18 count as -9e18, anything above 9e18 as 9e18 (``trunc_ll`` of csrc/losses.hip): the
+    conversion of such a float to an integer differs between devices, and INT64_MIN - 158 would wrap to a large
+    positive bound."""
     scale = torch.tensor(W / _ORIG_W, dtype=torch.float32, device=boxes.device)
-    s = (boxes.float() * scale).trunc().long()
+    s = torch.nan_to_num(boxes.float() * scale, nan=-9e18, posinf=9e18, neginf=-9e18).clamp(-9e18, 9e18).trunc().long()
 
     def norm(v, L):
         v = torch.where(v < 0, v + L, v)
