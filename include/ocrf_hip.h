@@ -1543,6 +1543,95 @@ int ocrf_track_step(int B, int M, int D, int n_classes, int max_age, float min_s
                     int *count_out, int *next_id_out, int *ids, int *hits, ocrf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * nuScenes detection metrics (csrc/det_eval.hip; ocrfdet_amd/detection_eval.py is the caller): AP over centre-distance
+ * thresholds, the five true-positive errors, mAP and NDS of `detection_cvpr_2019`, from the padded output of the fused
+ * decode and padded ground truth, accumulated batch by batch without a host read.  The rules below are written from
+ * the benchmark's published procedure; they are the specification here (tests/eval_oracle.py restates them
+ * sequentially), they have not been compared with the nuScenes devkit's own output.
+ *
+ * Inputs per batch (device), all in the key frame's ego frame: boxes (B, M, D) f32, D = 9 or 7, columns (x, y, z, w, l,
+ *   h, yaw[, vx, vy]); scores (B, M) f32; labels (B, M) int32; counts (B) int32, clamped to [0, M]; gt_boxes (B, G, D)
+ *   f32 in the same columns; gt_labels (B, G) int32; gt_counts (B) int32, clamped to [0, G]; gt_attrs (B, G) int32 or
+ *   NULL, -1 = none; gt_valid (B, G) bytes or NULL (0 = not evaluated).  Tables: class_range (n_classes) f32 metres;
+ *   class_tab (n_classes, 3) int32 = (attribute of a moving prediction, of a still one, -1 = none; flags:
+ *   OCRF_DET_EVAL_HALF_TURN the yaw period is pi, _NO_ORIENT / _NO_VEL / _NO_ATTR the class has no such error).
+ *   Host scalars: th (4) f64 the distance thresholds, tp_index in [0, 4) the one whose matches carry the errors,
+ *   sample_index the number of samples accumulated before this batch, capacity the samples the buffers hold.
+ *
+ * Evaluated: a box whose label is in [0, n_classes), whose x, y, z (and score, for a prediction) are finite, whose
+ *   gt_valid byte (ground truth) is not 0 and for which x x + y y < r r in f64 (a product, a product, a sum), r the
+ *   widened class_range[label].  Centre distances, yaw and velocity differences and speeds are invariant under the
+ *   rigid ego -> global map, so no pose is needed.
+ * Predicted attribute: class_tab[label][0] when vx vx + vy vy > 0.2 0.2 in f64 (0.2 the double), else [1]; D = 7: [1].
+ * Matching, per sample, class and threshold t = th[k]: the evaluated predictions of the class in descending score
+ *   (-0 counts as +0), ties to the lowest row, each take the unclaimed evaluated ground truth of the class with the
+ *   smallest d2 = dx dx + dy dy, dx = px - gx, dy = py - gy in f64, ties to the lowest index; the prediction is a
+ *   true positive iff d2 < t t (strict) and then claims the box, else a false positive.  Four separate claim sets.
+ * Errors of a prediction matched at th[tp_index], in f64, one operation at a time in the order written:
+ *   trans  sqrt(d2)
+ *   scale  1 - i / ((vp + vg) - i), i = (min(w) min(l)) min(h), v = (w l) h
+ *   orient |a|, a = m - P / 2 with m = fmod((yaw_g - yaw_p) + P / 2, P), plus P when negative; a less 2 pi when a > pi;
+ *          P = pi with OCRF_DET_EVAL_HALF_TURN, else 2 pi (the doubles nearest pi and 2 pi)
+ *   vel    sqrt(dvx dvx + dvy dvy), dv = v_p - v_g; NaN when D = 7 or a ground-truth velocity component is NaN
+ *   attr   0 when the predicted attribute equals gt_attrs, else 1; NaN when gt_attrs is NULL or -1
+ * Record of slot (sample_index + b) M + row: key (u32: ~o, o the score's bits with the sign bit flipped when it is
+ *   clear and all bits flipped when it is set, so that ascending keys are descending scores; 0xFFFFFFFF when not evaluated), info
+ *   (int32: class | OCRF_DET_EVAL_EVALUATED | tp bits << 8; class 31 and nothing else when not evaluated), match (4
+ *   int32: the claimed ground-truth index per threshold, -1 none), err (5 f64 in the order above, NaN when unmatched).
+ *   gt_count[(sample_index + b) n_classes + c]: the evaluated ground truth of class c.  Every slot of the batch and
+ *   every count is written on each call.
+ * ocrf_det_eval_match: ONE launch, one workgroup per sample, one wavefront per class (at least two, classes
+ *   round-robin over the waves); no atomics, no workspace, reruns bit-identical.  ocrf_det_eval_match_lds_bytes(M, G):
+ *   its dynamic LDS (52 M + 28 G + 128 bytes), 0 for sizes that are not positive.  Limits: B in [1, 65535], M, G >= 1, D in
+ *   {7, 9}, n_classes in [1, OCRF_DET_EVAL_MAX_CLASSES], 0 <= sample_index, sample_index + B <= capacity, capacity M
+ *   < 2^31, dynamic LDS <= OCRF_DET_EVAL_MAX_LDS, finite th, no NULL operand but gt_attrs and gt_valid; anything else
+ *   returns hipErrorInvalidValue and launches nothing.
+ *
+ * Summary over the first n_samples samples (n = n_samples M slots).  Global order per class: descending score, ties
+ *   by slot (sample in order of arrival, then row): a stable LSD sort by key, then by class.  Per class c with its n_c
+ *   evaluated predictions in that order and npos = the sum of its gt_count, per threshold, in f64 as numpy defines
+ *   cumsum, linspace and interp:
+ *     tp, fp the cumulative counts; prec = tp / (tp + fp); rec = tp / npos; conf the widened scores;
+ *     rec_interp[j] = j 0.01 (j = 100: 1); prec_i = interp(rec_interp, rec, prec, right = 0), conf_i likewise;
+ *     AP = (sum_j=first..100 max(prec_i[j] - min_precision, 0)) / (101 - first) / (1 - min_precision), summed in order;
+ *   per error e over the K matches of th[tp_index] (conf_m, e_m in that order): cm[k] = (sum of the non-NaN e_m[0..k])
+ *     / their number, 0 where that number is 0, all ones when every e_m is NaN; err_i = interp(conf_i, conf_m, cm)
+ *     taken over the reversed (ascending) arrays; TP metric = the mean of err_i[first .. last], summed in order, last
+ *     the largest j with conf_i[j] != 0 (0 when none); 1 when last < first.
+ *   npos = 0 or n_c = 0: AP 0, errors 1.  K = 0: errors 1.  A class with _NO_ORIENT / _NO_VEL / _NO_ATTR: NaN there.
+ *   mAP = the mean over classes of the mean over thresholds; mTP_e = the mean over the classes where it is not NaN (NaN
+ *   when none); NDS = (5 mAP + sum_e (1 - min(1, mTP_e))) / 10, a NaN mTP_e counting as 1.
+ * ocrf_det_eval_summary: copies the keys, sorts them and the classes (radix driver), gathers order / sorted_cls / the
+ *   TP flags, scans the flags (look-back scan, one per threshold), one curve launch of (n_classes, 9) workgroups (the
+ *   NaN-aware sums run as a fixed-order f64 prefix inside it: 128-wide chunks in sequence, a shuffle scan in each)
+ *   and one final workgroup.  Outputs: order (n) int32 slots, sorted_cls (n) int32 (class; 16 for what is not
+ *   evaluated, sorted last), tp_excl (4, n) int32 exclusive prefix of the TP flags over the whole order, result
+ *   (9 n_classes + 7) f64 = AP (n_classes, 4), errors (n_classes, 5), mAP, mTP (5), NDS.  A look-back scan that gave up
+ *   turns every result into NaN (the gather clamps the sort's ids into [0, n), so nothing is read out of bounds then).  Reads nothing back.  Limits: n_samples >= 1, n < 2^31, first in [1, 100],
+ *   min_precision in [0, 1), a workspace of ocrf_det_eval_summary_workspace_bytes(n) bytes (0 for such n), 256-byte
+ *   aligned; anything else returns hipErrorInvalidValue and launches nothing.
+ */
+#define OCRF_DET_EVAL_MAX_CLASSES 16
+#define OCRF_DET_EVAL_MAX_LDS 65024
+#define OCRF_DET_EVAL_EVALUATED 32
+#define OCRF_DET_EVAL_HALF_TURN 1
+#define OCRF_DET_EVAL_NO_ORIENT 2
+#define OCRF_DET_EVAL_NO_VEL 4
+#define OCRF_DET_EVAL_NO_ATTR 8
+size_t ocrf_det_eval_match_lds_bytes(int M, int G);
+int ocrf_det_eval_match(int B, int M, int D, int G, int n_classes, long long sample_index, long long capacity,
+                        double th0, double th1, double th2, double th3, int tp_index, const float *boxes,
+                        const float *scores, const int *labels, const int *counts, const float *gt_boxes,
+                        const int *gt_labels, const int *gt_counts, const int *gt_attrs, const unsigned char *gt_valid,
+                        const float *class_range, const int *class_tab, unsigned *rec_key, int *rec_info,
+                        int *rec_match, double *rec_err, int *gt_count, ocrf_stream_t stream);
+size_t ocrf_det_eval_summary_workspace_bytes(long long n_slots);
+int ocrf_det_eval_summary(long long n_samples, int M, int n_classes, int tp_index, int first, double min_precision,
+                          const unsigned *rec_key, const int *rec_info, const double *rec_err, const int *gt_count,
+                          const int *class_tab, int *order, int *sorted_cls, int *tp_excl, double *result,
+                          void *workspace, size_t workspace_bytes, ocrf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-kernel device timer (measurement aid for bench.py; not part of the reference's surface)
  * ------------------------------------------------------------------------------------------
  * While a timer is armed for kernel id K, every launch of K inside the library is bracketed by
@@ -1680,7 +1769,13 @@ enum {
   OCRF_K_BEV_STREAM_ALIGN = 155,      /* bev_stream_align_kernel<float, V> */
   OCRF_K_BEV_STREAM_ALIGN_BF16 = 156, /* bev_stream_align_kernel<unsigned short, V> */
   OCRF_K_CD_SELECT_BF16 = 157,        /* cd_select_kernel<unsigned short> */
-  OCRF_K_TRACK_STEP = 158             /* track_step_kernel */
+  OCRF_K_TRACK_STEP = 158,            /* track_step_kernel */
+  OCRF_K_DET_EVAL_MATCH = 159,        /* det_eval_match_kernel */
+  OCRF_K_DET_EVAL_GATHER = 160,       /* det_eval_gather_kernel */
+  OCRF_K_DET_EVAL_CURVES = 161,       /* det_eval_curves_kernel */
+  OCRF_K_DET_EVAL_FINAL = 162,        /* det_eval_final_kernel */
+  OCRF_K_DET_EVAL_COPY_KEYS = 163,    /* det_eval_copy_keys_kernel */
+  OCRF_K_DET_EVAL_CLASS_KEYS = 164    /* det_eval_class_keys_kernel */
 };
 const char *ocrf_kernel_name(int kernel_id);           /* symbol as rocprofv3 prints it */
 /* Diagnostic: a one-thread kernel that stores the device's constant-rate clock (wall_clock64, 100 MHz)

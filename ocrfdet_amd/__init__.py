@@ -44,6 +44,9 @@ Drop-in mirrors of the reference's Python surface for that path (and nothing els
   ...detectors.bevdet_vggt.CrossAttentionAlign    (build_cost_volume, group_corr_volume, group_corr_volume_torch,
                                                   kd_losses, kd_losses_torch, CrossAttentionAlign, resize_img,
                                                   get_pair_indices; the VGGT teacher itself is passed in)
+  ...datasets.nuscenes_dataset                    ocrfdet_amd.detection_eval (EvalConfig, DetectionEval,
+  NuScenesDataset.evaluate (the metrics, not the  evaluate_host, evaluate_stream; OcRFDet4D.evaluate_stream): AP,
+  devkit's JSON submission)                       the TP errors, mAP and NDS from padded device tensors
   ==============================================  =================================================
 
 Every op calls the C ABI of ``csrc/libocrf_hip.so`` (``include/ocrf_hip.h``) through ctypes with

@@ -209,6 +209,12 @@ const char* ocrf_kernel_name(int kernel_id) {
     case OCRF_K_BEV_STREAM_ALIGN_BF16: return "bev_stream_align_kernel<unsigned short, *>";
     case OCRF_K_CD_SELECT_BF16: return "cd_select_kernel<unsigned short>";
     case OCRF_K_TRACK_STEP: return "track_step_kernel";
+    case OCRF_K_DET_EVAL_MATCH: return "det_eval_match_kernel";
+    case OCRF_K_DET_EVAL_GATHER: return "det_eval_gather_kernel";
+    case OCRF_K_DET_EVAL_CURVES: return "det_eval_curves_kernel";
+    case OCRF_K_DET_EVAL_FINAL: return "det_eval_final_kernel";
+    case OCRF_K_DET_EVAL_COPY_KEYS: return "det_eval_copy_keys_kernel";
+    case OCRF_K_DET_EVAL_CLASS_KEYS: return "det_eval_class_keys_kernel";
     default: return "";
   }
 }

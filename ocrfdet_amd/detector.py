@@ -350,6 +350,15 @@ class OcRFDet4D(nn.Module):
         return track_stream(self, img_inputs, state=state, tracks=tracks, time_lag=time_lag, new_sequence=new_sequence,
                             multi_frame=multi_frame, bf16=bf16, track_cfg=track_cfg)
 
+    def evaluate_stream(self, frames_with_gt, evaluator, state=None, multi_frame=False, bf16=False):
+        """Streaming detection into the nuScenes detection metrics: per ``(img_inputs, gt)`` one ``stream_step``, the
+        head, ``get_bboxes_padded`` and one ``detection_eval.DetectionEval.update`` launch; ``gt``: ``dict(gt_boxes,
+        gt_labels, gt_counts[, gt_attrs][, gt_valid][, new_sequence])`` on the device, in the key frame's ego.  Returns
+        ``(evaluator, state)``: ``evaluator.results_to_host()`` is the one read-back, ``state`` the stream state for
+        the next call.  Takes the BEV augmentation as the identity."""
+        from .detection_eval import evaluate_stream
+        return evaluate_stream(self, frames_with_gt, evaluator, state=state, multi_frame=multi_frame, bf16=bf16)
+
     # ---------------------------------------------------------------- what a subclass overrides
     def frame_args(self, key_frame):
         """Hook of the frame loop: the positional arguments of this class's ``prepare_bev_feat`` behind the sixteen of
